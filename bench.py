@@ -13,9 +13,18 @@ embeddings, padding masks and the [B,N,T] timestamp mask derived from the batch'
 that depends on the model -- and all of get_loss, including its positive masks and the column compaction -- runs every step).  Multi-GPU shards
 by video (weak scaling: every rank its own 128 videos), one all-reduce of the flat gradient per step.
 
-Prints ONE JSON line (rank 0): value = whole-job video-seq/s; `roofline` = the dominant kernel (the MFMA GEMM family)
-timed live with HIP events on its own stream inside the timed steps; `cpu_baseline` = the CPU oracle (oracle/, a PyTorch
-CPU restatement of the reference pinned to reference-generated goldens) on a bounded sample of the same workload.
+Prints ONE JSON line (rank 0): value = whole-job video-seq/s, ms_per_step = the mean of the K timed steps.  A plain run does only
+that: W untimed warm-up steps, K timed steps, the line.  `--dump-outputs DIR` then writes what the last timed step computed (its loss
+dict, and fixed seeded samples of the updated parameters and of the step's gradients) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.  The step runs at learning rate 0 (the same kernels and the same
+work: see run_config), so the parameters -- and with them every step's inputs -- stay the same; runs differ only by the rounding of
+one step's f32 gradient atomics.
+
+`--full` adds everything else the benchmark measures: the extra untimed warm-up until the step time is steady (`--settle-s`; its step
+count varies from run to run), `roofline` = the dominant kernel (the MFMA GEMM family) timed live with HIP events on its own stream
+inside the timed steps plus an `isolated` reading in extra steps, the `extra` configurations, the `comm` block of a data-parallel run,
+and `cpu_baseline` = the CPU oracle (oracle/, a PyTorch CPU restatement of the reference pinned to reference-generated goldens) on a
+bounded sample of the same workload.
 """
 import argparse
 import ctypes as C
@@ -64,10 +73,35 @@ def parse():
     ap.add_argument("--timer-stride", type=int, default=4, help="the kernel timer brackets every n-th launch of the MFMA family in the sampled step")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra driver-timed configurations (stage 2, len=256) of the N=1 run")
     ap.add_argument("--extra-steps", type=int, default=10)
-    ap.add_argument("--settle-s", type=float, default=2.0, help="bound [s] of the extra untimed warm-up that runs until the step time is "
-                    "steady (two consecutive steps and two consecutive 4-step blocks within 1 %%); 0 = only --warmup")
+    ap.add_argument("--settle-s", type=float, default=2.0, help="--full: bound [s] of the extra untimed warm-up that runs until the step "
+                    "time is steady (two consecutive steps and two consecutive 4-step blocks within 1 %%); 0 = only --warmup")
     ap.add_argument("--with-lm", action="store_true", help="the step starts from token ids (Word2Vec embedder inside it, train/main.py:55-65)")
+    ap.add_argument("--full", action="store_true", help="also the settle warm-up, kernel timer / roofline, extra configurations, comm "
+                    "block and CPU baseline (the --no-* / --settle-s / --timer-* / --extra-steps / --cpu-* options act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 22          # elements kept of each large output (16 MB in float32)
+
+
+def dump_outputs(out_dir, loss, model):
+    """What a caller of `Trainer.step` receives from the last timed step: the loss dict, the updated parameters and the gradients the
+    step left in `p.grad` (zeros where a parameter has none), each flattened in `named_parameters` order.  The two flat vectors are
+    sampled at DUMP_SAMPLE fixed seeded positions; float32 throughout."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in loss.items():
+        v = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+    params = [p for _, p in model.named_parameters()]                # (waits for what a pipelined step left running)
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params]).float()
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params]).float()
+    for name, flat, seed in (("params_sample", flat_p, 1), ("grads_sample", flat_g, 2)):
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat.cpu().numpy())
 
 
 def cpu_baseline(a, args_ns):
@@ -146,13 +180,18 @@ def traffic_profile(stage, batch_size, seq_len):
 
 
 def run_config(a, world, rank, dev, stage, batch_size, seq_len, steps, warmup, timer_every, ddp_mode=None, global_negatives=None,
-               with_lm=False, grad_dtype=None):
-    """One configuration: W untimed + K timed steps between barriers; returns the result fields (no printing)."""
+               with_lm=False, grad_dtype=None, dump_dir=None):
+    """One configuration: W untimed + K timed steps between barriers; returns the result fields (no printing).  Without `a.full`
+    nothing else runs: no settle steps, no kernel timer, no collective timing."""
     from temporalalignnet_amd import _lib, dist, synth
     from temporalalignnet_amd.train import Trainer, build_model, default_args, to_device_batch
+    # lr = 0: AdamW still reads and writes every parameter, moment and weight image (no path tests the rate), but the parameters come
+    # out bit-identical, so every step computes from the same inputs.  At lr > 0 on this repeated batch the run-dependent order of the
+    # f32 gradient atomics, re-rounded into the bf16 weight images, compounds from step to step and two runs drift apart.
     args_ns = default_args(model="init" if stage == 1 else "cotrain", num_encoder_layers=a.layers, num_decoder_layers=a.layers,
-                           loss_threshold=0.0 if stage == 1 else 0.5, seq_len=seq_len)
+                           loss_threshold=0.0 if stage == 1 else 0.5, seq_len=seq_len, lr=0.0)
     torch.manual_seed(888)
+    np.random.seed(888)                  # (stage 1's random position starts draw from numpy's global stream)
     gneg = a.global_negatives if global_negatives is None else global_negatives
     model = build_model(args_ns, compute_dtype=a.dtype, language_model="word2vec" if with_lm else None).to(dev)
     if stage == 1:
@@ -163,8 +202,8 @@ def run_config(a, world, rank, dev, stage, batch_size, seq_len, steps, warmup, t
         trainer.ddp_mode = ddp_mode
     if grad_dtype is not None:
         trainer.ddp_grad_dtype = grad_dtype
-    trainer.time_comm = dist.active()
-    trainer.batches_seen = 1000                                          # past warm-up: non-zero learning rate
+    trainer.time_comm = dist.active() and a.full
+    trainer.batches_seen = 1000                                          # past warm-up: the schedule's full rate (x lr = 0)
     trainer.iteration = 1000
     if stage == 2:
         model._copy_param()
@@ -180,10 +219,10 @@ def run_config(a, world, rank, dev, stage, batch_size, seq_len, steps, warmup, t
 
     for _ in range(warmup):                                              # (the first step broadcasts rank 0's parameters)
         trainer.step(batch)
-    settle = settle_steps(trainer, batch, dev) if a.settle_s > 0 else 0
+    settle = settle_steps(trainer, batch, dev) if a.full and a.settle_s > 0 else 0
     trainer.comm_events.clear()
     L = _lib.lib()
-    use_timer = not a.no_kernel_timer
+    use_timer = a.full and not a.no_kernel_timer
     if use_timer:
         _lib.check(L.tan_prof_enable(1, 1200 * max(steps, 1)), "tan_prof_enable")
         L.tan_prof_stride(a.timer_stride)        # inside the timed steps: every n-th launch of the family (an event pair costs 8-14 us)
@@ -208,8 +247,10 @@ def run_config(a, world, rank, dev, stage, batch_size, seq_len, steps, warmup, t
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
     srt = sorted(step_ms)
     final_loss = float(loss["loss"].item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, loss, model)       # (before the `isolated` reading of --full steps the model further)
     comm = None
-    if dist.active():
+    if dist.active() and a.full:
         import torch.distributed as tdist
         exposed = [e0.elapsed_time(e1) for e0, e1 in trainer.comm_events]
         alone = trainer.allreduce_alone_ms()
@@ -330,9 +371,10 @@ def main():
     dev = torch.device("cuda", local)
     global SETTLE_S
     SETTLE_S = a.settle_s
-    head, args_ns = run_config(a, world, rank, dev, a.stage, a.batch, a.seq_len, a.steps, a.warmup, a.timer_every, with_lm=a.with_lm)
+    head, args_ns = run_config(a, world, rank, dev, a.stage, a.batch, a.seq_len, a.steps, a.warmup, a.timer_every, with_lm=a.with_lm,
+                               dump_dir=a.dump_outputs)
     extra = []
-    headline = (a.stage, a.batch, a.seq_len) == (1, 128, 64) and not a.with_lm
+    headline = (a.stage, a.batch, a.seq_len) == (1, 128, 64) and not a.with_lm and a.full
     if world == 1 and not dist.active() and headline and not a.no_extra and a.dtype == "bf16":
         # BASELINE configs[2] (stage-2 co-training, here on one GPU at the per-GPU batch) and configs[3] (len=256) are
         # driver-timed too, each with its own roofline; shorter runs (the headline keeps the driver's K / W).  VERDICT r2: the
@@ -373,7 +415,7 @@ def main():
             out["comm"] = head["comm"]
         if extra:
             out["extra"] = extra
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a, args_ns)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

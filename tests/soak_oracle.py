@@ -8,7 +8,7 @@ selected sentence -> pos_weight = 1/0 - 1), and the updated parameters must agre
 import os
 import sys
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch
 

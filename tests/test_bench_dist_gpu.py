@@ -17,8 +17,8 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 def test_bench_line_under_forced_dist_has_comm_and_every_variant():
     env = dict(os.environ, TAN_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("TAN_DDP_MODE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--extra-steps", "2", "--settle-s", "0",
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--extra-steps", "2",
+                        "--settle-s", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -54,7 +54,7 @@ def test_bench_two_ranks_through_its_own_launcher():
                TAN_DIST_BACKEND="gloo", TAN_DIST_SHARE_GPU="1")
     for k in ("TAN_DDP_MODE", "TAN_FORCE_DIST", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extra",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extra",
                         "--settle-s", "0", "--batch", "32"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

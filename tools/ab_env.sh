@@ -4,7 +4,7 @@
 VAR=$1; A=$2; B=$3; ROUNDS=${4:-2}; shift 4
 for r in $(seq 1 $ROUNDS); do
   for v in $A $B $B $A; do
-    ms=$(env $VAR=$v python bench.py --warmup 5 --steps 30 --no-cpu-baseline --no-extra "$@" 2>/dev/null | python -c 'import sys,json
+    ms=$(env $VAR=$v python bench.py --full --warmup 5 --steps 30 --no-cpu-baseline --no-extra "$@" 2>/dev/null | python -c 'import sys,json
 for l in sys.stdin:
     if l.startswith("{"): print(json.loads(l)["ms_per_step"])')
     echo "$VAR=$v $ms ms/step"

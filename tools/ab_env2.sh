@@ -3,7 +3,7 @@
 VAR=$1; A=$2; B=$3; ROUNDS=${4:-2}; STEPS=${5:-80}
 for r in $(seq 1 $ROUNDS); do
   for v in $A $B $B $A; do
-    env $VAR=$v python bench.py --warmup 5 --steps $STEPS --no-cpu-baseline --no-extra --no-kernel-timer 2>/dev/null | python -c '
+    env $VAR=$v python bench.py --full --warmup 5 --steps $STEPS --no-cpu-baseline --no-extra --no-kernel-timer 2>/dev/null | python -c '
 import sys,json
 for l in sys.stdin:
     if l.startswith("{"):

@@ -3,7 +3,7 @@
 A=$1; B=$2; ROUNDS=${3:-2}
 for r in $(seq 1 $ROUNDS); do
   for v in $A $B $B $A; do
-    TAN_HIP_LIB=$PWD/$v python bench.py --warmup 5 --steps 60 --no-cpu-baseline --no-extra --no-kernel-timer 2>/dev/null | python -c '
+    TAN_HIP_LIB=$PWD/$v python bench.py --full --warmup 5 --steps 60 --no-cpu-baseline --no-extra --no-kernel-timer 2>/dev/null | python -c '
 import sys,json
 for l in sys.stdin:
     if l.startswith("{"):

@@ -1,6 +1,6 @@
 """Lists the distinct tan_gemm calls one training step makes from Python (shape, layouts, batch, K slices).  Tool only."""
 import sys, os, collections
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import torch
 from temporalalignnet_amd import synth, ops
 from temporalalignnet_amd.train import Trainer, build_model, default_args, to_device_batch

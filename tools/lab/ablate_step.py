@@ -1,7 +1,7 @@
 """Which parts of a training step are on its critical path: un-synchronised steps with single pieces switched off (results are
 WRONG in those variants: timing only).  Tool only."""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))
 import torch
 from temporalalignnet_amd import synth
 from temporalalignnet_amd.train import Trainer, build_model, default_args, to_device_batch

@@ -1,6 +1,6 @@
 """Stand-alone time of the attention core at one shape (bf16): fwd, bwd.  env B, L; TAN_ATTN_MID=0 for the streamed kernels."""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))
 import torch
 from temporalalignnet_amd import ops
 B, L, H, C = int(os.environ.get("B", 32)), int(os.environ.get("L", 272)), 8, 512

@@ -1,7 +1,7 @@
 """Lab: the text-feature gradient of the NCE backward, d_tn[s] = dl[s]^T vn[s]  ([Mc x R] x [R x 512] per stage), as the tiled GEMM
 it is today vs the 256 x 256-tile weight-gradient kernel (tan_linear_wgrad_group).  Tool only."""
 import ctypes as C, os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..")))
 import torch
 from temporalalignnet_amd import _lib, ops
 L = _lib.lib()

@@ -4,8 +4,8 @@ import ctypes as C
 import os
 import sys
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", "..")))
+sys.path.insert(0, os.path.join(os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", "..")), "tests"))
 import torch
 from temporalalignnet_amd import _lib, ops
 from test_panel_gpu import pack

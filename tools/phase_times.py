@@ -2,7 +2,7 @@
 get_loss issued, backward issued, optimizer issued), averaged over steps.  The host runs ahead, so a phase's event interval is the
 GPU's time for it (side streams join the main stream inside each phase).  Tool only."""
 import sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import torch
 from temporalalignnet_amd import synth, loss as L
 from temporalalignnet_amd import train as TR

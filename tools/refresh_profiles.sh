@@ -3,9 +3,9 @@
 # then `bash tools/install_profiles.sh r06` copies gpurun_out/refresh/* over profiles/r06_*.  Counters are collected in their own passes (--pmc with --kernel-trace only).
 set -x
 R=$PWD; O=$R/gpurun_out/refresh; rm -rf $O; mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python $R/bench.py --steps 10 --warmup 3 --settle-s 0 --no-cpu-baseline --no-extra > $O/under_rocprof.json 2> $O/under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python $R/bench.py --full --steps 10 --warmup 3 --settle-s 0 --no-cpu-baseline --no-extra > $O/under_rocprof.json 2> $O/under_rocprof.err
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --steps 10 --warmup 5 --settle-s 0 --no-cpu-baseline --no-kernel-timer --no-extra > /dev/null 2> $O/pmc_$c.err

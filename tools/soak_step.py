@@ -10,7 +10,7 @@ SOAK_BIG=1 adds B = 48 ... 128; SOAK_STAGE2=1 soaks the co-training step instead
 import os
 import sys
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 import torch
 

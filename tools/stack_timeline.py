@@ -6,7 +6,7 @@ import os
 import sys
 import threading
 
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import torch
 
 from temporalalignnet_amd import synth

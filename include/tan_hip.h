@@ -650,6 +650,33 @@ int tan_attnblk_fwd_split(const tan_attnblk_desc* d, float* part, void* stream);
  * tan_attnblk_fwd, or NULL (default): no instrumentation */
 int tan_attnblk_lab_set_dbg(void* device_buffer);
 
+/* ---- corpus auto-alignment (HTM-AA inference; the evaluation loop of eval/eval_zeroshot_align.py:129-223 over MANY videos) ----
+ * Videos, sentences and windows of a chunk are packed: video features [sum vlen, Dv], sentence embeddings [sum K, Dt], and an
+ * int32 window table of TAN_WIN_FIELDS per window, in plan order (videos in chunk order, windows by start time):
+ *   vrow (packed frame row of s0), t (= e0 - s0), krow (packed sentence row of the first active sentence), k (active sentences),
+ *   s0, vlen, aoff (the video's first element in the [K, vlen] accumulators), kbase (packed row of the video's sentence 0).
+ * A pass is a contiguous slice of the table (W windows, pointer offset by the caller).                                         */
+#define TAN_WIN_FIELDS 8
+/* One pass's model input in one launch: out_video [W, T, Dv] (frames beyond t zero), out_vmask [W, T] bytes (1 = padding),
+ * out_text [W, Kp, Dt] (rows beyond k zero), out_tmask [W, Kp] -- the slicing of train/main.py:171-189's per-window calls,
+ * stacked.  A bit copy: *_elem_bytes = 2 (f16 / bf16) or 4 (f32), the outputs have the inputs' element type.                   */
+int tan_window_pack(const void* video, int video_elem_bytes, int Dv, const void* text, int text_elem_bytes, int Dt,
+                    const int* table, int W, int T, int Kp, void* out_video, unsigned char* out_vmask, void* out_text,
+                    unsigned char* out_tmask, void* stream);
+/* acc_j / acc_d [sum K*vlen] += the pass's last-stage joint / dual similarities x (1/0.07) (eval_zeroshot_align.py:197-201),
+ * cnt += 1 over each window's [k, t] block; tcnt [sum K] += 1 per window holding the sentence and, with the alignability head
+ * (a_joint = the joint stage-2 head logits [W, Kp], eval_zeroshot_align.py:186), a_sum [sum K] += them.  sim_j / sim_d: one
+ * stage of eval_windows' output, [W, T, Kp] f32.  Each element adds its windows in window order (no atomics): f32-identical to
+ * the host loop, however the windows are cut into passes.  a_joint and a_sum are both NULL without the head.                    */
+int tan_window_stitch_acc(const float* sim_j, const float* sim_d, const float* a_joint, const int* table, int W, int T, int Kp,
+                          float* acc_j, float* acc_d, float* cnt, long n_acc, float* tcnt, float* a_sum, long n_rows,
+                          void* stream);
+/* Per sentence row g (rows [n_rows, 2] int32 = accumulator offset, vlen): acc_j row <- sim = (acc_j/max(cnt,1e-5) +
+ * acc_d/max(cnt,1e-5)) / 2, 0 -> -6e4 (eval_zeroshot_align.py:199-205,221); res [4, n_rows] f32 = first arg-max of the row,
+ * max of its softmax over time, score (a_sum / max(tcnt, 1e-5) with the head, else the row max, :219-223), tcnt > 0.          */
+int tan_window_stitch_final(float* acc_j, const float* acc_d, const float* cnt, const float* tcnt, const float* a_sum,
+                            const int* rows, long n_rows, long n_acc, float* res, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

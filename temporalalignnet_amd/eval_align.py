@@ -83,6 +83,42 @@ def make_batched_sim_fn(model, embed_text, use_alignability_head=True, max_windo
     return run
 
 
+def plan_windows(start, end, vlen, seq_len=64, candidates=None, *, max_sentences=None, vid=None):
+    """The windows of one video, as eval/eval_zeroshot_align.py:129-170 forms them: [(s0, e0, left, right_excl)].
+
+    Window starts are `arange(0, vlen - seq_len // 2, seq_len // 4)`; a window is active when the midpoint of at least one CANDIDATE
+    sentence lies in [s0 - seq_len, s0 + 2 * seq_len], and then holds the sentences left..right of the active ones (every sentence in
+    between, candidate or not).  Edge rule: the first four windows start at sentence 0, the last four run to the end (`right = vlen`,
+    so a slice up to vlen + 1 -- every sentence when K <= vlen + 1).  e0 = min(vlen, s0 + seq_len).  `candidates` (bool [K]): the
+    evaluation passes the NON-alignable sentences (~aligned, no ground-truth leak); None = every sentence (corpus inference).
+    `max_sentences`: a window holding more sentences than the joint stack accepts raises ValueError naming `vid` (sentences are
+    never dropped silently)."""
+    start, end = np.asarray(start, dtype=np.float64), np.asarray(end, dtype=np.float64)
+    K = len(start)
+    cand = np.ones(K, bool) if candidates is None else np.asarray(candidates).astype(bool)
+    steps = np.arange(0, vlen - seq_len // 2, seq_len // 4)
+    mid = (start + end) / 2
+    c_idx, c_mid = np.arange(K)[cand], mid[cand]
+    out = []
+    for i, s0 in enumerate(steps):
+        act = c_idx[(s0 - seq_len <= c_mid) & (c_mid <= s0 + 2 * seq_len)]
+        if len(act) == 0:
+            continue
+        left, right = int(act.min()), int(act.max())
+        if i <= 3:
+            left = 0
+        elif i >= len(steps) - 4:
+            right = int(vlen)
+        right_excl = min(right + 1, K)
+        if right_excl <= left:
+            continue
+        if max_sentences is not None and right_excl - left > max_sentences:
+            raise ValueError(f"{vid}: the window at {int(s0)} s holds {right_excl - left} sentences, the joint stack takes at most "
+                             f"{max_sentences} beside {seq_len} frames")
+        out.append((int(s0), int(min(vlen, s0 + seq_len)), left, right_excl))
+    return out
+
+
 @torch.no_grad()
 def test_alignment_htm(get_text_visual_sim, videos, device="cuda", seq_len=64, use_alignability_head=True,
                        method="overlap-seq", return_per_video=False, batched_sim=None):
@@ -99,29 +135,15 @@ def test_alignment_htm(get_text_visual_sim, videos, device="cuda", seq_len=64, u
         K, vlen = len(text), video.shape[1]
         abs_pos = torch.stack((torch.as_tensor(item["start"]), torch.as_tensor(item["end"])), -1).div(vlen).to(device)
         if method == "overlap-seq":
-            steps = np.arange(0, vlen - seq_len // 2, seq_len // 4)
-            mid = (start + end) / 2
             acc_j = torch.zeros(K, vlen, device=device)
             acc_d = torch.zeros(K, vlen, device=device)
             cnt = torch.zeros(K, vlen, device=device)
             a_d, a_j, tcnt = (torch.zeros(K, device=device) for _ in range(3))
-            na_idx, na_mid = np.arange(K)[~aligned], mid[~aligned]
             windows = []
-            for i, s0 in enumerate(steps):
-                inside = (s0 - seq_len <= na_mid) & (na_mid <= s0 + 2 * seq_len)
-                act = na_idx[inside]
-                if len(act) == 0:
-                    continue
-                left, right = act.min(), act.max()
-                if i <= 3:
-                    left = 0
-                elif i >= len(steps) - 4:
-                    right = vlen
+            for s0, e0, left, right in plan_windows(start, end, vlen, seq_len, candidates=~aligned):
                 m = np.zeros(K, bool)
-                m[left:right + 1] = True
-                if not m.any():
-                    continue
-                windows.append((int(s0), int(min(vlen, s0 + seq_len)), m))
+                m[left:right] = True
+                windows.append((s0, e0, m))
             if batched_sim is not None:
                 results = batched_sim(video, text, windows, seq_len)
             else:

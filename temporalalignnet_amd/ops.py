@@ -237,3 +237,42 @@ def attn_bwd(qkv, keypad_u8, o, lse, d_o, dqkv, B, L, H, g_b_qkv=None):
     _lib.check(_lib.lib().tan_attn_bwd(_ptr(qkv), _ptr(keypad_u8), _ptr(o), _f32(lse), _ptr(d_o), _ptr(dqkv), C.c_int(B),
                                         C.c_int(L), C.c_int(H), _dt(qkv), _stream()), "tan_attn_bwd")
     return dqkv
+
+
+def _elem_bytes(t):
+    if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"unsupported dtype {t.dtype}")
+    return t.element_size()
+
+
+def window_pack(video, text, table, T, Kp, out_video, vmask, out_text, tmask):
+    """One pass's `eval_windows` input from the chunk's packed features (tan_window_pack): video [sum vlen, Dv], text [sum K, Dt]
+    (f32 / f16 / bf16), table [W, 8] int32 -> out_video [W, T, Dv], vmask [W, T] bool, out_text [W, Kp, Dt], tmask [W, Kp] bool."""
+    W = table.shape[0]
+    assert table.dtype == torch.int32 and table.is_contiguous() and video.is_contiguous() and text.is_contiguous()
+    assert out_video.dtype == video.dtype and out_text.dtype == text.dtype and vmask.dtype == tmask.dtype == torch.bool
+    assert out_video.shape == (W, T, video.shape[-1]) and out_text.shape == (W, Kp, text.shape[-1])
+    assert vmask.shape == (W, T) and tmask.shape == (W, Kp)
+    _lib.check(_lib.lib().tan_window_pack(_ptr(video), _elem_bytes(video), video.shape[-1], _ptr(text), _elem_bytes(text),
+                                          text.shape[-1], _ptr(table), W, T, Kp, _ptr(out_video), _ptr(vmask), _ptr(out_text),
+                                          _ptr(tmask), _stream()), "tan_window_pack")
+
+
+def window_stitch_acc(sim_j, sim_d, a_joint, table, acc_j, acc_d, cnt, tcnt, a_sum):
+    """acc_j / acc_d / cnt [sum K*vlen], tcnt / a_sum [sum K] += one pass (tan_window_stitch_acc); sim_j / sim_d [W, T, Kp] f32 (one
+    stage of eval_windows' output, read in place), a_joint [W, Kp] f32 or None (no alignability head: a_sum is None too)."""
+    W, T, Kp = sim_j.shape
+    assert sim_j.is_contiguous() and sim_d.is_contiguous() and sim_d.shape == sim_j.shape and table.shape == (W, 8)
+    assert a_joint is None or (a_joint.is_contiguous() and a_joint.shape == (W, Kp))
+    _lib.check(_lib.lib().tan_window_stitch_acc(_f32(sim_j), _f32(sim_d), _f32(a_joint), _ptr(table), W, T, Kp, _f32(acc_j),
+                                                _f32(acc_d), _f32(cnt), acc_j.numel(), _f32(tcnt), _f32(a_sum), tcnt.numel(),
+                                                _stream()), "tan_window_stitch_acc")
+
+
+def window_stitch_final(acc_j, acc_d, cnt, tcnt, a_sum, rows, res):
+    """acc_j <- the stitched rows in place; res [4, sum K] f32 <- arg-max, softmax max, score, covered (tan_window_stitch_final).
+    rows [sum K, 2] int32: each sentence's accumulator offset and vlen."""
+    n = tcnt.numel()
+    assert rows.dtype == torch.int32 and rows.shape == (n, 2) and res.shape == (4, n)
+    _lib.check(_lib.lib().tan_window_stitch_final(_f32(acc_j), _f32(acc_d), _f32(cnt), _f32(tcnt), _f32(a_sum), _ptr(rows), n,
+                                                  acc_j.numel(), _f32(res), _stream()), "tan_window_stitch_final")

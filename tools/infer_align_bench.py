@@ -1,0 +1,90 @@
+"""Corpus auto-alignment throughput: `infer_align.align_corpus` against the per-video evaluation path (`test_alignment_htm` +
+`make_batched_sim_fn`, every sentence a candidate), same model, same synthetic corpus, one process, ABBA order, device-synchronised
+wall clocks.  Prints one JSON line.
+
+    python tools/infer_align_bench.py [--videos 256] [--reps 2] [--only corpus]
+
+Corpus: seeded, vlen uniform in [120, 900] s, one sentence per ~8 s, [vlen, 1024] f16 features, random [K, 512] sentence embeddings
+(looked up, so neither path pays for a language model).  Model: E6D6, bf16, alignability head, random weights.
+`--only corpus` runs align_corpus alone (for a `rocprofv3 --kernel-trace --stats` run of its own).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from temporalalignnet_amd.eval_align import make_batched_sim_fn, plan_windows, test_alignment_htm  # noqa: E402
+from temporalalignnet_amd.infer_align import align_corpus  # noqa: E402
+from temporalalignnet_amd.train import build_model, default_args  # noqa: E402
+
+
+def corpus(n, seed=0):
+    rng = np.random.default_rng(seed)
+    vids = []
+    for i in range(n):
+        vlen = int(rng.integers(120, 901))
+        K = max(1, int(round(vlen / 8)))
+        mid = np.sort(rng.uniform(0, vlen, K))
+        dur = rng.uniform(1, 8, K)
+        vids.append({"vid": f"v{i:04d}", "video": (np.abs(rng.standard_normal((vlen, 1024))) * 0.3).astype(np.float16),
+                     "start": np.clip(mid - dur / 2, 0, None), "end": np.minimum(mid + dur / 2, vlen),
+                     "aligned": np.zeros(K, np.int64), "str": [f"v{i}s{k}" for k in range(K)]})
+    return vids
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--videos", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=2, help="ABBA blocks")
+    ap.add_argument("--windows-per-pass", type=int, default=256)
+    ap.add_argument("--only", choices=("corpus",), default=None)
+    a = ap.parse_args()
+    torch.manual_seed(0)
+    model = build_model(default_args(model="init", num_encoder_layers=6, num_decoder_layers=6, use_alignability_head=1),
+                        compute_dtype="bf16", random_pos_start=0).cuda().eval()
+    vids = corpus(a.videos)
+    names = {s: j for j, s in enumerate(s for v in vids for s in v["str"])}
+    table = torch.randn(len(names), 512, device="cuda")
+    embed = lambda strs: table[torch.tensor([names[s] for s in strs], device="cuda")]      # noqa: E731
+    n_win = sum(len(plan_windows(v["start"], v["end"], len(v["video"]))) for v in vids)
+
+    def run_corpus():
+        for _ in align_corpus(model, vids, embed, windows_per_pass=a.windows_per_pass):
+            pass
+
+    def run_per_video():
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            test_alignment_htm(None, vids, return_per_video=True, batched_sim=make_batched_sim_fn(model, embed))
+
+    paths = {"corpus": run_corpus} if a.only else {"corpus": run_corpus, "per_video": run_per_video}
+    for f in paths.values():                   # warm-up: code objects, workspaces of every pass shape
+        f()
+    times = {k: [] for k in paths}
+    order = ["corpus"] if a.only else ["corpus", "per_video", "per_video", "corpus"]
+    for _ in range(a.reps):
+        for k in order:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            paths[k]()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    out = {"videos": len(vids), "windows": n_win, "sentences": len(names), "windows_per_pass": a.windows_per_pass,
+           "model": "E6D6 bf16 head", "gpu": torch.cuda.get_device_name(0)}
+    for k, ts in times.items():
+        best, med = min(ts), float(np.median(ts))
+        out[k] = {"s": [round(t, 4) for t in ts], "videos_per_s": round(len(vids) / med, 2), "windows_per_s": round(n_win / med, 1)}
+    if "per_video" in out:
+        out["speedup_median"] = round(float(np.median(times["per_video"]) / np.median(times["corpus"])), 2)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

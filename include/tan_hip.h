@@ -172,7 +172,9 @@ int tan_attn_bwd_bias(const void* qkv, const unsigned char* key_padding_mask, co
  * tan_nce_fwd: symmetric multi-positive NCE terms of loss.py:240-253 (and 262-274):
  *   v_terms[s,r] = LSE_cols(all) - LSE_cols(pos), t_terms[s,c] = LSE_rows(all) - LSE_rows(pos); the row/column sums of
  *   exp(l/0.07 - 1/0.07) are saved (rowsum [S,R], colsum [S,Mp], possum_v [S,R], possum_t [S,Mp]) for tan_nce_bwd, which
- *   turns upstream g_v [S,R], g_t [S,Mp] into dlogits [S,R,Mp] (out_dtype).  ws: tan_nce_ws_floats() f32 scratch.   */
+ *   turns upstream g_v [S,R], g_t [S,Mp] into dlogits [S,R,Mp] (out_dtype).  ws: tan_nce_ws_floats() f32 scratch.
+ *   A row with an empty positive set takes the reference's fill -6e4 + log(#real text columns): n_valid_cols when > 0, else
+ *   counted from col_invalid on the device (the fused sweeps always count their col_invalid that way).                */
 long tan_nce_ws_floats(int S, int B, int T, int N);
 int tan_nce_fwd(const float* logits, const float* tgt, const unsigned char* col_invalid, const unsigned char* row_leak,
                 float* rowsum, float* colsum, float* possum_v, float* possum_t, float* v_terms, float* t_terms, float* ws,

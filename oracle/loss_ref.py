@@ -62,8 +62,8 @@ def window_bank(durations, T):
     """Normalised sliding windows, loss.py:112-131.  durations [B,N] (float, 0 for padded texts).
     bank[b,n,i,:] averages over [i, i+d) when that fits in [0,T); frames 0 and T-1 are then
     removed from every window ("never choose temp-index 0 / -1") and the rest renormalised."""
-    i = torch.arange(T)[:, None]
-    j = torch.arange(T)[None, :]
+    i = torch.arange(T, device=durations.device)[:, None]
+    j = torch.arange(T, device=durations.device)[None, :]
     d = durations[:, :, None, None]
     member = (j >= i) & (j < i + d) & (i + d <= T)            # [B,N,T,T]
     member = member & (j != 0) & (j != T - 1)
@@ -91,8 +91,57 @@ def self_label(diag_logits, video_pad, text_pad, bank):
 
 def _block_diag(x_btn, B):
     """[B,T,N] -> [B,T,B,N] with x on the same-video blocks, zero elsewhere."""
-    eye = torch.eye(B, dtype=x_btn.dtype)
+    eye = torch.eye(B, dtype=x_btn.dtype, device=x_btn.device)
     return x_btn[:, :, None, :] * eye[:, None, :, None]
+
+
+def agreement(jt, dt, tgt_raw, conf_d, conf_j, kind):
+    """Agreement of the two self-labelled windows and the exclusion principle, loss.py:181-226.
+    jt, dt, tgt_raw [B,N,T] bool; conf_d / conf_j [B,N] bool (max logit >= its 0.3-quantile).
+    Returns (dedup [B,N,T] float target, iou [B,N], conf [B,N] bool)."""
+    inter = (jt & dt).sum(-1).float()
+    union = (jt | dt).sum(-1).float()
+    iou = inter / union.clamp(min=1e-5)                                           # [B,N]
+    conf_iou = iou >= 0.5
+    conf = conf_d & conf_j & conf_iou
+    if kind == "i":
+        agree = (jt & dt) & conf[:, :, None]
+    elif kind == "u":
+        agree = (jt | dt) & conf[:, :, None]
+    elif kind == "keep":
+        agree = torch.where(conf_iou[:, :, None], jt | dt, tgt_raw)
+    elif kind == "keep-joint":
+        agree = torch.where(conf_iou[:, :, None], jt, tgt_raw)
+    else:
+        raise ValueError(kind)
+    agree = agree.float()                                                         # [B,N,T]
+    # exclusion (loss.py:216-226): per (video, t) keep only the first text; text 0 keeps its own
+    # row; texts left with no positive at all get the YouTube target back.
+    first = agree.argmax(1)                                                       # [B,T], 0 if none
+    dedup = torch.zeros_like(agree)
+    dedup.scatter_(1, first[:, None, :], 1.0)
+    dedup[:, 0, :] = agree[:, 0, :]
+    lost = dedup.sum(-1) == 0                                                     # [B,N]
+    dedup[lost] = tgt_raw.float()[lost]
+    return dedup, iou, conf
+
+
+def threshold_metric(md, mj):
+    """-(z-score of md + z-score of mj) over the real sentences' per-text maxima, loss.py:284-285."""
+    zd = (md - md.mean()) / md.std()
+    zj = (mj - mj.mean()) / mj.std()
+    return -(zd + zj)
+
+
+def alignability_labels(md, mj, med_d, med_j, centre=None):
+    """1 where both maxima are above their medians, 0 where both are below or the sentence's centre lies
+    outside [0.2, 0.8], 2 (ignore) elsewhere, loss.py:309-328."""
+    lab = torch.full_like(md, 2.0)
+    lab = lab.masked_fill((md > med_d) & (mj > med_j), 1.0)
+    lab = lab.masked_fill((md < med_d) & (mj < med_j), 0.0)
+    if centre is not None:
+        lab = lab.masked_fill((centre < 0.2) | (centre > 0.8), 0.0)
+    return lab
 
 
 def nce(scaled_logits, tgt_cols, keep_cols):
@@ -146,33 +195,9 @@ def get_loss(input_data, video_seq, text_embed, video_padding_mask, text_padding
             J = self_label(_diag_blocks(src_j), vpad, tpad, bank)
             D = self_label(_diag_blocks(src_d), vpad, tpad, bank)
             jt, dt = J["tgt"], D["tgt"]                                               # [B,N,T] bool
-            inter = (jt & dt).sum(-1).float()
-            union = (jt | dt).sum(-1).float()
-            iou = inter / union.clamp(min=1e-5)                                       # [B,N]
             conf_d = D["max_logit"] >= torch.quantile(D["max_logit"][keep].float(), 0.3)
             conf_j = J["max_logit"] >= torch.quantile(J["max_logit"][keep].float(), 0.3)
-            conf_iou = iou >= 0.5
-            conf = conf_d & conf_j & conf_iou
-            kind = args.temporal_agreement_type
-            if kind == "i":
-                agree = (jt & dt) & conf[:, :, None]
-            elif kind == "u":
-                agree = (jt | dt) & conf[:, :, None]
-            elif kind == "keep":
-                agree = torch.where(conf_iou[:, :, None], jt | dt, tgt_raw)
-            elif kind == "keep-joint":
-                agree = torch.where(conf_iou[:, :, None], jt, tgt_raw)
-            else:
-                raise ValueError(kind)
-            agree = agree.float()                                                     # [B,N,T]
-            # exclusion (loss.py:216-226): per (video, t) keep only the first text; text 0 keeps its own
-            # row; texts left with no positive at all get the YouTube target back.
-            first = agree.argmax(1)                                                   # [B,T], 0 if none
-            dedup = torch.zeros_like(agree)
-            dedup.scatter_(1, first[:, None, :], 1.0)
-            dedup[:, 0, :] = agree[:, 0, :]
-            lost = dedup.sum(-1) == 0                                                 # [B,N]
-            dedup[lost] = tgt_raw.float()[lost]
+            dedup, iou, conf = agreement(jt, dt, tgt_raw, conf_d, conf_j, args.temporal_agreement_type)
             tgt_full = _block_diag(dedup.permute(0, 2, 1), B)                         # [B,T,B,N]
             out["confidence-ratio"] = conf[keep].float().mean()
             out["iou-threshold"] = torch.tensor(0.5)
@@ -207,9 +232,7 @@ def get_loss(input_data, video_seq, text_embed, video_padding_mask, text_padding
             # per-text max over time of the last-stage same-video logits (online model), loss.py:280-283
             md = _diag_blocks(ld)[:, -1].permute(1, 0, 2)[:, keep].max(0).values        # [M]
             mj = _diag_blocks(lj)[:, -1].permute(1, 0, 2)[:, keep].max(0).values
-            zd = (md - md.mean()) / md.std()
-            zj = (mj - mj.mean()) / mj.std()
-            metric = -(zd + zj)
+            metric = threshold_metric(md, mj)
             th_mask = metric <= torch.quantile(metric.float(), args.loss_threshold, -1, keepdim=True)
             if "th_mask" in fixed:
                 th_mask = fixed["th_mask"].bool()
@@ -230,14 +253,10 @@ def get_loss(input_data, video_seq, text_embed, video_padding_mask, text_padding
             out["loss-joint"] = loss_joint_th.detach()
         if args.use_alignability_head:
             with torch.no_grad():
-                lab = torch.full_like(metric, 2.0)                                      # 2 = ignore
                 med_d = torch.quantile(md.float(), 0.5, keepdim=True)
                 med_j = torch.quantile(mj.float(), 0.5, keepdim=True)
-                lab = lab.masked_fill((md > med_d) & (mj > med_j), 1.0)
-                lab = lab.masked_fill((md < med_d) & (mj < med_j), 0.0)
-                if abs_text_pos is not None:
-                    centre = abs_text_pos[keep, :].mean(-1)
-                    lab = lab.masked_fill((centre < 0.2) | (centre > 0.8), 0.0)
+                centre = abs_text_pos[keep, :].mean(-1) if abs_text_pos is not None else None
+                lab = alignability_labels(md, mj, med_d, med_j, centre)                 # 2 = ignore
                 if "lab" in fixed:
                     lab = fixed["lab"].float()
                 aux["t_align_th_mask"] = lab

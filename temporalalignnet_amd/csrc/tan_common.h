@@ -76,6 +76,21 @@ __device__ __forceinline__ float wave_sum(float v) {
     auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false);
     return __int_as_float(r32[0]) + __int_as_float(r32[1]);
 }
+// log(number of zero bytes in flags[0, n)), by the whole block: every thread calls it, every thread gets the result.  The fill of
+// an NCE term whose positive set is empty is -6e4 + log(count) with the count of the REAL text columns: the reference drops padded
+// sentences before its log-sum-exps (loss.py:64-70), so padded and filler columns must not be counted.
+__device__ __forceinline__ float block_log_count_zero(const unsigned char* __restrict__ flags, int n) {
+    __shared__ float cnt_part[16];
+    float c = 0.f;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) c += flags[i] ? 0.f : 1.f;
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0) cnt_part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    float tot = 0.f;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += cnt_part[w];
+    __syncthreads();
+    return logf(tot);
+}
 // Sums of 16 per-lane values over the 32 lanes that share lane >> 5, 38 instructions instead of 16 x 6: every level adds the
 // partner lane's value for two values at once and keeps one of them per lane (v_permlane16_swap does both in one go for the
 // lanes 16 apart; then row_ror:8, row_half_mirror, quad_perm [1,0,3,2], and a last quad_perm [2,3,0,1] add).  Lane l ends up

@@ -84,9 +84,11 @@ __global__ __launch_bounds__(256) void nce_pos_kernel(const float* __restrict__ 
 }
 
 // v_terms[s,r] = LSE_all - LSE_pos (loss.py:246-248), t_terms[s,c] likewise (loss.py:250-253).  LSE over an empty positive
-// set reproduces the reference's -6e4 fill: log(sum_valid exp(-6e4)) = -6e4 + log(#cols).
+// set reproduces the reference's -6e4 fill: log(sum exp(-6e4)) = -6e4 + log(count) over the reference's rows (R) or real text
+// columns; with `count_invalid` the count is that of the zero flags among its n_count entries (the real columns), else log_count.
 __global__ void nce_terms_kernel(const float* __restrict__ allsum, const float* __restrict__ possum, float* __restrict__ terms,
-                                 long n, float log_count) {
+                                 long n, float log_count, const unsigned char* __restrict__ count_invalid, int n_count) {
+    if (count_invalid) log_count = block_log_count_zero(count_invalid, n_count);
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float shift = 1.0f / TAU;
@@ -447,10 +449,11 @@ extern "C" int tan_nce_fwd(const float* logits, const float* tgt, const unsigned
     TAN_LAUNCH_CHECK();
     hipLaunchKernelGGL(nce_pos_kernel, dim3(B, S), dim3(256), 0, st, logits, tgt, col_invalid, row_leak, possum_v, possum_t, B, T, N);
     TAN_LAUNCH_CHECK();
+    // (n_valid_cols <= 0: the real columns are counted from col_invalid on the device -- no host sync for the caller)
     hipLaunchKernelGGL(nce_terms_kernel, dim3(cdiv((long)S * R, 256)), dim3(256), 0, st, rowsum, possum_v, v_terms, (long)S * R,
-                       logf((float)n_valid_cols));
+                       logf((float)max(n_valid_cols, 1)), n_valid_cols > 0 ? nullptr : col_invalid, Mp);
     hipLaunchKernelGGL(nce_terms_kernel, dim3(cdiv((long)S * Mp, 256)), dim3(256), 0, st, colsum, possum_t, t_terms,
-                       (long)S * Mp, logf((float)R));
+                       (long)S * Mp, logf((float)R), (const unsigned char*)nullptr, 0);
     TAN_LAUNCH_CHECK();
     return 0;
 }

@@ -1083,8 +1083,10 @@ __global__ void simnce_terms(const float* __restrict__ allsum, const float* __re
 
 // v_terms and t_terms in one launch (they were two launches on the loss's serial chain)
 __global__ void simnce_terms2(const float* __restrict__ rowsum, const float* __restrict__ possum_v, float* __restrict__ v_terms, long SR,
-                              float log_cols, const float* __restrict__ colsum, const float* __restrict__ possum_t,
-                              float* __restrict__ t_terms, long SM, float log_rows) {
+                              const unsigned char* __restrict__ col_invalid, int ncols, const float* __restrict__ colsum,
+                              const float* __restrict__ possum_t, float* __restrict__ t_terms, long SM, float log_rows) {
+    // the row terms' empty-positive fill counts the sweep's real columns (block_log_count_zero); blocks of column terms skip it
+    const float log_cols = (long)blockIdx.x * blockDim.x < SR ? block_log_count_zero(col_invalid, ncols) : 0.f;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= SR + SM) return;
     const bool rows = i < SR;
@@ -1263,7 +1265,7 @@ static int simnce_fwd_impl(const void* vn, const void* tn, long t_stage_stride, 
                            possum_v, possum_t, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, B, T, N, colmap, a.Mp);
     }
     if (phases & TAN_SIM_TERMS) {
-        hipLaunchKernelGGL(simnce_terms2, dim3(cdiv(SR + SM, 256)), dim3(256), 0, st, rowsum, possum_v, v_terms, SR, logf((float)a.Mp), colsum,
+        hipLaunchKernelGGL(simnce_terms2, dim3(cdiv(SR + SM, 256)), dim3(256), 0, st, rowsum, possum_v, v_terms, SR, a.col_invalid, a.Mp, colsum,
                            possum_t, t_terms, SM, logf((float)a.R));
     }
     TAN_LAUNCH_CHECK();
@@ -1494,7 +1496,7 @@ struct FamFin {
     const float *g_v, *g_t; float* corr;                             // optional: the backward's same-video corrections [S, R, N]
     float* zero; long nzero;
     int S, B, T, N, Mc; long R;
-    float log_cols, log_rows;
+    float log_rows;
 };
 
 // Everything between the statistics sweep and the loss terms in ONE launch, one block per (video, stage): the same-video cosine block
@@ -1531,6 +1533,13 @@ __global__ __launch_bounds__(256) void simfam_finish_kernel(FamFin a) {
     int* ccs = reinterpret_cast<int*>(colf + 96);                     // [32] sweep column of sentence k, or -1
     unsigned char* validk = reinterpret_cast<unsigned char*>(ccs + 32);   // [32] column takes part in the row sums
     unsigned char* leakf = validk + 32;                                // [T]
+    {   // the real columns of the sweep, for the rows' empty-positive fill (as block_log_count_zero): per-wave counts in colf[0..3],
+        // published by the barrier behind the cosines and read before the one behind `ev` (colf is written only after that)
+        float c = 0.f;
+        for (int i = tid; i < Mc; i += 256) c += a.col_invalid[i] ? 0.f : 1.f;
+        c = wave_sum(c);
+        if (lane == 0) colf[wave] = c;
+    }
     if (tid < 32) {
         int cc = -1;
         if (tid < N) { cc = a.colmap ? a.colmap[b * N + tid] : b * N + tid; if (cc >= Mc) cc = -1; }
@@ -1564,6 +1573,7 @@ __global__ __launch_bounds__(256) void simfam_finish_kernel(FamFin a) {
         }
     }
     __syncthreads();
+    const float log_cols = logf(colf[0] + colf[1] + colf[2] + colf[3]);
     // ---- column partial sums of this video's sentences (fixed order: deterministic)
     {
         const int k = tid & 31, p0 = tid >> 5;
@@ -1591,7 +1601,7 @@ __global__ __launch_bounds__(256) void simfam_finish_kernel(FamFin a) {
         if (leak) { rs -= sum; a.rowsum[ri] = rs; }
         a.possum_v[ri] = pv;
         accRl[t] = pv;
-        a.v_terms[ri] = (logf(rs) + shift) - (pv > 0.f ? logf(pv) + shift : -6e4f + a.log_cols);
+        a.v_terms[ri] = (logf(rs) + shift) - (pv > 0.f ? logf(pv) + shift : -6e4f + log_cols);
     }
     // ---- columns
     if (tid < N && ccs[tid] >= 0) {
@@ -1766,7 +1776,7 @@ extern "C" int tan_simfam_fwd(tan_simfam_desc* d, void* stream) {
         f.rowsum = d->rowsum; f.colsum = d->colsum; f.possum_v = d->possum_v; f.possum_t = d->possum_t;
         f.v_terms = d->v_terms; f.t_terms = d->t_terms;
         f.S = S; f.B = B; f.T = T; f.N = N; f.Mc = Mc; f.R = R;
-        f.log_cols = logf((float)Mc); f.log_rows = logf((float)R);
+        f.log_rows = logf((float)R);
         if (d->g_v) {
             TAN_REQUIRE(d->d_tn_acc);
             f.g_v = d->g_v; f.g_t = d->g_t; f.corr = w.corr;

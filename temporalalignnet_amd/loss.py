@@ -10,7 +10,10 @@ padded texts are handled by masks/weights instead of compaction, which is the sa
 Known, documented differences from the reference:
   * only sim='cos' (the reference model only produces cosine logits, tan_model.py:116-119);
   * loss.py:296,301 index a [#texts-with-positives] tensor with a [#texts] mask and raise IndexError if some
-    non-padded text has no positive frame; here such a text is simply averaged like the others.
+    non-padded text has no positive frame; here such a text is simply averaged like the others;
+  * global negatives (dist_nce.py): a frame whose positive set is empty gets the v-term fill -6e4 + log(#real sentences of its OWN
+    rank), where the reference counts every rank's sentences.  That fill reaches the loss for padded frames that the self-labelling
+    marked positive (model='init' + learn_agreement leaks -6e4 into them); single-rank runs count exactly like the reference.
 """
 from __future__ import annotations
 
@@ -85,7 +88,7 @@ class _NCEFn(torch.autograd.Function):
         ws = torch.empty(L.tan_nce_ws_floats(C.c_int(S), C.c_int(B), C.c_int(T), C.c_int(N)), device=dev)
         _lib.check(L.tan_nce_fwd(_p(lg), _p(tgt), _p(col_invalid), _p(row_leak), _p(rowsum), _p(colsum), _p(possum_v),
                                  _p(possum_t), _p(v_terms), _p(t_terms), _p(ws), C.c_int(S), C.c_int(B), C.c_int(T), C.c_int(N),
-                                 C.c_int(Mp), ops._stream()), "tan_nce_fwd")
+                                 C.c_int(0), ops._stream()), "tan_nce_fwd")      # 0: the real columns are counted on the device
         ctx.saved = (lg, tgt, col_invalid, row_leak, rowsum, colsum, possum_v, possum_t)
         ctx.dims = (S, B, T, N)
         return v_terms, t_terms

@@ -443,7 +443,9 @@ typedef struct tan_encoder_desc {
     void* const* layer_done;                    /* HOST array [layers] of tan_event handles or NULL: layer_done[i] is recorded on
                                                    the stream once every gradient of layer i's parameters is final (layers finish
                                                    last to first) -- lets a data-parallel caller start reducing a layer's slice of
-                                                   the flat gradient while the earlier layers' backward still runs */
+                                                   the flat gradient while the earlier layers' backward still runs.  Not together
+                                                   with an effective dw_tail > 0 (dw_stream set and not the stack's stream): the tail
+                                                   blocks' weight gradients are not final on the stream, so tan_encoder_bwd returns -1 */
     /* forward only */
     int no_save;                                /* != 0: no backward will follow (torch.no_grad(): the EMA target's forward,
                                                    tan_model.py:348-351, and every evaluation entry point) -- the tensors that exist

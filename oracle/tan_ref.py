@@ -28,10 +28,12 @@ def layer_norm(x, p, name):
     return F.layer_norm(x, (x.shape[-1],), p[f"{name}.weight"], p[f"{name}.bias"], LN_EPS)
 
 
-def mha(xn, key_padding_mask, p, prefix, heads=HEADS):
+def mha(xn, key_padding_mask, p, prefix, heads=HEADS, padded_zero=False):
     """Self-attention as nn.MultiheadAttention computes it (model/tfm_model.py:21,30-32):
     packed in-proj (q,k,v order), q scaled by dh^-0.5, masked keys -> -inf, softmax over keys,
-    out-proj.  No attn mask, dropout 0.  xn: [B,L,C]; key_padding_mask: [B,L] bool (True = ignore)."""
+    out-proj.  No attn mask, dropout 0.  xn: [B,L,C]; key_padding_mask: [B,L] bool (True = ignore).
+    padded_zero: a video whose keys are ALL padded gets attention output 0 and no gradient into q, k, v -- the HIP
+    kernels' definition of that case -- where nn.MultiheadAttention returns NaN."""
     B, L, C = xn.shape
     dh = C // heads
     qkv = xn @ p[f"{prefix}.attn.in_proj_weight"].t() + p[f"{prefix}.attn.in_proj_bias"]
@@ -40,17 +42,24 @@ def mha(xn, key_padding_mask, p, prefix, heads=HEADS):
     k = k.view(B, L, heads, dh).transpose(1, 2)
     v = v.view(B, L, heads, dh).transpose(1, 2)
     s = q @ k.transpose(-1, -2)                                   # [B,H,L,L]
+    empty = None
     if key_padding_mask is not None:
         s = s.masked_fill(key_padding_mask[:, None, None, :], float("-inf"))
-    a = torch.softmax(s, dim=-1) @ v                              # [B,H,L,dh]
+        if padded_zero:
+            empty = key_padding_mask.all(dim=-1)[:, None, None, None]
+            s = s.masked_fill(empty, 0.0)                         # finite scores, so neither direction sees a NaN
+    a = torch.softmax(s, dim=-1)
+    if empty is not None:
+        a = a.masked_fill(empty, 0.0)
+    a = a @ v                                                     # [B,H,L,dh]
     a = a.transpose(1, 2).reshape(B, L, C)
     return a @ p[f"{prefix}.attn.out_proj.weight"].t() + p[f"{prefix}.attn.out_proj.bias"]
 
 
-def block(x, key_padding_mask, p, prefix):
+def block(x, key_padding_mask, p, prefix, padded_zero=False):
     """ResidualAttentionBlock_Step.forward -- model/tfm_model.py:34-38. Returns (x_out, ln_1(x_in))."""
     xn = layer_norm(x, p, f"{prefix}.ln_1")
-    x = x + mha(xn, key_padding_mask, p, prefix)
+    x = x + mha(xn, key_padding_mask, p, prefix, padded_zero=padded_zero)
     h = layer_norm(x, p, f"{prefix}.ln_2")
     h = quick_gelu(h @ p[f"{prefix}.mlp.c_fc.weight"].t() + p[f"{prefix}.mlp.c_fc.bias"])
     x = x + (h @ p[f"{prefix}.mlp.c_proj.weight"].t() + p[f"{prefix}.mlp.c_proj.bias"])
@@ -65,6 +74,22 @@ def encoder(x, key_padding_mask, p, prefix, layers):
         x, xn = block(x, key_padding_mask, p, f"{prefix}.resblocks.{i}")
         feats.append(xn)
     return feats[1:] + [x]
+
+
+def encoder_stack(x, key_padding_mask, p, prefix, layers, post, tap=None):
+    """One stack as tan_encoder_fwd computes it: encoder() with the last stage post-LN'ed by `post` (as visual_feature /
+    joint_feature do) and all-padded videos defined as in mha(padded_zero=True).  Returns (stages, x_outs): the S stages and
+    every block's output.  tap(i, x_out) -> tensor, if given, replaces block i's output (tests hook gradients there)."""
+    stages, outs = [], []
+    for i in range(layers):
+        x, xn = block(x, key_padding_mask, p, f"{prefix}.resblocks.{i}", padded_zero=True)
+        if tap is not None:
+            x = tap(i, x)
+        outs.append(x)
+        if i > 0:
+            stages.append(xn)
+    stages.append(layer_norm(x, p, post))
+    return stages, outs
 
 
 def interp_linear(src, size):

@@ -256,6 +256,8 @@ extern "C" int tan_encoder_bwd(const tan_encoder_desc* e, void* st) {
     // the last `tail` blocks' weight-gradient launches on e->dw_stream (see tan_hip.h); tail > 1: those blocks alternate between two
     // sets of the scratch buffers the launch reads
     int tail = e->dw_stream && e->dw_stream != st ? (e->dw_tail > 0 ? e->dw_tail : 0) : 0;
+    // layer_done[i] is recorded on `st`, which never waits for a tail block's weight gradients on dw_stream: the two do not combine
+    TAN_REQUIRE(!(tail > 0 && e->layer_done));
     if (tail > S) tail = S;
     if (tail > 16) tail = 16;
     const bool two_sets = e->scr2_dx && e->scr2_dx2 && e->scr2_dh && e->scr2_dqkv;

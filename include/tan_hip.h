@@ -603,7 +603,8 @@ typedef struct tan_embed_desc {
 int tan_embed_fwd(const tan_embed_desc* d, int nprob, void* stream);
 
 /* tan_embed_bwd: backward of tan_embed_fwd's LayerNorm + position add for up to two problems in one launch (autograd of
- * model/tan_model.py:155-167, 187-199, 212-234): dy = d_out[0] + d_out[1] (either may be NULL; rows addressed like tan_embed_fwd's out[]),
+ * model/tan_model.py:155-167, 187-199, 212-234): dy = d_out[0] + d_out[1] (either may be NULL; rows addressed like tan_embed_fwd's out[]:
+ *   row v*d_out_grp_rows[d] + d_out_off[d] + t, and a present d_out[d] needs 0 <= d_out_off[d] and T + d_out_off[d] <= d_out_grp_rows[d]),
  *   d_proj [rows, C] bf16 = LayerNorm-backward(dy; proj, mean, rstd, ln_g)   (operand of the pre-projection's weight gradient)
  *   g_ln_g += colsum(dy o xhat), g_ln_b += colsum(dy);  d_pos[d] [ceil(videos / tan_embed_bwd_group())][T, C] f32 = per video GROUP,
  *   the sum over its videos of d_out[d] (plain stores, every plane written in full; NULL = not wanted; tan_pos_ln_bwd adds the planes)

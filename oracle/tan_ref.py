@@ -131,6 +131,15 @@ def textual_feature_with_time(lang_embed, p, pos_start, interpolate_from=None):
     return x + layer_norm(pos, p, "ln_position_init")[None]
 
 
+def front_end(video, lang_embed, p, p_v, p_t, p_j, use_text_pos_enc=False):
+    """The four uses of the input embeddings in one forward (tan_model.py:155-167, 187-199, 212-234), position offsets given:
+    (dual video x0, joint video rows, dual text lang_raw, joint text rows)."""
+    T = video.shape[1]
+    lang_raw = textual_feature(lang_embed, p)
+    lang_t = textual_feature_with_time(lang_embed, p, p_t) if use_text_pos_enc else lang_raw
+    return video_embedding(video, p, T, p_v), video_embedding(video, p, T, p_j), lang_raw, lang_t
+
+
 def visual_feature(video, video_padding_mask, p, E, pos_start=0, interpolate_from=None):
     """get_visual_feature -- tan_model.py:152-179. Returns [B,S,T,C] (last stage post-LN'ed)."""
     B, T, _ = video.shape

@@ -366,6 +366,7 @@ extern "C" int tan_embed_bwd(const tan_embed_bwd_desc* d, int nprob, void* strea
         EmbBwdProb& p = i ? A.p1 : A.p0;
         p.rows = s.rows; p.T = s.T; p.nvid = (int)(s.rows / s.T);
         for (int k = 0; k < 2; ++k) {
+            TAN_REQUIRE(!s.d_out[k] || (s.d_out_off[k] >= 0 && s.d_out_grp_rows[k] >= s.T + s.d_out_off[k]));   // (tan_embed_fwd's out[] rule)
             p.dout[k] = (const bf16_t*)s.d_out[k]; p.grp[k] = s.d_out_grp_rows[k]; p.off[k] = s.d_out_off[k]; p.dpos[k] = s.d_out[k] ? s.d_pos[k] : nullptr;
         }
         p.proj = (const bf16_t*)s.proj; p.mean = s.mean; p.rstd = s.rstd; p.g = s.ln_g;

@@ -113,7 +113,7 @@ def test_embed_fwd_matches_torch(B, T, N, Dv, Dt, a_dtype, pads):
     assert torch.equal(keypad, want_pad)
 
 
-def _step_outputs(fused, seed=3, text_pos=0):
+def _step_outputs(fused, seed=3, text_pos=0, B=6):
     """one bf16 forward + backward of the whole model with the fused front-end on / off: loss inputs and every parameter gradient"""
     os.environ["TAN_EMBED_FUSED"] = "1" if fused else "0"
     try:
@@ -128,7 +128,7 @@ def _step_outputs(fused, seed=3, text_pos=0):
             if k in sd and sd[k].shape == torch.Size(v.shape):
                 sd[k].copy_(torch.from_numpy(v))
         m.invalidate_shadow()
-        b = synth.make_batch(11, B=6, T=32, n_min=3, n_max=9)
+        b = synth.make_batch(11, B=B, T=32, n_min=3, n_max=9)
         video, lang = torch.from_numpy(b["video"]).cuda(), torch.from_numpy(b["text_embed"]).cuda().requires_grad_(True)
         vp = torch.from_numpy(b["padding_mask"]).bool().cuda()
         vp[1, -5:] = True
@@ -145,8 +145,17 @@ def _step_outputs(fused, seed=3, text_pos=0):
 
 @pytest.mark.parametrize("text_pos", [0, 1])
 def test_fused_front_end_matches_the_launches_it_replaces(text_pos):
-    ld1, lj1, gl1, g1 = _step_outputs(True, text_pos=text_pos)
-    ld0, lj0, gl0, g0 = _step_outputs(False, text_pos=text_pos)
+    _check_fused_against_unfused(text_pos, 6)
+
+
+def test_fused_front_end_matches_the_launches_it_replaces_at_17_videos():
+    """three partial planes of video position sums, the last holding one video"""
+    _check_fused_against_unfused(1, 17)
+
+
+def _check_fused_against_unfused(text_pos, B):
+    ld1, lj1, gl1, g1 = _step_outputs(True, text_pos=text_pos, B=B)
+    ld0, lj0, gl0, g0 = _step_outputs(False, text_pos=text_pos, B=B)
     assert (ld1 - ld0).abs().max().item() < 0.02 and (lj1 - lj0).abs().max().item() < 0.02      # cosines, bf16 features
     assert set(g1) == set(g0)
 

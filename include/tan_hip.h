@@ -283,6 +283,13 @@ int tan_simnce_bwd_dl_dvn_kept(const void* e_keep, const void* vn, const void* t
  * v_grp_rows = T; joint stack: T + N); padded sentence m = b*N + k at x_text.p[st] + ((m / N) * t_grp_rows + t_off + m % N) * C;
  * d_video / d_text are addressed the same way.  St = 1: one text embedding for all stages (dual), St = S: per stage (joint).
  * Column compaction as tan_simnce_fwd: idx [Mc] (sweep column -> padded sentence), colmap [B*N] (or both NULL: Mc = B*N, identity).
+ * Sweep column c holds the unit row of padded sentence idx[c], filler columns (flagged in col_invalid) included; their t_terms are
+ * finite and meaningless.  The [T, N] block the finishing launch holds twice in the LDS bounds T: 8*T*N + 5*T + 1584 <= 163840 bytes
+ * (T <= 621 at N = 32), checked with everything else before the first launch of either call.
+ * row_leak: a flagged frame gets its terms by SUBTRACTING its same-video exponentials from the sweep's row and column sums.  That
+ * needs the other videos' part to stay above about 1e-4 of the sum (f32); with B = 1, or when every other video's cosine to the frame
+ * is far below its same-video ones (two or three videos at cosines < -0.4 against 0.9), the terms of flagged frames and of padded
+ * columns are rounding noise or non-finite.  Callers with such batches take tan_nce_fwd on materialised logits.
  * Saved between the two calls (caller-owned): vn [S,R,C], inv_v [S,R], tn [St,Mc,C], inv_t [St,Mc], rowsum / possum_v [S,R],
  * colsum / possum_t [S,Mc], e_keep (tan_simnce_keep_elems), ws (tan_simfam_ws_bytes).                                              */
 #define TAN_SIMFAM_NORM_IN_SWEEP 1   /* flags: the sweep normalises its frame panel itself and writes vn / inv_v (no separate launch) */
@@ -315,7 +322,8 @@ typedef struct tan_simfam_desc {
 } tan_simfam_desc;
 long tan_simfam_ws_bytes(int S, int St, int B, int T, int N, int Mc);
 int tan_simfam_fwd(tan_simfam_desc* d, void* stream);
-/* byte offset inside `ws` of stage s's same-video cosine blocks [B, T, N] f32 written by the finishing launch */
+/* byte offset inside `ws` of stage s's same-video cosine blocks [B, T, N] f32 written by the finishing launch (every stage; entries of
+ * padded sentences are their cosines without compaction and undefined with it: a dropped sentence has no sweep column) */
 long tan_simfam_diag_offset(int S, int St, int B, int T, int N, int Mc, int s);
 int tan_simfam_bwd(tan_simfam_desc* d, void* stream);
 

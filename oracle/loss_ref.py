@@ -155,6 +155,55 @@ def nce(scaled_logits, tgt_cols, keep_cols):
     return v, t
 
 
+def nce_ref(lg, tgt, tpad, row_leak):
+    """fp64 (v_terms [S,R], t_terms [S,M]) of `nce` over the real sentences; lg [S,R,Mp] raw cosines, tgt [B,T,N],
+    tpad [B,N] bool, row_leak [R] or None (the -6e4 fill of get_loss on the same-video blocks of those frames)."""
+    S, R, Mp = lg.shape
+    B, T, N = tgt.shape
+    f64 = torch.float64
+    x = (lg.to(f64) / TEMPERATURE).view(S, B, T, B, N).permute(1, 0, 2, 3, 4)         # [B,S,T,B,N]
+    if row_leak is not None:
+        leak = _block_diag(row_leak.view(B, T, 1).expand(B, T, N).to(f64), B).bool()[:, None]
+        x = torch.where(leak, torch.full((), FILL, dtype=f64, device=x.device), x)
+    keep = ~tpad.bool()
+    tgt_cols = _block_diag(tgt.to(f64), B)[:, :, keep].reshape(B * T, -1)
+    return nce(x, tgt_cols, keep)
+
+
+def family_rows(x, grp, G, B):
+    """Rows of one stage buffer under the family addressing of include/tan_hip.h: item i = b*G + j (frame or padded sentence) lives
+    at row b * grp[0] + grp[1] + j.  -> [B*G, C] (a gather: differentiable towards x)."""
+    j = torch.arange(B * G, device=x.device)
+    return x[(j // G) * grp[0] + grp[1] + j % G]
+
+
+def nce_family_ref(x_video, v_grp, x_text, t_grp, tgt, text_pad, row_leak, B, T, N, unit=None):
+    """One feature family (tan_model.py:116-119 dual, 136-139 joint) with loss.py:240-253, in float64 on the inputs' device.
+    x_video: S stage buffers, x_text: 1 (dual) or S (joint) buffers, addressed as `family_rows`; tgt [B,T,N]; text_pad [B,N] bool;
+    row_leak [B*T] or None.  `unit` = (vn [S,R,C], tn [St,Mp,C]) evaluates the cosines and terms on THOSE unit rows instead (a
+    kernel's own bf16 ones) -- the stage buffers then only give the norms.
+    -> dict: vn [S,R,C], inv_v [S,R], tn [St,Mp,C], inv_t [St,Mp] (all padded sentences), cos [S,R,Mp], v_terms [S,R],
+    t_terms [S,#real sentences].  Stage by stage, so the [R,Mp] logits exist once per stage and not S times per intermediate."""
+    f64 = torch.float64
+    S, St = len(x_video), len(x_text)
+    xv = [family_rows(x.to(f64), v_grp, T, B) for x in x_video]
+    xt = [family_rows(x.to(f64), t_grp, N, B) for x in x_text]
+    inv_v = torch.stack([1.0 / x.norm(dim=-1) for x in xv])
+    inv_t = torch.stack([1.0 / x.norm(dim=-1) for x in xt])
+    vn = torch.stack([x / x.norm(dim=-1, keepdim=True) for x in xv])           # tan_ref._unit: no epsilon
+    tn = torch.stack([x / x.norm(dim=-1, keepdim=True) for x in xt])
+    uv, ut = (vn, tn) if unit is None else (unit[0].to(f64), unit[1].to(f64))
+    cos, v_terms, t_terms = [], [], []
+    for s in range(S):
+        c = torch.einsum("rc,mc->rm", uv[s], ut[s if St > 1 else 0])
+        v, t = nce_ref(c[None], tgt, text_pad, row_leak)
+        cos.append(c)
+        v_terms.append(v[0])
+        t_terms.append(t[0])
+    return {"vn": vn, "inv_v": inv_v, "tn": tn, "inv_t": inv_t, "cos": torch.stack(cos), "v_terms": torch.stack(v_terms),
+            "t_terms": torch.stack(t_terms)}
+
+
 def get_loss(input_data, video_seq, text_embed, video_padding_mask, text_padding_mask, logits, args,
              abs_text_pos=None, decisions=None):
     """get_loss -- loss.py:55-422.  Returns (loss_dict, aux).

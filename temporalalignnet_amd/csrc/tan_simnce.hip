@@ -1696,9 +1696,16 @@ static FamWs simfam_ws(void* ws, int S, int St, int B, int T, int N, int Mc) {
     return w;
 }
 
+// dynamic LDS of simfam_finish_kernel: the [T, N] cosine block twice + its row / column arrays
+static size_t simfam_fin_lds(int T, int N) {
+    return sizeof(float) * (2 * (size_t)T * N + T + 256 + 96) + 4 * 32 + 32 + (size_t)T + 16;
+}
+
 static int simfam_check(const tan_simfam_desc* d) {
     TAN_REQUIRE(d && d->S >= 1 && d->S <= 8 && (d->St == 1 || d->St == d->S) && d->B > 0 && d->T > 0 && d->N > 0 && d->N <= DV_MAX_N);
     TAN_REQUIRE(d->C == 512 && d->Mc > 0 && d->Mc % 8 == 0 && d->Mc <= S_MAXCOLS_RES && d->Mc <= 32767);
+    // (here and not in front of the finishing launch: a block that launch cannot hold must be refused before the sweep has run)
+    TAN_REQUIRE(simfam_fin_lds(d->T, d->N) <= 160 * 1024);
     TAN_REQUIRE((d->idx != nullptr) == (d->colmap != nullptr));
     TAN_REQUIRE(d->idx || d->Mc == d->B * d->N);
     TAN_REQUIRE(d->col_invalid && d->tgt && d->vn && d->inv_v && d->tn && d->inv_t && d->rowsum && d->colsum && d->possum_v && d->possum_t);
@@ -1782,8 +1789,7 @@ extern "C" int tan_simfam_fwd(tan_simfam_desc* d, void* stream) {
             f.g_v = d->g_v; f.g_t = d->g_t; f.corr = w.corr;
             f.zero = d->d_tn_acc; f.nzero = (long)St * Mc * 512;
         }
-        const size_t lds = sizeof(float) * (2 * (size_t)T * N + T + 256 + 96) + 4 * 32 + 32 + (size_t)T + 16;
-        TAN_REQUIRE(lds <= 160 * 1024);
+        const size_t lds = simfam_fin_lds(T, N);
         static std::atomic<unsigned long long> lds_done{0};
         const hipError_t attr = ensure_dyn_lds((const void*)simfam_finish_kernel, 160 * 1024, lds_done);
         if (attr != hipSuccess) return (int)attr;

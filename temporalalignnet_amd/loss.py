@@ -341,11 +341,11 @@ class _ManualCtx:
         pass
 
 
-def nce_family(vn, tn, tgt, col_invalid, B, T, N, nv, g_v, g_t):
+def nce_family(vn, tn, tgt, col_invalid, B, T, N, nv, g_v, g_t, row_leak=None):
     """Similarity + multi-positive NCE of ONE family, forward and backward back to back on the current stream (loss.py:240-253 and its
     autograd): -> (v_terms, t_terms, d_vn, d_tn).  g_v [S, R] / g_t [S, Mc]: d loss / d terms (`nce_term_grads`)."""
     ctx = _ManualCtx()
-    v_terms, t_terms = _FusedNCEFn.forward(ctx, vn, tn, tgt, col_invalid, None, B, T, N, nv)
+    v_terms, t_terms = _FusedNCEFn.forward(ctx, vn, tn, tgt, col_invalid, row_leak, B, T, N, nv)
     d_vn, d_tn = _FusedNCEFn.backward(ctx, g_v, g_t)[:2]
     return v_terms, t_terms, d_vn, d_tn
 
@@ -378,7 +378,7 @@ class SimFam:
     gradients (thresholds over BOTH families' forward results) arrive in between (stage 2, `Trainer._forward_backward_chains2`):
     `tgt`, `g_v`, `g_t` are then buffers that other launches fill before the call that reads them."""
 
-    def __init__(self, x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k=0):
+    def __init__(self, x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k=0, row_leak=None):
         S, St = len(x_video), len(x_text)
         R, Mp = B * T, B * N
         dev, Cw = x_video[0].device, x_video[0].shape[-1]
@@ -394,6 +394,8 @@ class SimFam:
         else:
             d.col_invalid = col_invalid.data_ptr()
         d.tgt = tgt.data_ptr()
+        if row_leak is not None:
+            d.row_leak = row_leak.data_ptr()         # [B*T] bytes: frames whose same-video logits read -6e4 (include/tan_hip.h)
         # one f32 block (saved sums, terms, norms, the text-gradient accumulator; pieces 16-byte aligned) + the bf16 tensors
         sizes = [S * R] * 4 + [S * Mc] * 3 + [St * Mc, St * Mc * Cw]
         offs = [0]
@@ -421,7 +423,7 @@ class SimFam:
         # the last stage's same-video cosines [B, T, N] f32 inside `ws`, written by the finishing launch (train/loss.py:280-283 reads them)
         off = L.tan_simfam_diag_offset(S, St, B, T, N, Mc, S - 1)
         self.diag_last = ws[off:off + 4 * B * T * N].view(torch.float32).view(B, T, N)
-        self._keep = (f32, vn, tn, ekeep, dl, ws, tgt, col_invalid, nv, x_video, x_text, d_video, d_text)
+        self._keep = (f32, vn, tn, ekeep, dl, ws, tgt, col_invalid, nv, x_video, x_text, d_video, d_text, row_leak)
         self.base_flags = d.flags
 
     def _fwd(self, flags, with_g):
@@ -460,7 +462,7 @@ def simfam_stages_ok(x_video, x_text, N, nv, B, T):
     return simfam_ok(S, N, Mc, x_video[0].dtype, T) and x_video[0].shape[-1] == 512 and St in (1, S)
 
 
-def nce_family_stages(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k=0):
+def nce_family_stages(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k=0, row_leak=None):
     """Similarity + multi-positive NCE of ONE family from the stacks' stage OUTPUTS to their stage GRADIENTS, forward and backward
     back to back on the current stream (tan_model.py:116-119 / 136-139, loss.py:240-253 and their autograd) -> (v_terms, t_terms).
       x_video  list of S stage buffers; frame row r = b*T + t at row (r // T) * v_grp[0] + v_grp[1] + r % T
@@ -469,6 +471,7 @@ def nce_family_stages(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_i
       d_video / d_text  where the gradients go, addressed the same way (every row is written: dropped sentences get zeros)
       nv       column compaction (idx, colmap, pad flags of the sweep's columns) or None
       g_v [S, R] / g_t [S, Mc]  d loss / d terms (`nce_term_grads`)
+      row_leak [B*T] bytes or None: frames whose same-video logits read -6e4 (as `_FusedNCEFn`)
     Six to seven launches through `tan_simfam_fwd / tan_simfam_bwd` (18 before); shapes those do not take run the same arithmetic as
     separate launches (`nce_family` between L2-normalisation launches)."""
     S, St = len(x_video), len(x_text)
@@ -480,11 +483,11 @@ def nce_family_stages(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_i
         inv_v, inv_t = torch.empty(S * R, device=dev), torch.empty(St * Mp, device=dev)
         ops.l2norm_fwd_multi(x_video, vn, inv_v, R, Cw, T, v_grp[0], v_grp[1])
         ops.l2norm_fwd_multi(x_text, tn, inv_t, Mp, Cw, N, t_grp[0], t_grp[1])
-        v_terms, t_terms, d_vn, d_tn = nce_family(vn, tn, tgt, col_invalid, B, T, N, nv, g_v, g_t)
+        v_terms, t_terms, d_vn, d_tn = nce_family(vn, tn, tgt, col_invalid, B, T, N, nv, g_v, g_t, row_leak)
         ops.l2norm_bwd_multi(d_vn, vn, inv_v, d_video, R, Cw, T, v_grp[0], v_grp[1])
         ops.l2norm_bwd_multi(d_tn.view(St, Mp, Cw), tn, inv_t, d_text, Mp, Cw, N, t_grp[0], t_grp[1])
         return v_terms, t_terms
-    fam = SimFam(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k)
+    fam = SimFam(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k, row_leak)
     fam.run()
     return fam.v_terms, fam.t_terms
 

@@ -36,18 +36,7 @@ def _u8(x):
 # ------------------------------------------------------------------------------------------------------------------------------
 # 1. materialised NCE: tan_nce_fwd / tan_nce_bwd through _NCEFn
 
-def nce_ref(lg, tgt, tpad, row_leak):
-    """fp64 (v_terms [S,R], t_terms [S,M]) of loss_ref.nce over the real sentences; lg [S,R,Mp] raw cosines, tgt [B,T,N],
-    tpad [B,N] bool, row_leak [R] or None (the -6e4 fill of loss_ref.get_loss on the same-video blocks of those frames)."""
-    S, R, Mp = lg.shape
-    B, T, N = tgt.shape
-    x = (lg.to(F64) / TAU).view(S, B, T, B, N).permute(1, 0, 2, 3, 4)                 # [B,S,T,B,N]
-    if row_leak is not None:
-        leak = loss_ref._block_diag(row_leak.view(B, T, 1).expand(B, T, N).to(F64), B).bool()[:, None]
-        x = torch.where(leak, torch.full((), FILL, dtype=F64, device=x.device), x)
-    keep = ~tpad.bool()
-    tgt_cols = loss_ref._block_diag(tgt.to(F64), B)[:, :, keep].reshape(B * T, -1)
-    return loss_ref.nce(x, tgt_cols, keep)
+nce_ref = loss_ref.nce_ref          # (the fp64 terms of loss_ref.nce over the real sentences, leaked frames filled: stated in the oracle)
 
 
 def _fill_rows(tgt, tpad, row_leak, S):

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 C = 512
 
 
-def _problem(B, T, N_max, S, joint, seed, compaction=True, pad_frames=False):
+def _problem(B, T, N_max, S, joint, seed, compaction=True):
     from temporalalignnet_amd import loss as L
     from temporalalignnet_amd.train import default_args, to_device_batch
     b = to_device_batch(synth.make_batch(seed, B=B, T=T, n_min=max(1, N_max // 4), n_max=N_max))

@@ -380,7 +380,9 @@ int tan_wordpool_bwd(const void* d_pooled, const void* pooled, const int* argmax
 /* ---- fused AdamW (+ EMA twin, + bf16 shadow weights) over one flat f32 parameter buffer ---------------------
  * torch.optim.AdamW single-tensor arithmetic (train/main.py:397, groups of main.py:330-356) followed by
  * TwinTemporalAligner._momentum_update (tan_model.py:339-344).  mode[i]: 0 no decay, 1 decay, 2 parameter never
- * receives a gradient (skipped like a .grad-is-None parameter); NULL = all decay.  step >= 1 is the 1-based count. */
+ * receives a gradient (skipped like a .grad-is-None parameter), 3 frozen for the optimizer, still EMA'd; NULL = all decay.
+ * Modes 2 and 3 leave p, m, v and p_bf16 untouched; the EMA twin (ema, ema_bf16) moves from the unchanged p in every mode.
+ * step >= 1 is the 1-based count. */
 int tan_adamw_step(float* p, const float* g, float* m, float* v, const unsigned char* mode, long n, double lr,
                    double beta1, double beta2, double eps, double weight_decay, int step, float grad_scale, void* p_bf16,
                    float* ema, float ema_m, void* ema_bf16, void* stream);
@@ -389,7 +391,8 @@ int tan_adamw_step(float* p, const float* g, float* m, float* v, const unsigned 
  * tan_pack_weights image of W in tiles [tn_w][tk_w] (p_packed; tn_w = 384 selects "qkv16", 0 = none) and of W^T in tiles [tn_t][tk_t]
  * (p_tpacked), and the EMA twin's packed W (ema_packed); any image pointer may be NULL.  unit_prefix (DEVICE, [n_entries + 1]) =
  * running sum of N/64 * K/64 over the table, n_units its last element; N % 64 == 0, K % 64 == 0.  mode (required) as in
- * tan_adamw_step; rest_idx (DEVICE, int32 [n_rest], ascending) lists every element of the flat buffer OUTSIDE the table's matrices:
+ * tan_adamw_step, but read ONCE per matrix, at mode[off]: a table matrix must carry a uniform mode (a matrix in mode 2 or 3 keeps
+ * p, m, v and still gets every image rewritten from its current values); rest_idx (DEVICE, int32 [n_rest], ascending) lists every element of the flat buffer OUTSIDE the table's matrices:
  * those are updated by the plain kernel in a second launch.  Replaces tan_adamw_step + tan_transpose_batch + 2 x tan_pack_weights of a training step (train/main.py:112-122). */
 typedef struct tan_image_entry { long off; int N, K, tn_w, tk_w, tn_t, tk_t; } tan_image_entry;
 typedef struct tan_adamw_images_desc {

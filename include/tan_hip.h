@@ -693,6 +693,45 @@ int tan_window_stitch_acc(const float* sim_j, const float* sim_d, const float* a
 int tan_window_stitch_final(float* acc_j, const float* acc_d, const float* cnt, const float* tcnt, const float* a_sum,
                             const int* rows, long n_rows, long n_acc, float* res, void* stream);
 
+/* ---- zero-shot retrieval (eval/eval_zeroshot_retrieval.py:13-27,157-256) and corpus search over a per-second index ----
+ * tan_rank_topk: a matrix-free sweep over scores[q, n] = <Tq[q, :], Vn[n, :]>, Tq [Q, C], Vn [N, C], C == 512, both `dtype`
+ * (TAN_BF16: bf16 operands, f32 accumulation; TAN_F32: exact-f32 MFMA), 16-byte aligned, rows prepared by the caller (normalised /
+ * centred / standardised).  Nothing whose size grows with Q * N is stored.
+ *   pair [Q] int32 or NULL: higher[q] / ties[q] (int32 [Q]) <- how many index rows score strictly above / exactly equal to the score
+ *     of row pair[q] -- what compute_metrics (:13-27) reads off a sorted row.  The paired score is produced by the same instruction
+ *     sequence as the sweep's own entry (q, pair[q]): ties[q] >= 1.  pair[q] in [0, N) is the CALLER's contract (the kernel clamps
+ *     the address it reads, nothing more; the Python wrapper checks on request).  pair == NULL: higher / ties are not touched.
+ *   k in [0, 32], k <= N: top_score / top_row [Q, k] <- the k best (score f32, row int32) per query by descending score, equal scores
+ *     by ascending row; k == 0: counts only (then pair must be given; top_* may be NULL).
+ *   splits: how many workgroups share the index per query tile of 128; 0 = chosen from Q and N, at most 256.  Counts, scores, rows
+ *     and order are bit-identical from run to run and for every `splits`: per-split lists are merged by a total order in a second
+ *     small launch, counts with integer atomics, no float atomics.
+ *   ws: tan_rank_topk_ws_bytes(Q, N, k) bytes of scratch, 16-byte aligned (it does not depend on `splits`; -1 for invalid sizes).
+ * Any Q >= 1, 1 <= N < 2^31; tails are masked in the kernel.  Another width, k > 32, k > N, bad sizes: TAN_ERR_BAD_ARG, nothing
+ * launched.                                                                                                                       */
+long tan_rank_topk_ws_bytes(long Q, long N, int k);
+int tan_rank_topk(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* pair, int k, int splits,
+                  int* higher, int* ties, float* top_score, int* top_row, void* ws, void* stream);
+/* Clip pooling of test_retrieval_yc2 (:197-214).  stage: one stage of the video stack's output, window w's frame f at
+ * stage + w * win_stride + f * 512 elements of `dtype` (win_stride >= T * 512, a multiple of 8); table [W, 3] int32 = (clip,
+ * first_frame, n_frames) per window.  normalize != 0: every selected frame is L2-normalised (sim = 'cos').  sum [n_clips, 512] /
+ * cnt [n_clips] f32 += the frames / their number; the windows of a clip may come in several calls.  Within a call the first window
+ * naming a clip adds all of them in window order (no float atomics).  _final: out [n_clips, 512] f32 = sum / cnt -- the
+ * reference's mean over windows of the mean over frames, a clip's windows holding equally many frames -- L2-normalised again when
+ * normalize != 0.                                                                                                                */
+int tan_segment_pool_acc(const void* stage, int dtype, long win_stride, int T, const int* table, int W, int normalize, float* sum,
+                         float* cnt, int n_clips, void* stream);
+int tan_segment_pool_final(const float* sum, const float* cnt, int n_clips, int normalize, float* out, void* stream);
+/* The per-second index: the feature counterpart of tan_window_stitch_acc / _final.  feat: the last video stage of a pass's windows
+ * (addressing as above); table: the pass's TAN_WIN_FIELDS rows, of which vrow (index row of the window's first frame) and t are
+ * read.  acc [n_rows, 512] / cnt [n_rows] f32 += every covering window's L2-normalised frame row / 1, the first covering window of
+ * the pass adding all of them in window order.  _final: out [n_rows, 512] (TAN_BF16 or TAN_F32) = acc / max(cnt, 1).  The text
+ * side of the dual similarity is one unit vector t_hat in every window, so <out[g], t_hat> / 0.07 is the stitched dual similarity
+ * acc_d / cnt of eval_zeroshot_align.py:198,201.                                                                                 */
+int tan_window_feat_acc(const void* feat, int dtype, long win_stride, const int* table, int W, int T, float* acc, float* cnt,
+                        long n_rows, void* stream);
+int tan_window_feat_final(const float* acc, const float* cnt, long n_rows, void* out, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

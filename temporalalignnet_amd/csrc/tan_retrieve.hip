@@ -1,0 +1,497 @@
+// Zero-shot retrieval on the device: a matrix-free rank / top-k sweep, clip pooling, and the per-second corpus index.
+//
+// tan_rank_topk answers, for Q query rows against N index rows of width 512, "how many index rows beat / tie the query's paired row"
+// (what eval_zeroshot_retrieval.py:13-27 gets from sorting the whole text x video matrix) and "which k rows score best", without ever
+// storing a [Q, N] score.  Three launches:
+//   1. pair   : the score of (q, pair[q]) for every query, by the SAME tile routine as the sweep with the paired rows gathered into
+//               the index tile -- one MFMA chain per score, in the same order, so the sweep's own entry (q, pair[q]) has the same bits
+//               (ties >= 1).  Also zeroes higher / ties.
+//   2. sweep  : grid (query tiles of 128, index splits).  A wave keeps the B fragments of its 32 queries in registers for the whole
+//               kernel; 64-row index tiles stream through LDS in K chunks (double buffered, one barrier per chunk) as the A operand of
+//               32x32 MFMAs.  A lane's 16 accumulators all belong to ONE query (column = lane & 31), so the counts are two compares per
+//               score in registers.  Top-k: scores at or above the query's threshold are appended to a 64-slot LDS buffer per query;
+//               when a buffer would overflow, the wave sorts it (64-lane bitonic network, order: score descending, then row ascending)
+//               keeps the k best and raises the threshold to the k-th.  At the end of the split each query's k best go to scratch.
+//   3. merge  : one wave per query folds the splits' lists through the same sorting network.  The order is total (no two entries
+//               share a row), so the result is the top k of all N rows whatever the split count; integer counts are summed with
+//               integer atomics, whose result does not depend on order.  No float atomics anywhere.
+//
+// tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
+// of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
+#include <type_traits>
+
+#include "tan_mma.h"
+
+namespace tal {
+namespace {
+
+constexpr int RC = 512;                     // feature width (the model's)
+constexpr int BQ = 128;                     // queries per block: 4 waves x 32
+constexpr int BN = 64;                      // index rows per tile
+constexpr int CAP = 64;                     // candidate slots per query
+constexpr int KMAX = 32;
+constexpr int MAX_SPLITS = 256;
+constexpr int SENT_ROW = 0x7fffffff;
+
+template <typename T> struct RCfg;
+template <> struct RCfg<bf16_t> { static constexpr int KC = 128, LD = 136; };     // 256 B of a row per chunk; 272-B pitch: b128 reads conflict-free
+template <> struct RCfg<float> { static constexpr int KC = 64, LD = 65; };        // 256 B of a row per chunk; odd pitch: b32 reads conflict-free
+
+template <typename T> constexpr int tile_bytes() { return 2 * BN * RCfg<T>::LD * (int)sizeof(T); }
+constexpr int BUF_BYTES = 4 * 32 * CAP * 8;
+template <typename T> constexpr int sweep_lds() { return (tile_bytes<T>() + 15) / 16 * 16 + BUF_BYTES; }
+
+__device__ __forceinline__ bool better(float s, int n, float os, int on) { return s > os || (s == os && n < on); }
+
+// 64 (score, row) pairs, one per lane -> lane j holds rank j (score descending, equal scores by ascending row)
+__device__ __forceinline__ void sort64(float& s, int& n, int lane) {
+#pragma unroll
+    for (int size = 2; size <= 64; size <<= 1) {
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const float os = __shfl_xor(s, stride, 64);
+            const int on = __shfl_xor(n, stride, 64);
+            const bool lower = (lane & stride) == 0, desc = (lane & size) == 0;
+            const bool mine = better(s, n, os, on);
+            const bool keep = (lower == desc) ? mine : !mine;
+            if (!keep) { s = os; n = on; }
+        }
+    }
+}
+
+template <typename T> struct QFrag;
+template <> struct QFrag<bf16_t> {
+    static __device__ __forceinline__ bf16x8 load(const bf16_t* row, int j, int lane) {
+        return *reinterpret_cast<const bf16x8*>(row + j * 16 + 8 * (lane >> 5));
+    }
+};
+template <> struct QFrag<float> {
+    static __device__ __forceinline__ float load(const float* row, int j, int lane) { return row[j * 2 + (lane >> 5)]; }
+};
+
+template <typename T>
+__device__ __forceinline__ void stage_store(T* tile, int tid, const uint4 (&pre)[4]) {
+    constexpr int LD = RCfg<T>::LD;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
+        if constexpr (sizeof(T) == 2) {
+            *reinterpret_cast<uint4*>(tile + row * LD + c16 * 8) = pre[i];
+        } else {
+            float* d = reinterpret_cast<float*>(tile) + row * LD + c16 * 4;
+            d[0] = __uint_as_float(pre[i].x); d[1] = __uint_as_float(pre[i].y);
+            d[2] = __uint_as_float(pre[i].z); d[3] = __uint_as_float(pre[i].w);
+        }
+    }
+}
+
+// PAIR = true : launch 1 (grid = query tiles); tile t of 2 holds the paired rows of the block's queries 64 t .. 64 t + 63
+// PAIR = false: launch 2 (grid = query tiles x splits)
+template <typename T, bool PAIR>
+__global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Q, long N,
+                                                   const int* __restrict__ pair, int k, long tiles_per_split, long n_tiles,
+                                                   float* __restrict__ dscore, int* __restrict__ higher, int* __restrict__ ties,
+                                                   float* __restrict__ part_s, int* __restrict__ part_n) {
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, KS = M::KS, NCH = RC / KC, SPC = KC / KS, NFR = RC / KS;
+    constexpr int TS = BN * LD;                                    // elements per tile buffer
+    constexpr long ROWB = (long)RC * sizeof(T);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* tile = reinterpret_cast<T*>(smem);
+    float* bs = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16);
+    int* bn = reinterpret_cast<int*>(bs + 4 * 32 * CAP);
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
+    const long qblk = (long)blockIdx.x * BQ;
+    const long qme = qblk + wave * 32 + col;
+    const bool qok = qme < Q;
+
+    frag_t qf[NFR];                                                // the wave's 32 queries, resident
+    {
+        const T* qrow = Tq + (qok ? qme : Q - 1) * RC;
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(qrow, j, lane);
+    }
+
+    long t0, t1;
+    if (PAIR) { t0 = 0; t1 = 2; }
+    else { t0 = (long)blockIdx.y * tiles_per_split; t1 = t0 + tiles_per_split < n_tiles ? t0 + tiles_per_split : n_tiles; }
+
+    const bool counting = !PAIR && pair != nullptr;
+    const float dq = (counting && qok) ? dscore[qme] : 0.0f;
+    int hi = 0, eq = 0, fill = 0;
+    float thr = -INFINITY, dval = 0.0f;
+    const int bbase = (wave * 32 + col) * CAP;
+
+    uint4 pre[4];
+    auto issue = [&](long t, int kc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
+            long n;
+            if (PAIR) {
+                const long q = qblk + t * BN + row;
+                n = q < Q ? (long)pair[q] : 0;
+                n = n < 0 ? 0 : (n >= N ? N - 1 : n);              // memory safety only: a pair outside [0, N) is the caller's error
+            } else {
+                n = t * BN + row;
+            }
+            pre[i] = n < N ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Vn) + n * ROWB + kc * 256 + c16 * 16)
+                           : make_uint4(0, 0, 0, 0);
+        }
+    };
+
+    if (t0 < t1) issue(t0, 0);
+    for (long t = t0; t < t1; ++t) {
+        f32x16 acc[2];
+        acc_zero(acc[0]);
+        acc_zero(acc[1]);
+#pragma unroll
+        for (int kc = 0; kc < NCH; ++kc) {
+            T* cur = tile + (kc & 1) * TS;                         // NCH is even: the buffer alternates across tiles too
+            stage_store<T>(cur, tid, pre);
+            __syncthreads();
+            if (kc + 1 < NCH) issue(t, kc + 1);
+            else if (t + 1 < t1) issue(t + 1, 0);
+#pragma unroll
+            for (int ks = 0; ks < SPC; ++ks) {
+                const frag_t a0 = M::template load<true>(cur, LD, 0, ks * KS, lane);
+                const frag_t a1 = M::template load<true>(cur, LD, 32, ks * KS, lane);
+                M::mma(acc[0], a0, qf[kc * SPC + ks]);
+                M::mma(acc[1], a1, qf[kc * SPC + ks]);
+            }
+        }
+        if (PAIR) {
+            if (t == (wave >> 1)) {
+                const f32x16 a = (wave & 1) ? acc[1] : acc[0];
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (acc_row(r, lane) == col) dval = a[r];
+            }
+            continue;
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            const long nbase = t * BN + rt * 32;
+            unsigned mask = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const bool valid = nbase + acc_row(r, lane) < N;
+                const float v = acc[rt][r];
+                hi += (valid && v > dq) ? 1 : 0;
+                eq += (valid && v == dq) ? 1 : 0;
+                if (valid && v >= thr) mask |= 1u << r;
+            }
+            if (k == 0) continue;
+            const int c_me = __popc(mask), c_pt = __shfl_xor(c_me, 32, 64), need = c_me + c_pt;
+            if (__any(fill + need > CAP)) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                for (int qi = 0; qi < 32; ++qi) {
+                    const int f = __builtin_amdgcn_readlane(fill, qi), nd = __builtin_amdgcn_readlane(need, qi);
+                    if (f + nd <= CAP) continue;
+                    const int b = (wave * 32 + qi) * CAP;
+                    float s = lane < f ? bs[b + lane] : -INFINITY;
+                    int n = lane < f ? bn[b + lane] : SENT_ROW;
+                    sort64(s, n, lane);
+                    const int nf = f < k ? f : k;
+                    if (lane < nf) { bs[b + lane] = s; bn[b + lane] = n; }
+                    const float th = __shfl(s, k - 1, 64);
+                    if (col == qi) { fill = nf; thr = th; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            }
+            int off = bbase + fill + ((lane >> 5) ? c_pt : 0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if ((mask >> r) & 1) {
+                    bs[off] = acc[rt][r];
+                    bn[off] = (int)(nbase + acc_row(r, lane));
+                    ++off;
+                }
+            fill += need;
+        }
+    }
+
+    if (PAIR) {
+        if ((((col >> 2) & 1) == (lane >> 5)) && qok) {            // the lane that holds row == column of its 32x32 tile
+            dscore[qme] = dval;
+            if (higher) { higher[qme] = 0; ties[qme] = 0; }
+        }
+        return;
+    }
+    if (counting) {
+        hi += __shfl_xor(hi, 32, 64);
+        eq += __shfl_xor(eq, 32, 64);
+        if (lane < 32 && qok) {
+            atomicAdd(&higher[qme], hi);
+            atomicAdd(&ties[qme], eq);
+        }
+    }
+    if (k > 0) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int qi = 0; qi < 32; ++qi) {
+            const int f = __builtin_amdgcn_readlane(fill, qi);
+            const int b = (wave * 32 + qi) * CAP;
+            float s = lane < f ? bs[b + lane] : -INFINITY;
+            int n = lane < f ? bn[b + lane] : SENT_ROW;
+            sort64(s, n, lane);
+            const long q = qblk + wave * 32 + qi;
+            if (q < Q && lane < k) {
+                const long o = ((long)blockIdx.y * Q + q) * k + lane;
+                part_s[o] = s;
+                part_n[o] = n;
+            }
+        }
+    }
+}
+
+// launch 3: one wave per query; lanes 0..31 carry the best so far, lanes 32..63 take the next split's list
+__global__ void __launch_bounds__(256) rank_merge_kernel(const float* __restrict__ part_s, const int* __restrict__ part_n, long Q, int k,
+                                                         int splits, float* __restrict__ top_s, int* __restrict__ top_n) {
+    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (q >= Q) return;
+    float s = -INFINITY;
+    int n = SENT_ROW;
+    for (int sp = 0; sp < splits; ++sp) {
+        if (lane >= 32) {
+            const bool real = lane - 32 < k;
+            const long o = ((long)sp * Q + q) * k + (lane - 32);
+            s = real ? part_s[o] : -INFINITY;
+            n = real ? part_n[o] : SENT_ROW;
+        }
+        sort64(s, n, lane);
+    }
+    if (lane < k) { top_s[q * k + lane] = s; top_n[q * k + lane] = n; }
+}
+
+// ---- one wave per frame row: 64 lanes x 8 channels
+template <typename T> __device__ __forceinline__ f8 ld_row8(const T* p) {
+    if constexpr (sizeof(T) == 2) return ld8(p); else return ld8f(p);
+}
+template <typename T> __device__ __forceinline__ f8 unit_row(const T* row, int lane, bool normalize) {
+    f8 x = ld_row8<T>(row + lane * 8);
+    if (normalize) {
+        float ss = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ss += x.v[i] * x.v[i];
+        const float nrm = sqrtf(wave_sum(ss));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x.v[i] = x.v[i] / nrm;
+    }
+    return x;
+}
+
+// one block per window; the first window of the launch that names a clip owns it and adds all of them in window order
+template <typename T>
+__global__ void __launch_bounds__(256) segment_pool_acc_kernel(const T* __restrict__ stage, long win_stride, int T_len,
+                                                               const int* __restrict__ table, int W, int normalize,
+                                                               float* __restrict__ sum, float* __restrict__ cnt, int n_clips) {
+    __shared__ float part[4][RC];
+    const int w = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int clip = table[3 * w];
+    if (clip < 0 || clip >= n_clips) return;
+    for (int w2 = 0; w2 < w; ++w2)
+        if (table[3 * w2] == clip) return;                          // block-uniform
+    float a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int frames = 0, slot = 0;
+    for (int w2 = w; w2 < W; ++w2) {
+        if (table[3 * w2] != clip) continue;
+        int f0 = table[3 * w2 + 1], nf = table[3 * w2 + 2];
+        f0 = f0 < 0 ? 0 : f0;
+        nf = f0 + nf > T_len ? T_len - f0 : nf;
+        for (int f = 0; f < nf; ++f, ++slot) {
+            if ((slot & 3) != wave) continue;
+            const f8 x = unit_row<T>(stage + (long)w2 * win_stride + (long)(f0 + f) * RC, lane, normalize != 0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a[i] += x.v[i];
+        }
+        frames += nf > 0 ? nf : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) part[wave][lane * 8 + i] = a[i];
+    __syncthreads();
+    for (int c = threadIdx.x; c < RC; c += 256)
+        sum[(long)clip * RC + c] += ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+    if (threadIdx.x == 0) cnt[clip] += (float)frames;
+}
+
+__global__ void __launch_bounds__(256) segment_pool_final_kernel(const float* __restrict__ sum, const float* __restrict__ cnt, int n_clips,
+                                                                 int normalize, float* __restrict__ out) {
+    const long c = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (c >= n_clips) return;
+    f8 x = ld8f(sum + c * RC + lane * 8);
+    const float m = cnt[c];
+    float ss = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { x.v[i] = x.v[i] / m; ss += x.v[i] * x.v[i]; }
+    if (normalize) {
+        const float nrm = sqrtf(wave_sum(ss));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x.v[i] = x.v[i] / nrm;
+    }
+    st4(out + c * RC + lane * 8, make_float4(x.v[0], x.v[1], x.v[2], x.v[3]));
+    st4(out + c * RC + lane * 8 + 4, make_float4(x.v[4], x.v[5], x.v[6], x.v[7]));
+}
+
+// one block per window, one wave per frame; index row g = vrow + frame.  Windows are in plan order (packed rows ascending), so the
+// windows that can cover g are the neighbours whose [vrow, vrow + t) holds it.
+template <typename T>
+__global__ void __launch_bounds__(256) window_feat_acc_kernel(const T* __restrict__ feat, long win_stride, const int* __restrict__ table,
+                                                              int W, int T_len, float* __restrict__ acc, float* __restrict__ cnt,
+                                                              long n_rows) {
+    constexpr int NF = TAN_WIN_FIELDS;
+    const int w = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int* e = table + (long)w * NF;
+    const int t_w = min(e[1], T_len);
+    for (int tt = wave; tt < t_w; tt += 4) {
+        const long g = (long)e[0] + tt;
+        if (g < 0 || g >= n_rows) continue;
+        bool owner = true;
+        for (int w2 = w - 1; w2 >= 0; --w2) {
+            const int* e2 = table + (long)w2 * NF;
+            if ((long)e2[0] + min(e2[1], T_len) <= g) break;
+            if (e2[0] <= g) { owner = false; break; }
+        }
+        if (!owner) continue;
+        f8 a = ld8f(acc + g * RC + lane * 8);
+        float c = cnt[g];
+        for (int w2 = w; w2 < W; ++w2) {
+            const int* e2 = table + (long)w2 * NF;
+            if (e2[0] > g) break;
+            if (g >= (long)e2[0] + min(e2[1], T_len)) continue;
+            const f8 x = unit_row<T>(feat + (long)w2 * win_stride + (g - e2[0]) * RC, lane, true);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) a.v[i] += x.v[i];
+            c += 1.0f;
+        }
+        st4(acc + g * RC + lane * 8, make_float4(a.v[0], a.v[1], a.v[2], a.v[3]));
+        st4(acc + g * RC + lane * 8 + 4, make_float4(a.v[4], a.v[5], a.v[6], a.v[7]));
+        if (lane == 0) cnt[g] = c;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) window_feat_final_kernel(const float* __restrict__ acc, const float* __restrict__ cnt, long n_rows,
+                                                                T* __restrict__ out) {
+    const long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= n_rows) return;
+    f8 x = ld8f(acc + g * RC + lane * 8);
+    const float m = fmaxf(cnt[g], 1.0f);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x.v[i] = x.v[i] / m;
+    if constexpr (sizeof(T) == 2) {
+        st8(out + g * RC + lane * 8, x);
+    } else {
+        st4(out + g * RC + lane * 8, make_float4(x.v[0], x.v[1], x.v[2], x.v[3]));
+        st4(out + g * RC + lane * 8 + 4, make_float4(x.v[4], x.v[5], x.v[6], x.v[7]));
+    }
+}
+
+inline long n_index_tiles(long N) { return (N + BN - 1) / BN; }
+
+template <typename T>
+int rank_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair, int k, int splits, int* higher, int* ties,
+                float* top_s, int* top_n, void* ws, hipStream_t st) {
+    const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
+    long want = splits > 0 ? splits : (512 + q_tiles - 1) / q_tiles;
+    want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
+    want = want > n_tiles ? n_tiles : want;
+    const long tps = (n_tiles + want - 1) / want;
+    const int ns = (int)((n_tiles + tps - 1) / tps);
+    float* dscore = (float*)ws;
+    float* part_s = dscore + (Q + 3) / 4 * 4;
+    int* part_n = (int*)(part_s + (long)ns * Q * k);
+    if (pair) {
+        hipLaunchKernelGGL((rank_kernel<T, true>), dim3((unsigned)q_tiles), dim3(256), tile_bytes<T>(), st, (const T*)Tq, (const T*)Vn, Q, N,
+                           pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr);
+        TAN_LAUNCH_CHECK();
+    }
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false>, sweep_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((rank_kernel<T, false>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), sweep_lds<T>(), st, (const T*)Tq,
+                       (const T*)Vn, Q, N, pair, k, tps, n_tiles, dscore, higher, ties, part_s, part_n);
+    TAN_LAUNCH_CHECK();
+    if (k > 0) {
+        hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, Q, k, ns, top_s, top_n);
+        TAN_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+}  // namespace
+}  // namespace tal
+
+using namespace tal;
+
+extern "C" long tan_rank_topk_ws_bytes(long Q, long N, int k) {
+    if (Q < 1 || N < 1 || N >= (1L << 31) || k < 0 || k > KMAX) return TAN_ERR_BAD_ARG;
+    const long ns = n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS;
+    return ((Q + 3) / 4 * 4) * 4 + ns * Q * k * 8;
+}
+
+extern "C" int tan_rank_topk(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* pair, int k, int splits,
+                             int* higher, int* ties, float* top_score, int* top_row, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && Vn && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 0 && k <= KMAX && k <= N);
+    TAN_REQUIRE(splits >= 0 && (pair || k > 0));
+    TAN_REQUIRE(!pair || (higher && ties));
+    TAN_REQUIRE(k == 0 || (top_score && top_row));
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16 ? rank_launch<bf16_t>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, st)
+                             : rank_launch<float>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, st);
+}
+
+extern "C" int tan_segment_pool_acc(const void* stage, int dtype, long win_stride, int T, const int* table, int W, int normalize,
+                                    float* sum, float* cnt, int n_clips, void* stream) {
+    TAN_REQUIRE(stage && table && sum && cnt && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(W > 0 && T > 0 && n_clips > 0 && win_stride >= (long)T * RC && win_stride % 8 == 0 && (uintptr_t)stage % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == TAN_BF16)
+        hipLaunchKernelGGL(segment_pool_acc_kernel<bf16_t>, dim3(W), dim3(256), 0, st, (const bf16_t*)stage, win_stride, T, table, W,
+                           normalize, sum, cnt, n_clips);
+    else
+        hipLaunchKernelGGL(segment_pool_acc_kernel<float>, dim3(W), dim3(256), 0, st, (const float*)stage, win_stride, T, table, W,
+                           normalize, sum, cnt, n_clips);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tan_segment_pool_final(const float* sum, const float* cnt, int n_clips, int normalize, float* out, void* stream) {
+    TAN_REQUIRE(sum && cnt && out && n_clips > 0);
+    hipLaunchKernelGGL(segment_pool_final_kernel, dim3(cdiv(n_clips, 4)), dim3(256), 0, (hipStream_t)stream, sum, cnt, n_clips, normalize,
+                       out);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tan_window_feat_acc(const void* feat, int dtype, long win_stride, const int* table, int W, int T, float* acc, float* cnt,
+                                   long n_rows, void* stream) {
+    TAN_REQUIRE(feat && table && acc && cnt && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(W > 0 && T > 0 && n_rows > 0 && win_stride >= (long)T * RC && win_stride % 8 == 0 && (uintptr_t)feat % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == TAN_BF16)
+        hipLaunchKernelGGL(window_feat_acc_kernel<bf16_t>, dim3(W), dim3(256), 0, st, (const bf16_t*)feat, win_stride, table, W, T, acc, cnt,
+                           n_rows);
+    else
+        hipLaunchKernelGGL(window_feat_acc_kernel<float>, dim3(W), dim3(256), 0, st, (const float*)feat, win_stride, table, W, T, acc, cnt,
+                           n_rows);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tan_window_feat_final(const float* acc, const float* cnt, long n_rows, void* out, int out_dtype, void* stream) {
+    TAN_REQUIRE(acc && cnt && out && n_rows > 0 && (out_dtype == TAN_F32 || out_dtype == TAN_BF16));
+    hipStream_t st = (hipStream_t)stream;
+    if (out_dtype == TAN_BF16)
+        hipLaunchKernelGGL(window_feat_final_kernel<bf16_t>, dim3(cdiv(n_rows, 4)), dim3(256), 0, st, acc, cnt, n_rows, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(window_feat_final_kernel<float>, dim3(cdiv(n_rows, 4)), dim3(256), 0, st, acc, cnt, n_rows, (float*)out);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}

@@ -75,24 +75,30 @@ class _Chunk:
 
     def load(self, device, stream):
         """Feature files -> one pinned [sum vlen, Dv] buffer -> device on `stream` (the prefetch thread)."""
-        feats = []
-        for it in self.items:
-            v = it["video"]() if callable(it["video"]) else it["video"]
-            v = torch.as_tensor(v)
-            if v.dim() != 2 or v.shape[0] != it["vlen"]:
-                raise ValueError(f"{it['vid']}: features {tuple(v.shape)}, expected [{it['vlen']}, Dv]")
-            feats.append(v)
-        dtype = feats[0].dtype
-        for f in feats[1:]:
-            dtype = torch.promote_types(dtype, f.dtype)
-        host = torch.empty((int(self.v_off[-1]), feats[0].shape[1]), dtype=dtype, pin_memory=True)
-        for f, a, b in zip(feats, self.v_off[:-1], self.v_off[1:]):
-            host[a:b].copy_(f)
+        host = load_packed(self.items, self.v_off)
         self.host = (host, self.table.pin_memory(), self.rows.pin_memory())     # alive until the copies have run
         with torch.cuda.stream(stream):
-            self.video, self.table_d, self.rows_d = (t.to(device, non_blocking=True) for t in self.host)
+            self.video, self.table_d, self.rows_d = self.tensors = tuple(t.to(device, non_blocking=True) for t in self.host)
             self.ready = torch.cuda.Event()
             self.ready.record(stream)
+
+
+def load_packed(items, v_off):
+    """The items' feature arrays (or the callables that read them) -> one pinned [sum vlen, Dv] buffer."""
+    feats = []
+    for it in items:
+        v = it["video"]() if callable(it["video"]) else it["video"]
+        v = torch.as_tensor(v)
+        if v.dim() != 2 or v.shape[0] != it["vlen"]:
+            raise ValueError(f"{it['vid']}: features {tuple(v.shape)}, expected [{it['vlen']}, Dv]")
+        feats.append(v)
+    dtype = feats[0].dtype
+    for f in feats[1:]:
+        dtype = torch.promote_types(dtype, f.dtype)
+    host = torch.empty((int(v_off[-1]), feats[0].shape[1]), dtype=dtype, pin_memory=True)
+    for f, a, b in zip(feats, v_off[:-1], v_off[1:]):
+        host[a:b].copy_(f)
+    return host
 
 
 def _chunks(videos, seq_len, windows_per_pass, candidates, max_sentences, on_reject):
@@ -149,7 +155,7 @@ def _prefetch(chunks, device):
                 raise ch
             cur = torch.cuda.current_stream(device)
             cur.wait_event(ch.ready)
-            for t in (ch.video, ch.table_d, ch.rows_d):
+            for t in ch.tensors:                      # whatever the chunk's load() put on the device
                 t.record_stream(cur)
             yield ch
     finally:

@@ -276,3 +276,76 @@ def window_stitch_final(acc_j, acc_d, cnt, tcnt, a_sum, rows, res):
     assert rows.dtype == torch.int32 and rows.shape == (n, 2) and res.shape == (4, n)
     _lib.check(_lib.lib().tan_window_stitch_final(_f32(acc_j), _f32(acc_d), _f32(cnt), _f32(tcnt), _f32(a_sum), _ptr(rows), n,
                                                   acc_j.numel(), _f32(res), _stream()), "tan_window_stitch_final")
+
+
+def rank_topk_ws_bytes(Q, N, k):
+    n = _lib.lib().tan_rank_topk_ws_bytes(Q, N, k)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_rank_topk_ws_bytes({Q}, {N}, {k}): bad argument")
+    return n
+
+
+def rank_topk(tq, vn, pair=None, k=0, *, splits=0, check_pair=False, out=None, ws=None):
+    """Matrix-free rank / top-k of scores = tq @ vn.T (tan_rank_topk): tq [Q, 512], vn [N, 512], both bf16 or both f32, contiguous.
+    pair [Q] int32 (device) or None.  Returns (higher [Q] int32, ties [Q] int32, top_score [Q, k] f32, top_row [Q, k] int32); the
+    pieces that were not asked for (no pair / k == 0) are None.  splits: 0 = automatic; the result does not depend on it.
+    check_pair: verify pair in [0, N) on the host (one synchronisation); otherwise that is the caller's contract.
+    out / ws: caller-owned outputs (the same 4-tuple) and scratch (uint8, >= rank_topk_ws_bytes) instead of fresh ones."""
+    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and _dt(tq) == _dt(vn)
+    Q, N, dev = tq.shape[0], vn.shape[0], tq.device
+    if pair is not None:
+        assert pair.dtype == torch.int32 and pair.shape == (Q,) and pair.is_contiguous()
+        if check_pair and Q and (int(pair.min()) < 0 or int(pair.max()) >= N):
+            raise ValueError("rank_topk: pair outside [0, N)")
+    if out is None:
+        higher = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
+        ties = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
+        top_s = torch.empty(Q, k, dtype=torch.float32, device=dev) if k > 0 else None
+        top_r = torch.empty(Q, k, dtype=torch.int32, device=dev) if k > 0 else None
+    else:
+        higher, ties, top_s, top_r = out
+    L = _lib.lib()
+    need = L.tan_rank_topk_ws_bytes(Q, N, k)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    _lib.check(L.tan_rank_topk(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(pair), k, splits, _ptr(higher), _ptr(ties),
+                               _ptr(top_s), _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk")
+    return higher, ties, top_s, top_r
+
+
+def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
+    """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
+    selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""
+    W, T, Cc = stage.shape
+    assert Cc == 512 and stage.stride(2) == 1 and stage.stride(1) == Cc and table.dtype == torch.int32 and table.shape == (W, 3)
+    assert table.is_contiguous() and sum_.is_contiguous() and sum_.shape[1] == Cc and cnt.shape == (sum_.shape[0],)
+    _lib.check(_lib.lib().tan_segment_pool_acc(_ptr(stage), _dt(stage), stage.stride(0), T, _ptr(table), W, int(normalize), _f32(sum_),
+                                               _f32(cnt), sum_.shape[0], _stream()), "tan_segment_pool_acc")
+
+
+def segment_pool_final(sum_, cnt, out, normalize=True):
+    """out [n_clips, 512] f32 = sum_ / cnt, L2-normalised when `normalize` (tan_segment_pool_final)."""
+    assert out.shape == sum_.shape and out.is_contiguous()
+    _lib.check(_lib.lib().tan_segment_pool_final(_f32(sum_), _f32(cnt), sum_.shape[0], int(normalize), _f32(out), _stream()),
+               "tan_segment_pool_final")
+    return out
+
+
+def window_feat_acc(feat, table, acc, cnt):
+    """acc [n_rows, 512] / cnt [n_rows] f32 += one pass (tan_window_feat_acc); feat [W, T, 512] (f32 / bf16, window stride free):
+    the last video stage of the pass's windows, table [W, 8] int32 its window table."""
+    W, T, Cc = feat.shape
+    assert Cc == 512 and feat.stride(2) == 1 and feat.stride(1) == Cc and table.dtype == torch.int32 and table.shape == (W, 8)
+    assert table.is_contiguous() and acc.is_contiguous() and acc.shape == (cnt.numel(), Cc)
+    _lib.check(_lib.lib().tan_window_feat_acc(_ptr(feat), _dt(feat), feat.stride(0), _ptr(table), W, T, _f32(acc), _f32(cnt),
+                                              cnt.numel(), _stream()), "tan_window_feat_acc")
+
+
+def window_feat_final(acc, cnt, out):
+    """out [n_rows, 512] (bf16 / f32) = acc / max(cnt, 1) (tan_window_feat_final)."""
+    assert out.shape == acc.shape and out.is_contiguous()
+    _lib.check(_lib.lib().tan_window_feat_final(_f32(acc), _f32(cnt), cnt.numel(), _ptr(out), _dt(out), _stream()),
+               "tan_window_feat_final")
+    return out

@@ -1,0 +1,207 @@
+"""Corpus search with the dual encoder: "which seconds of which videos match this sentence".
+
+The reference's `get_visual_feature` "can be used for retrieval setting" (model/tan_model.py:152); `infer_align.align_corpus` asks
+the dual encoder only about a video's own ASR sentences.  Here the video side is computed ONCE into a per-second index and any
+sentence is ranked against all of it:
+
+  * `build_index`: the window stepping of `eval_align.plan_windows` with every second covered (no sentences involved), passes of up
+    to `windows_per_pass` windows cut across video boundaries and packed by `tan_window_pack`, the video stack only, then
+    `tan_window_feat_acc / _final`: index[t] = the mean over the windows covering second t of the L2-normalised last-stage feature.
+    The text side of the dual similarity is the same unit vector t_hat in every window, so <index[t], t_hat> / 0.07 is the stitched
+    dual similarity of eval_zeroshot_align.py:198,201 -- computed without knowing the sentence.
+  * `search`: sentences -> `get_textual_feature`, normalised -> `tan_rank_topk` against the index (no [Q, N] score matrix) -> rows
+    mapped to (vid, second) on the host.
+
+    python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
+    python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+
+import numpy as np
+import torch
+
+from . import ops
+from .infer_align import PASSES_PER_CHUNK, WIN_FIELDS, _aligner, _prefetch, load_packed
+
+TEMPERATURE = 0.07
+
+
+def plan_index_windows(vlen, seq_len=64):
+    """[(s0, e0)]: window starts `arange(0, vlen - seq_len // 2, seq_len // 4)` as eval/eval_zeroshot_align.py:129-133 steps them,
+    e0 = min(vlen, s0 + seq_len); a video of at most seq_len // 2 seconds, which that rule gives no window, gets one."""
+    steps = np.arange(0, max(int(vlen) - seq_len // 2, 1), seq_len // 4)
+    return [(int(s0), int(min(vlen, s0 + seq_len))) for s0 in steps]
+
+
+class _IndexChunk:
+    def __init__(self, items, seq_len, windows_per_pass):
+        self.items = items
+        V = np.array([it["vlen"] for it in items], dtype=np.int64)
+        self.v_off = np.concatenate([[0], np.cumsum(V)])
+        if int(self.v_off[-1]) >= 2 ** 31:
+            raise ValueError("chunk exceeds the int32 window table")
+        tab = [(self.v_off[i] + s0, e0 - s0, 0, 0, s0, V[i], 0, 0) for i, it in enumerate(items)
+               for s0, e0 in plan_index_windows(it["vlen"], seq_len)]
+        self.table = torch.from_numpy(np.asarray(tab, dtype=np.int32).reshape(-1, WIN_FIELDS))
+        self.passes = [(p0, min(p0 + windows_per_pass, len(tab))) for p0 in range(0, len(tab), windows_per_pass)]
+
+    def load(self, device, stream):
+        self.host = (load_packed(self.items, self.v_off), self.table.pin_memory())
+        with torch.cuda.stream(stream):
+            self.video, self.table_d = self.tensors = tuple(t.to(device, non_blocking=True) for t in self.host)
+            self.ready = torch.cuda.Event()
+            self.ready.record(stream)
+
+
+def _index_chunks(videos, seq_len, windows_per_pass):
+    items, n = [], 0
+    for it in videos:
+        it = dict(it)
+        if "vlen" not in it:
+            it["vlen"] = int(len(it["video"]))
+        if it["vlen"] < 1:
+            raise ValueError(f"{it.get('vid')}: empty video")
+        items.append(it)
+        n += len(plan_index_windows(it["vlen"], seq_len))
+        if n >= windows_per_pass * PASSES_PER_CHUNK:
+            yield _IndexChunk(items, seq_len, windows_per_pass)
+            items, n = [], 0
+    if items:
+        yield _IndexChunk(items, seq_len, windows_per_pass)
+
+
+class VideoIndex:
+    """feat [sum vlen, 512] (device, bf16 or f32): one row per second; v_off [n_videos + 1]: each video's first row; vids."""
+
+    def __init__(self, feat, v_off, vids):
+        self.feat, self.v_off, self.vids = feat, np.asarray(v_off, dtype=np.int64), list(vids)
+
+    def __len__(self):
+        return int(self.feat.shape[0])
+
+    def locate(self, rows):
+        """index rows -> (video number, second)"""
+        rows = np.asarray(rows, dtype=np.int64)
+        v = np.searchsorted(self.v_off, rows, side="right") - 1
+        return v, rows - self.v_off[v]
+
+    def save(self, path):
+        """One .npz of plain arrays (bf16 rows as their uint16 bit patterns)."""
+        f = self.feat.cpu()
+        bf16 = f.dtype == torch.bfloat16
+        with open(path, "wb") as fh:
+            np.savez(fh, feat=(f.view(torch.int16).numpy().view(np.uint16) if bf16 else f.numpy()), bf16=np.array(bf16),
+                     v_off=self.v_off, vids=np.array(self.vids, dtype=np.str_))
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        with np.load(path, allow_pickle=False) as z:
+            f = torch.from_numpy(z["feat"].view(np.int16)).view(torch.bfloat16) if bool(z["bf16"]) else torch.from_numpy(z["feat"])
+            return cls(f.to(device).contiguous(), z["v_off"], [str(v) for v in z["vids"]])
+
+
+@torch.no_grad()
+def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfloat16):
+    """`videos`: iterable of {'vid', 'video' [vlen, Dv] (array / tensor) or a callable that reads it (then 'vlen' is required)} --
+    `infer_align.read_corpus` items work as they are.  Every second of every video gets one row (see the module docstring); the rows
+    do not depend on how the windows are cut into passes."""
+    net = _aligner(model)
+    device = torch.device("cuda", torch.cuda.current_device())
+    T = seq_len
+    feats, vlens, vids = [], [], []
+    no_text = torch.zeros(1, 8, device=device)
+    for ch in _prefetch(_index_chunks(videos, seq_len, windows_per_pass), device):
+        n_rows = int(ch.v_off[-1])
+        acc = torch.zeros(n_rows, 512, device=device)
+        cnt = torch.zeros(n_rows, device=device)
+        for p0, p1 in ch.passes:
+            W, tab = p1 - p0, ch.table_d[p0:p1]
+            vid = torch.empty(W, T, ch.video.shape[1], dtype=ch.video.dtype, device=device)
+            vm = torch.empty(W, T, dtype=torch.bool, device=device)
+            txt = torch.empty(W, 1, 8, device=device)
+            tm = torch.empty(W, 1, dtype=torch.bool, device=device)
+            ops.window_pack(ch.video, no_text, tab, T, 1, vid, vm, txt, tm)
+            v = net.get_visual_feature(vid, vm)                                     # [W, S, T, 512]
+            ops.window_feat_acc(v[:, -1], tab, acc, cnt)
+        feats.append(ops.window_feat_final(acc, cnt, torch.empty(n_rows, 512, dtype=dtype, device=device)))
+        vlens += [it["vlen"] for it in ch.items]
+        vids += [it.get("vid") for it in ch.items]
+    if not feats:
+        raise ValueError("build_index: no videos")
+    return VideoIndex(torch.cat(feats, 0), np.concatenate([[0], np.cumsum(vlens)]), vids)
+
+
+@torch.no_grad()
+def query_features(index, model, embed_text, queries, text_batch=1024):
+    """Unit text features [Q, 512] in the index's dtype."""
+    net = _aligner(model)
+    dev = index.feat.device
+    t = torch.cat([net.get_textual_feature(embed_text(list(queries[a:a + text_batch])).to(dev)).float().reshape(-1, 512)
+                   for a in range(0, len(queries), text_batch)], 0).contiguous()
+    t = ops.l2norm_fwd(t, torch.empty_like(t), None, t.shape[0], 512)
+    return t if index.feat.dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.feat.dtype, device=dev))
+
+
+@torch.no_grad()
+def search(index, model, embed_text, queries, k=10, splits=0):
+    """Per query the k best seconds of the corpus: [[(vid, second, score)] * k] * len(queries), by descending score (equal scores
+    by index row).  score = <index row, unit text feature>: the stitched dual cosine; / 0.07 gives the evaluation's logit."""
+    queries = list(queries)
+    if not queries:
+        return []
+    k = min(int(k), len(index))
+    if not 1 <= k <= 32:
+        raise ValueError("search: k must lie in [1, 32]")
+    tq = query_features(index, model, embed_text, queries)
+    _, _, score, row = ops.rank_topk(tq, index.feat, None, k, splits=splits)
+    score, row = score.cpu().numpy(), row.cpu().numpy()
+    v, sec = index.locate(row)
+    return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    for name in ("index", "query"):
+        p = sub.add_parser(name)
+        p.add_argument("--checkpoint", required=True)
+        p.add_argument("--vocab", required=True, help="s3d_dict.npy (the Word2Vec vocabulary)")
+        p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
+        p.add_argument("--model", choices=("init", "cotrain"), default="init")
+    p = sub.choices["index"]
+    p.add_argument("--feature-dir", required=True)
+    p.add_argument("--asr-json", required=True)
+    p.add_argument("--vlen-csv", required=True)
+    p.add_argument("--out", required=True, help="index file (.npz)")
+    p.add_argument("--worker-id", type=int, default=0)
+    p.add_argument("--num-workers", type=int, default=1)
+    p = sub.choices["query"]
+    p.add_argument("--index", required=True)
+    p.add_argument("-k", type=int, default=10)
+    p.add_argument("sentences", nargs="+")
+    a = ap.parse_args(argv)
+    from .infer_align import build_aligner, make_embed_text, read_corpus
+    vocab = np.load(a.vocab)
+    model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
+    if a.cmd == "index":
+        if not 0 <= a.worker_id < a.num_workers:
+            ap.error("--worker-id must lie in [0, --num-workers)")
+        corpus = read_corpus(a.feature_dir, a.asr_json, a.vlen_csv, a.worker_id, a.num_workers)
+        idx = build_index(model, corpus, dtype=torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+        idx.save(a.out)
+        print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos", file=sys.stderr)
+        return 0
+    from .word2vec_model import Word2VecTokenizer
+    embed = make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab))
+    idx = VideoIndex.load(a.index)
+    for sentence, hits in zip(a.sentences, search(idx, model, embed, a.sentences, a.k)):
+        for vid, sec, score in hits:
+            print(f"{sentence}\t{vid}\t{sec}\t{score:.6f}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

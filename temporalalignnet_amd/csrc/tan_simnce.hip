@@ -1697,6 +1697,7 @@ static FamWs simfam_ws(void* ws, int S, int St, int B, int T, int N, int Mc) {
 }
 
 // dynamic LDS of simfam_finish_kernel: the [T, N] cosine block twice + its row / column arrays
+// (restated by `simfam_ok` of temporalalignnet_amd/loss.py, which keeps such shapes away from here: change the two together)
 static size_t simfam_fin_lds(int T, int N) {
     return sizeof(float) * (2 * (size_t)T * N + T + 256 + 96) + 4 * 32 + 32 + (size_t)T + 16;
 }

@@ -5,6 +5,7 @@ straight into the flat gradient buffer.  `_AlignerEngine` is mixed into Temporal
 public surface); nothing here is ATen arithmetic."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -14,6 +15,8 @@ import torch
 from . import _lib, ops
 from .flat_params import _vp
 from .workspace import HEADS, WIDTH, _Blocks, _EncRun, _WorkspaceMixin
+
+ChainsResult = collections.namedtuple("ChainsResult", "v_d t_d v_j t_j d_lang out_ev")
 
 
 class _AlignerFn(torch.autograd.Function):
@@ -644,7 +647,7 @@ class _AlignerEngine(_WorkspaceMixin):
 
     # ------------------------------------------------------------------ forward + backward as two independent chains (no autograd)
     def _chains_ok(self, video, lang, itp=None, allow_head=False):
-        """allow_head: the caller runs the alignability head itself on the joint chain (stage 2: `Trainer._forward_backward_chains2`)"""
+        """allow_head: the caller runs the alignability head itself on the joint chain (stage 2: `chain_step.Stage2Step`)"""
         return (self.compute_dtype == torch.bfloat16 and self._embed_fused_ok(video, lang, itp)
                 and (allow_head or not self.use_alignability_head) and self._side_stream(video.device) is not None)
 
@@ -684,12 +687,14 @@ class _AlignerEngine(_WorkspaceMixin):
         `family(which, x_video, v_grp, x_text, t_grp, d_video, d_text) -> (v_terms, t_terms)` runs a family's L2 normalisation,
         similarity + NCE forward and backward from the stack's stage outputs to its stage gradients on the current stream
         (`loss.nce_family_stages`; the upstream gradients of its terms depend on masks only).  Parameter gradients land in the flat
-        gradient buffer as in `_run_backward`.  Returns (v_d, t_d, v_j, t_j).
+        gradient buffer as in `_run_backward`.  Returns a `ChainsResult` (d_lang: [B, N, Dt] f32 or None).
+        `mid(v_d, t_d, joint_terms, joint_ready)`: main stream, behind the video stack's backward; the list holds the joint family's
+        `(v_j, t_j, event)` once the flag is set.
         `pipe` (a dict, `Trainer.step` with TAN_STEP_PIPELINE): steps are pipelined across their boundary.  In: the events the previous
         step left in `_Flat.pending` -- "dw_v" / "dw_j" (a stack's last weight-gradient launches: they read the activation workspaces this
         step is about to overwrite: the workspaces alternate between two sets instead of waiting), "video" / "joint" (the optimizer launch
         of a stack's matrices behind them: that stack's forward waits for it, and only for it) -- and "zero" (the gradient fill: the first
-        backward kernel of each chain waits for it).  Out: the same events of THIS step, and the main stream is NOT joined with the
+        backward kernel of each chain waits for it).  Out (`ChainsResult.out_ev`): the same events of THIS step, and the main stream is NOT joined with the
         streams that carry them: the embeddings and the video stack of the next step run under the joint stack's last weight gradients
         and optimizer launch.
         `pre` ({"video": fn, "joint": fn}, stage 2): called on each chain's stream / host thread in front of the online stack's forward,
@@ -751,7 +756,6 @@ class _AlignerEngine(_WorkspaceMixin):
 
         import threading
         joint_terms, joint_ready = [], threading.Event()      # the joint family's terms as soon as its launches are enqueued (for `mid`)
-        self._joint_terms = (joint_terms, joint_ready)
 
         def joint_chain():
             try:
@@ -791,7 +795,6 @@ class _AlignerEngine(_WorkspaceMixin):
             if exc is not None and getattr(main_exc, "tan_consequence", False) and not getattr(exc, "tan_consequence", False):
                 raise exc
             raise
-        self._dual_terms = (v_d, t_d)
         self._encoder_bwd(ev, fe["x0"], vmask_u8, "ln_video_post_enc", dv, d_x0, dw_stream=dw_v, dw_tail=tail_v)
         if hook is not None:
             hook("video", self._layer_events(ev.prefix, ev.layers))
@@ -803,7 +806,7 @@ class _AlignerEngine(_WorkspaceMixin):
         out_ev["video"] = aux_v.record_event()
         if mid is not None:                      # (main stream, behind the video stack's backward: e.g. the loss's masked means, which
             try:                                 #  would otherwise sit between the embeddings' backward and the optimizer launch)
-                mid()
+                mid(v_d, t_d, joint_terms, joint_ready)
             except BaseException:
                 if fut.done() and fut.exception() is not None:      # the joint chain failed first: that is the error to report
                     raise fut.exception()
@@ -822,17 +825,15 @@ class _AlignerEngine(_WorkspaceMixin):
             t.record_stream(main)
         run = {"em": em, "B": B, "T": T, "N": N, "sv_video": fe["sv_video"], "sv_video_j": fe["sv_video_j"], "sv_text": fe["sv_text"],
                "sv_text_t": fe["sv_text_t"]}
-        self._chain_d_lang = self._embed_bwd_fused(run, d_x0, d_xj, d_lang_raw, need_d_lang)      # [B, N, Dt] f32 or None
+        d_lang = self._embed_bwd_fused(run, d_x0, d_xj, d_lang_raw, need_d_lang)      # [B, N, Dt] f32 or None
         out_ev["joint"] = aux_j.record_event()
-        if pipe is not None:                       # the next step waits for each of them where it needs it (`_Flat.pending`)
-            pipe["out"] = out_ev
-        else:
+        if pipe is None:                           # (pipelined: the next step waits for each of them where it needs it, `_Flat.pending`)
             main.wait_stream(aux_v)                # the stacks' last weight gradients (and the optimizer launches behind them)
             main.wait_stream(aux_j)
         self._release_ws(ev)
         self._release_ws(ej)
         self._release_ws(em)
-        return v_d, t_d, v_j, t_j
+        return ChainsResult(v_d, t_d, v_j, t_j, d_lang, out_ev if pipe is not None else None)
 
     # ------------------------------------------------------------------ the HIP backward
     def _run_backward(self, run, grads, need_d_lang):

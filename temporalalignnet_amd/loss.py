@@ -301,7 +301,7 @@ class _FusedNCEFn(torch.autograd.Function):
                     _p(row_leak), _p(rowsum), _p(colsum), _p(possum_v), _p(possum_t), _p(g_v),
                     _p(g_t), _p(dl), _p(ws), C.c_int(S), C.c_int(B), C.c_int(T), C.c_int(N),
                     C.c_int(Cw), _p(tn) if compact else None, C.c_long(0 if shared else Mp * Cw),
-                    _p(colmap), C.c_int(Mc), C.c_int(1 | 2 | 16), ops._stream())      # SWEEP | DIAG | DIAG_KEEP: `ws` still holds the forward's same-video blocks
+                    _p(colmap), C.c_int(Mc), C.c_int(TAN_SIM_SWEEP | TAN_SIM_DIAG | TAN_SIM_DIAG_KEEP), ops._stream())      # `ws` still holds the forward's same-video blocks
         d_vn = torch.empty_like(vn)
         if fusable and _FUSED_DVN:
             # d logits and d_vn = dl . tn_run in one pass over the kept exponentials (the tile is the MFMA operand while it is in the LDS)
@@ -350,6 +350,9 @@ def nce_family(vn, tn, tgt, col_invalid, B, T, N, nv, g_v, g_t, row_leak=None):
     return v_terms, t_terms, d_vn, d_tn
 
 
+# flag bits of include/tan_hip.h, under their names there: `flags` of the tan_simnce_* sweeps / of tan_simfam_desc
+TAN_SIM_SWEEP, TAN_SIM_DIAG, TAN_SIM_DIAG_KEEP = 1, 2, 16
+TAN_SIMFAM_NORM_IN_SWEEP, TAN_SIMFAM_CORR_DONE, TAN_SIMFAM_SWEEP_ONLY, TAN_SIMFAM_FINISH_ONLY, TAN_SIMFAM_ACC_ZEROED = 1, 2, 4, 8, 16
 _SIMFAM = os.environ.get("TAN_SIMFAM", "1") != "0"
 # the statistics sweep L2-normalises its frame panel itself (TAN_SIMFAM_NORM_IN_SWEEP); 0 = a separate l2n_fwd launch in front of it
 _SIMFAM_NORM = os.environ.get("TAN_SIMFAM_NORM", "1") != "0"
@@ -359,6 +362,7 @@ def simfam_ok(S, N, Mc, dtype, T=64):
     """Shapes `tan_simfam_fwd / bwd` take (include/tan_hip.h): bf16, <= 8 stages, <= 32 sentences per video, sweep columns a multiple
     of 8 within the resident sweep's limit, and a [T, N] same-video block the finishing launch can hold twice in a CU's LDS (the bound
     of `tan_simfam_fwd`: anything larger takes the separate-launch path instead of failing with BAD_ARG -- ADVICE r5)."""
+    # (restates `simfam_fin_lds` of csrc/tan_simnce.hip: change the two together)
     fin_lds = 4 * (2 * T * N + T + 256 + 96) + 4 * 32 + 32 + T + 16
     return (_SIMFAM and dtype == torch.bfloat16 and S <= 8 and N <= 32 and Mc % 8 == 0 and Mc < 32768
             and fin_lds <= 160 * 1024 and Mc <= _lib.lib().tan_simnce_max_cols())
@@ -375,7 +379,7 @@ class SimFam:
     """One feature family through `tan_simfam_fwd / tan_simfam_bwd` with its buffers (see `nce_family_stages` for the arguments).
     `run()` = forward and backward back to back (stage 1: the targets and the terms' upstream gradients depend on the batch alone);
     `sweep()` / `finish()` / `backward()` = the same launches in three calls for a loss whose targets (EMA self-labelling) and upstream
-    gradients (thresholds over BOTH families' forward results) arrive in between (stage 2, `Trainer._forward_backward_chains2`):
+    gradients (thresholds over BOTH families' forward results) arrive in between (stage 2, `chain_step.Stage2Step`):
     `tgt`, `g_v`, `g_t` are then buffers that other launches fill before the call that reads them."""
 
     def __init__(self, x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, col_invalid, B, T, N, nv, g_v, g_t, split_k=0, row_leak=None):
@@ -386,7 +390,7 @@ class SimFam:
         L = _lib.lib()
         bf = torch.bfloat16
         d = self.d = _lib.SimFamDesc()
-        d.S, d.St, d.B, d.T, d.N, d.C, d.Mc, d.flags = S, St, B, T, N, Cw, Mc, (1 if _SIMFAM_NORM else 0)
+        d.S, d.St, d.B, d.T, d.N, d.C, d.Mc, d.flags = S, St, B, T, N, Cw, Mc, (TAN_SIMFAM_NORM_IN_SWEEP if _SIMFAM_NORM else 0)
         d.x_video, d.v_grp_rows, d.v_off = _ptr8(x_video), v_grp[0], v_grp[1]
         d.x_text, d.t_grp_rows, d.t_off = _ptr8(x_text), t_grp[0], t_grp[1]
         if nv is not None:
@@ -431,7 +435,7 @@ class SimFam:
         d.flags = self.base_flags | flags
         d.g_v, d.g_t = (self.g_v.data_ptr(), self.g_t.data_ptr()) if with_g else (None, None)
         _lib.check(_lib.lib().tan_simfam_fwd(C.byref(d), ops._stream()), "tan_simfam_fwd")
-        self.base_flags |= d.flags & 2           # TAN_SIMFAM_CORR_DONE
+        self.base_flags |= d.flags & TAN_SIMFAM_CORR_DONE
 
     def run(self):
         self._fwd(0, True)
@@ -439,11 +443,11 @@ class SimFam:
 
     def sweep(self):
         self._acc.zero_()                        # the text-gradient accumulator, cleared here instead of in the backward's first launch
-        self.base_flags |= 16                    # TAN_SIMFAM_ACC_ZEROED
-        self._fwd(4, False)                      # TAN_SIMFAM_SWEEP_ONLY
+        self.base_flags |= TAN_SIMFAM_ACC_ZEROED
+        self._fwd(TAN_SIMFAM_SWEEP_ONLY, False)
 
     def finish(self):
-        self._fwd(8, False)                      # TAN_SIMFAM_FINISH_ONLY (the upstream gradients are not known yet: no corrections)
+        self._fwd(TAN_SIMFAM_FINISH_ONLY, False)         # (the upstream gradients are not known yet: no corrections)
 
     def backward(self):
         d = self.d

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib, dist, ops
-from .loss import get_loss, get_mask_from_time
+from .chain_step import Stage1Step, Stage2Step, text_pad_bool
+from .loss import _side_stream, get_loss, get_mask_from_time, prepare_inputs_async, simfam_ok
 from .tan_model import TemporalAligner, TwinTemporalAligner, _vp
 
 
@@ -121,7 +122,7 @@ class _GradReducer:
         self.stack_events = {}            # two-chain step: per stack, the event behind its reduction on the stack's role stream
         self.wire = None
         if tr.ddp_grad_dtype == "bf16":
-            w = tr.__dict__.get("_wire")
+            w = tr._wire
             if w is None or w.numel() != self.flat.numel() or w.device != self.flat.device:
                 w = tr._wire = torch.empty(self.flat.numel(), dtype=torch.bfloat16, device=self.flat.device)
             self.wire = w
@@ -211,7 +212,12 @@ class Trainer:
         self.ddp_bucket_layers = max(1, int(os.environ.get("TAN_DDP_BUCKET_LAYERS", "2") if ddp_bucket_layers is None
                                             else ddp_bucket_layers))
         self._comm_streams = {}
-        self._zero_ev = None
+        self._wire, self._s2_consts, self._bucket_cache = None, {}, {}      # caches, built on first use
+        # why `step` refuses to go on (a step failed half way through its optimizer launches); the last `forward_backward` ran as two chains
+        self._poisoned, self._last_step_chains = None, False
+        # per step (`step` / `zero_grad` set them, the schedule underneath reads them): the gradient fill's event; inside `step`; the
+        # stacks `early_update` has stepped (a set once `_early_ok` said yes); a pipelined step's out-events (`ChainsResult.out_ev`)
+        self._zero_ev, self._in_step, self._early, self._pipe_out = None, False, (), None
         # TAN_DDP_MODE -- how the flat gradient (39.9 M f32) is summed over ranks each step:
         #   "flat" (default)  ONE logical all-reduce of the whole gradient, what BASELINE.json's north_star states, issued in contiguous
         #                     pieces as they become final: in the two-chain step the video stack's 45 % when its chain ends (under the
@@ -260,9 +266,8 @@ class Trainer:
         batch after a resume at lambda(b + 1)."""
         if self.iter_per_epoch is None:
             return self.args.lr
-        lr_iter = getattr(self, "_lr_iter", None)
-        b = self.batches_seen if lr_iter is None else lr_iter
-        return self.args.lr * lr_multiplier(max(b + getattr(self, "_resume_bump", 0), 1), self.iter_per_epoch, self.args.epochs,
+        b = self.batches_seen if self._lr_iter is None else self._lr_iter
+        return self.args.lr * lr_multiplier(max(b + self._resume_bump, 1), self.iter_per_epoch, self.args.epochs,
                                             self.warmup)
 
     def _comm_order_stream(self, device):
@@ -361,37 +366,24 @@ class Trainer:
     def forward_backward(self, batch):
         a, m = self.args, self.model
         batch = self._embed_tokens(batch)
-        fused = self.fused_loss
-        if fused:       # the logits-free sweep keeps one LDS accumulator per text column: beyond its limit use materialised logits
+        fused = self._fused_sweep_fits(batch)
+        if self.fused_loss and not fused and self.global_negatives:
             Bn, Nn = batch["text_embed"].shape[:2]
-            cols = Bn * Nn
-            if batch.get("n_text") is not None and not self.global_negatives:
-                cols = min(cols, (batch["n_text"] + 63) // 64 * 64)
-            if cols > _lib.lib().tan_simnce_max_cols():
-                if self.global_negatives:
-                    raise _lib.TanHipError(f"global_negatives: {Bn}x{Nn} text columns per rank exceed the fused sweep's limit")
-                fused = False
+            raise _lib.TanHipError(f"global_negatives: {Bn}x{Nn} text columns per rank exceed the fused sweep's limit")
         if self.online.compute_dtype == torch.bfloat16 and batch["video"].is_cuda:
             batch = self._pad_sentence_slots(batch)          # (whole 64-row panels for the joint stack: both step schedules)
         self._last_step_chains = self._chains_eligible(batch, fused)
         if self._last_step_chains:
-            return self._forward_backward_chains2(batch) if self.twin else self._forward_backward_chains(batch)
-        # (`step` decided on pipelining from `_will_chain` before this point; should the two ever disagree, the autograd schedule below must
-        #  not start under the previous step's pending optimizer launches: wait for them here, on this stream)
-        for fl_ in [self.online._flat] + ([self.model.target._flat] if self.twin else []):
-            if fl_.in_step:
-                fl_.in_step = False
-                fl_.drain()
+            return (Stage2Step if self.twin else Stage1Step)(self, batch).run()
         if batch["video"].is_cuda:
             # what get_loss derives from the batch alone (masks, targets, column compaction: ~20 tiny launches) runs on the loss
             # side stream next to the forward instead of between the stacks and the similarity sweeps
-            from .loss import prepare_inputs_async
             batch = dict(batch)
             Tn, Nn = batch["video"].shape[1], batch["text_embed"].shape[1]
             batch["_loss_prep"] = prepare_inputs_async(batch, batch["padding_mask"], batch["text_padding_mask"], Tn, Nn,
                                                        batch["video"].device, a, batch.get("n_text"),
                                                        want_compaction=bool(fused) and not self.global_negatives)
-        tp_bool = batch["_text_pad_bool"] if batch.get("_text_pad_bool") is not None else batch["text_padding_mask"].bool()
+        tp_bool = text_pad_bool(batch)
         logits = m(batch["video"], batch["text_embed"], video_padding_mask=batch["padding_mask"],
                    lang_padding_mask=tp_bool, text_timestamp=batch.get("_tgt_raw"),
                    abs_text_pos=batch.get("abs_text_pos"),
@@ -418,6 +410,17 @@ class Trainer:
         loss_dict["loss"].backward()
         return loss_dict
 
+    def _sweep_cols(self, batch):
+        """text columns of the similarity sweep: every sentence slot, or (rank-local negatives) the real sentences in whole 64-column tiles"""
+        Bn, Nn = batch["text_embed"].shape[:2]
+        nt = batch.get("n_text")
+        return Bn * Nn if nt is None or self.global_negatives else min(Bn * Nn, (int(nt) + 63) // 64 * 64)
+
+    def _fused_sweep_fits(self, batch):
+        """The loss runs logits-free for this batch: the fused sweep keeps one LDS accumulator per text column; beyond its limit the step
+        uses materialised logits.  The ONE copy of the decision: `_will_chain` (for `step`) and `forward_backward` both ask here."""
+        return self.fused_loss and self._sweep_cols(batch) <= _lib.lib().tan_simnce_max_cols()
+
     def _chains_eligible(self, batch, fused):
         """Stage 1 ('init': multi-positive NCE only, train/readme.md:10) on the fused bf16 path with rank-local negatives: the loss is
         (loss_dual + loss_joint) / 2 with weights that depend on the batch's masks only, so the step runs as two chains that never wait
@@ -433,7 +436,7 @@ class Trainer:
 
     def _chains2_eligible(self, batch):
         """Stage 2 ('cotrain' as train/readme.md:13 runs it: EMA self-labelling, loss threshold, alignability head + BCE) on the fused bf16
-        path with rank-local statistics: the step runs as two chains as well (`_forward_backward_chains2`), synchronised where the loss
+        path with rank-local statistics: the step runs as two chains as well (`chain_step.Stage2Step`), synchronised where the loss
         needs both families -- the agreement targets (both EMA stacks) and the thresholds / labels (both online families' forward).
         TAN_STAGE2_CHAINS=0: forward -> get_loss -> backward under autograd."""
         a, m, tg = self.args, self.online, self.model.target
@@ -445,11 +448,7 @@ class Trainer:
                 and m._chains_ok(video, lang, allow_head=True) and tg._chains_ok(video, lang, allow_head=True)
                 and tg.compute_dtype == m.compute_dtype and not m.use_text_pos_enc):
             return False
-        from .loss import simfam_ok
-        Mp = B * N
-        nt = batch.get("n_text")
-        Mc = Mp if nt is None else min(Mp, (int(nt) + 63) // 64 * 64)
-        return all(simfam_ok(S, N, Mc, torch.bfloat16, T) for S in (m.num_encoder_layers, m.num_decoder_layers))
+        return all(simfam_ok(S, N, self._sweep_cols(batch), torch.bfloat16, T) for S in (m.num_encoder_layers, m.num_decoder_layers))
 
     @staticmethod
     def _pad_sentence_slots(batch):
@@ -481,296 +480,8 @@ class Trainer:
             out["abs_text_pos"] = torch.cat([ap, torch.zeros(B, extra, ap.shape[2], dtype=ap.dtype, device=ap.device)], 1)
         return out
 
-    def _forward_backward_chains(self, batch):
-        from .loss import _ManualCtx, _NCETail, nce_family_stages, nce_term_grads, prepare_inputs_async
-        a, m = self.args, self.online
-        video, lang = batch["video"], batch["text_embed"]
-        B, T = video.shape[:2]
-        N = lang.shape[1]
-        dev = video.device
-        Se, Sd = m.num_encoder_layers, m.num_decoder_layers
-        main = torch.cuda.current_stream()
-        # everything the loss derives from the batch alone, incl. the gradients of the NCE terms, on the loss side stream
-        prep = prepare_inputs_async(batch, batch["padding_mask"], batch["text_padding_mask"], T, N, dev, a, batch.get("n_text"),
-                                    want_compaction=True)
-        from .loss import _side_stream
-        ls = _side_stream(dev)
-        with torch.cuda.stream(ls):
-            nv = prep.get("nv")
-            cols_tail = prep["cols_pos_c"] if nv is not None else prep["cols_pos"]
-            g_v_d, g_t_d, g_v_j, g_t_j, _ = nce_term_grads(prep["rows_pos"], cols_tail, Se, Sd)
-            ready = ls.record_event()
-        tgt, ci = prep["tgt"], prep["tpad_u8"].view(B * N)
-
-        def family(which, x_video, v_grp, x_text, t_grp, d_video, d_text):
-            torch.cuda.current_stream().wait_event(ready)          # (a finished event costs nothing)
-            gv, gt = (g_v_d, g_t_d) if which == "dual" else (g_v_j, g_t_j)
-            return nce_family_stages(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, ci, B, T, N, nv, gv, gt)
-        pipe = None
-        if getattr(self, "_in_step", False) and self.online._flat.in_step:
-            pipe = {"zero": self._zero_ev}               # (each chain waits for the fill in front of its first backward kernel)
-        elif self._zero_ev is not None:                  # the gradient buffer's fill ran on a side stream
-            main.wait_event(self._zero_ev)
-        self._zero_ev = None
-        tp_bool = batch["_text_pad_bool"] if batch.get("_text_pad_bool") is not None else batch["text_padding_mask"].bool()
-        early_v = early_j = None
-        if getattr(self, "_in_step", False):
-            early = os.environ.get("TAN_OPT_EARLY", "1") != "0" and self._early_ok()
-            ddp, gs = self._ddp, 1.0 / dist.world_size()
-
-            def stack_done(which):
-                # (main host thread, current stream = the one that carries the stack's last weight gradients) data parallel: the stack's
-                # slice of the gradient is summed over ranks first; then its matrices may be stepped
-                reduced = ddp.stack_done(which) if ddp is not None else True
-                if ddp is not None:
-                    # the remainder's optimizer launch (main stream) reads this stack's bias / LayerNorm gradients: behind the stack's
-                    # collective AND the bf16 wire's cast back to f32, which run on this role stream
-                    ddp.stack_events[which] = torch.cuda.current_stream().record_event()
-                if early and reduced:
-                    self.early_update(which, gs)
-            if early or ddp is not None:
-                early_v, early_j = (lambda: stack_done("video")), (lambda: stack_done("joint"))       # noqa: E731
-        tail = {}
-
-        def loss_tail():
-            # the masked means of the four term tensors (loss.py:254-275), on the main stream right behind the video stack's backward:
-            # the joint family's terms were final ~1.5 ms earlier on their stream; issued at the end of the step the launch sat between
-            # the embeddings' backward and the optimizer launch (4.126 -> 4.078 ms per step, ABBA x2 of 60 steps)
-            terms, ready = m._joint_terms
-            if not ready.wait(timeout=60.0) or not terms:
-                raise _lib.TanHipError("the joint chain did not reach its loss family")      # (`_run_chains` re-raises the chain's own error)
-            v_j_, t_j_, ev_j = terms[0]
-            main.wait_event(ev_j)
-            v_d_, t_d_ = m._dual_terms
-            for t in (v_j_, t_j_):
-                t.record_stream(main)
-            tail["out"] = _NCETail.forward(_ManualCtx(), v_d_, t_d_, v_j_, t_j_, prep["rows_pos"], cols_tail, None)
-        v_d, t_d, v_j, t_j = m._run_chains(video, lang, m._mask_u8(batch["padding_mask"]), m._mask_u8(tp_bool), family, early_v, early_j,
-                                           pipe=pipe, mid=loss_tail, need_d_lang=lang.requires_grad)
-        m._joint_terms = m._dual_terms = None
-        if lang.requires_grad:
-            # the step started from token ids: the sentence embeddings' gradient (the embeddings' backward produced it) goes on through
-            # the language model under autograd (index_select of `embed_sentences`, Word2VecModel's HIP nodes), on this stream
-            lang.backward(m.__dict__.pop("_chain_d_lang").to(lang.dtype))
-        for t in (g_v_d, g_t_d, g_v_j, g_t_j, cols_tail, prep["rows_pos"], v_j, t_j):
-            t.record_stream(main)
-        loss_dual, loss_joint, loss_mean = tail["out"]
-        if pipe is not None:
-            self._pipe_out = pipe["out"]
-        return {"loss-dual": loss_dual, "loss-joint": loss_joint, "loss": loss_mean}
-
-    def _forward_backward_chains2(self, batch):
-        """Stage-2 co-training step (train/main.py:89-98,122; train/loss.py:88-229,277-373) as two chains without autograd:
-            main:  EMA video stack -> cosines | online video stack -> sweep(dual)  .. finish(dual)  .. backward(dual)  -> stack backward
-            side:  EMA joint stack -> cosines | online joint stack -> head -> sweep(joint) .. finish(joint) .. backward(joint) + head -> stack backward
-        with two meeting points: (1) the agreement targets need both EMA stacks' same-video cosines (small launches on the loss stream,
-        issued by the main chain's host thread: they are through long before the online sweeps are); (2) the terms' upstream gradients
-        need both families' forward results -- per-sentence maxima -> z-scores / quantile threshold / kept rows, alignability labels,
-        BCE (train/loss.py:277-357) -- issued on the main chain's stream between its family's finishing launch and backward.
-        Every launch is the one `get_loss` issues on the autograd path (same kernels, `tan_simfam_*` for the families)."""
-        import threading
-        from .loss import (SimFam, _Blocks, _diag_max, _pos_masks, _side_stream, agreement_targets, prepare_inputs_async, stage2_masks)
-        from .loss import _p
-        a, m, tg = self.args, self.online, self.model.target
-        video, lang = batch["video"], batch["text_embed"]
-        B, T = video.shape[:2]
-        N = lang.shape[1]
-        R, Mp, L = B * T, B * N, T + N
-        dev = video.device
-        Se, Sd, Cw = m.num_encoder_layers, m.num_decoder_layers, 512
-        lib = _lib.lib()
-        main = torch.cuda.current_stream()
-        ls = _side_stream(dev)
-        prep = prepare_inputs_async(batch, batch["padding_mask"], batch["text_padding_mask"], T, N, dev, a, batch.get("n_text"),
-                                    want_compaction=True)
-        nv = prep.get("nv")
-        Mc = nv[0].shape[0] if nv is not None else Mp
-        tpad_u8, ci = prep["tpad_u8"], prep["tpad_u8"].view(Mp)
-        tp_bool = batch["_text_pad_bool"] if batch.get("_text_pad_bool") is not None else batch["text_padding_mask"].bool()
-        vmask, tmask = m._mask_u8(batch["padding_mask"]), m._mask_u8(tp_bool)
-        # buffers that the meeting points fill (their addresses go into the families' descriptors up front)
-        tgt = torch.empty(B, T, N, device=dev)
-        g = {"dual": (torch.empty(Se, R, device=dev), torch.empty(Se, Mc, device=dev)),
-             "joint": (torch.empty(Sd, R, device=dev), torch.empty(Sd, Mc, device=dev))}
-        d_head = torch.empty(Mp, device=dev)                    # d loss / d alignability logits of joint stage 2 (train/loss.py:341)
-        # host-side hand-overs between the two issuing threads (an event can only be waited for once it has been recorded) + their events
-        flags = {k: threading.Event() for k in ("ema_joint", "tgt", "fin_joint", "g")}
-        evs, fams, ema_diag, failed, aux, head = {}, {}, {}, [], {}, {}
-
-        def hand_over(name):
-            if not flags[name].wait(timeout=120.0) or failed:
-                err = _lib.TanHipError(f"stage-2 step: the other chain did not reach '{name}'" + (f" ({failed[0]} chain failed)" if failed else ""))
-                err.tan_consequence = True          # (`_run_chains` reports the other thread's error instead)
-                raise err
-            return evs[name]
-
-        def guarded(fn):
-            def run(*args_, **kw):
-                try:
-                    return fn(*args_, **kw)
-                except BaseException:
-                    failed.append(args_[0] if args_ else "?")
-                    for f_ in flags.values():       # the other thread must not wait out its timeout
-                        f_.set()
-                    raise
-            return run
-
-        # ---- the EMA target (tan_model.py:346-351 `forward_from_ema`, no gradient): its input embeddings here, its stacks on the chains
-        with torch.no_grad():
-            tg._ensure_flat()
-            fe_t = tg._embed_fused(video, lang, vmask, tmask, 0, 0, 0, False)
-
-        @guarded
-        def pre(which):
-            cur = torch.cuda.current_stream()
-            with torch.no_grad():
-                ema_diag[which] = tg._ema_stack_diag(which, fe_t, vmask, tmask, B, T, N)
-            evs["ema_" + which] = cur.record_event()
-            if which == "joint":
-                flags["ema_joint"].set()
-
-        def targets():
-            # meeting point 1, on the loss stream: train/loss.py:88-229 (self-labelling of both EMA families, agreement 'keep' / ...,
-            # de-duplication) + the positive masks of loss.py:236-237
-            hand_over("ema_joint")
-            ls.wait_event(evs["ema_video"])
-            ls.wait_event(evs["ema_joint"])
-            ls.wait_event(prep["_event"])
-            with torch.cuda.stream(ls):
-                for t_ in ema_diag.values():
-                    t_.record_stream(ls)
-                J, D, _, iou, conf = agreement_targets(_Blocks.of_diag(ema_diag["joint"]), _Blocks.of_diag(ema_diag["video"]), prep, B, T, N,
-                                                       a.temporal_agreement_type, tgt=tgt)
-                rows_pos, cols_pos = _pos_masks(tgt, tpad_u8, B, T, N)
-                cols_tail = cols_pos.index_select(0, nv[0]) if nv is not None else cols_pos
-                evs["tgt"] = ls.record_event()
-            aux.update(max_position_joint=J["max_pos"], max_position_dual=D["max_pos"], max_logits_joint=J["max_logit"],
-                       max_logits_dual=D["max_logit"], joint_self_tgt=J["tgt"], dual_self_tgt=D["tgt"], iou=iou, confidence_mask=conf,
-                       agreement_tgt=tgt, rows_pos=rows_pos, cols_tail=cols_tail)
-            flags["tgt"].set()
-
-        def upstream():
-            # meeting point 2, on the main chain's stream: train/loss.py:277-357 and the tail's backward
-            cur = torch.cuda.current_stream()
-            fd, fj = fams["dual"], fams["joint"]
-            fj.record_stream(cur)
-            md, mj = head["md"], head["mj"]          # per-sentence maxima (loss.py:280,283): each chain's own launch behind its finish
-            mj.record_stream(cur)
-            s2 = stage2_masks(md, mj, tpad_u8, tgt, batch.get("abs_text_pos"), aux["confidence_mask"], a.loss_threshold, True, B, T, N)
-            cols_th = s2["th_f"].index_select(0, nv[0]) if nv is not None else s2["th_f"]
-            out_th = torch.empty(5, device=dev)              # [loss_dual_th, loss_joint_th, their mean, n_rows, n_cols]
-            _lib.check(lib.tan_nce_tail_fwd(_p(fd.v_terms), _p(fd.t_terms), _p(fj.v_terms), _p(fj.t_terms), _p(s2["rows"]), _p(cols_th),
-                                            C.c_int(Se), C.c_int(Sd), C.c_long(R), C.c_long(Mc), _p(out_th), _p(out_th[3:]), None,
-                                            ops._stream()), "tan_nce_tail_fwd")
-            one, gb = self._stage2_consts(dev)
-            _lib.check(lib.tan_nce_tail_bwd(None, None, _p(one), _p(s2["rows"]), _p(cols_th), _p(out_th[3:]), C.c_int(Se), C.c_int(Sd),
-                                            C.c_long(R), C.c_long(Mc), _p(g["dual"][0]), _p(g["dual"][1]), _p(g["joint"][0]),
-                                            _p(g["joint"][1]), ops._stream()), "tan_nce_tail_bwd")
-            # BCE of the alignability head on joint stage 2 (loss.py:341-349), forward and backward
-            a_joint = head["a_j2"]
-            a_joint.record_stream(cur)
-            bce = torch.empty(2, device=dev)
-            _lib.check(lib.tan_bce_sel_fwd(_p(a_joint), _p(s2["y"]), _p(s2["sel"]), _p(s2["scal"]), C.c_int(Mp), _p(bce), ops._stream()),
-                       "tan_bce_sel_fwd")
-            _lib.check(lib.tan_bce_sel_bwd(_p(a_joint), _p(s2["y"]), _p(s2["sel"]), _p(s2["scal"]), _p(gb), C.c_int(Mp), _p(d_head),
-                                           ops._stream()), "tan_bce_sel_bwd")
-            evs["g"] = cur.record_event()
-            flags["g"].set()
-            aux.update(t_th_mask=s2["th_mask"], max_logits_dual_per_text=md, max_logits_joint_per_text=mj, t_align_th_mask=s2["lab"],
-                       out_th=out_th, bce=bce, s2=s2)
-
-        @guarded
-        def family(which, x_video, v_grp, x_text, t_grp, d_video, d_text):
-            cur = torch.cuda.current_stream()
-            cur.wait_event(prep["_event"])
-            fam = fams[which] = SimFam(x_video, v_grp, x_text, t_grp, d_video, d_text, tgt, ci, B, T, N, nv, *g[which])
-            fam.sweep()
-            if which == "joint":
-                # alignability head on the text rows of joint stage 2 (tan_model.py:147-148; the only stage the loss reads, loss.py:341)
-                jt = torch.empty(Mp, Cw, dtype=x_text[2].dtype, device=dev)
-                ops.rows_copy(x_text[2], jt, B, N, Cw, L, T, N, 0)
-                a_j2 = torch.empty(Mp, device=dev)
-                ops.head_fwd(jt, m._f("binary_head.weight").view(-1), m._f("binary_head.bias"), a_j2, Mp, Cw)
-                head.update(jt=jt, a_j2=a_j2)
-                cur.wait_event(hand_over("tgt"))
-                fam.finish()
-                head["mj"] = _diag_max(_Blocks.of_diag(fam.diag_last), None, B, T, N)
-                evs["fin_joint"] = cur.record_event()
-                flags["fin_joint"].set()
-                cur.wait_event(hand_over("g"))
-            else:
-                targets()
-                cur.wait_event(evs["tgt"])
-                fam.finish()
-                head["md"] = _diag_max(_Blocks.of_diag(fam.diag_last), None, B, T, N)
-                cur.wait_event(hand_over("fin_joint"))
-                upstream()
-            fam.backward()
-            if which == "joint":
-                d_jt = torch.empty(Mp, Cw, dtype=head["jt"].dtype, device=dev)
-                ops.head_bwd(d_head, head["jt"], m._f("binary_head.weight").view(-1), d_jt, m._g("binary_head.weight").view(-1),
-                             m._g("binary_head.bias"), Mp, Cw)
-                ops.rows_copy(d_jt, d_text[2], B, N, Cw, N, 0, L, T, accumulate=True)
-                d_head.record_stream(cur)
-            return fam.v_terms, fam.t_terms
-
-        pipe = None
-        if getattr(self, "_in_step", False) and m._flat.in_step:
-            pipe = {"zero": self._zero_ev}
-        elif self._zero_ev is not None:
-            main.wait_event(self._zero_ev)
-        self._zero_ev = None
-        early_v = early_j = None
-        if getattr(self, "_in_step", False):
-            early = os.environ.get("TAN_OPT_EARLY", "1") != "0" and self._early_ok()
-            ddp, gs = self._ddp, 1.0 / dist.world_size()
-
-            def stack_done(which):
-                reduced = ddp.stack_done(which) if ddp is not None else True
-                if ddp is not None:
-                    ddp.stack_events[which] = torch.cuda.current_stream().record_event()
-                if early and reduced:
-                    self.early_update(which, gs)
-            if early or ddp is not None:
-                early_v, early_j = (lambda: stack_done("video")), (lambda: stack_done("joint"))       # noqa: E731
-        m._run_chains(video, lang, vmask, tmask, family, early_v, early_j, pipe=pipe, need_d_lang=lang.requires_grad,
-                      pre={"video": lambda: pre("video"), "joint": lambda: pre("joint")})
-        m._joint_terms = m._dual_terms = None
-        tg._release_ws(fe_t["em"])
-        if lang.requires_grad:
-            lang.backward(m.__dict__.pop("_chain_d_lang").to(lang.dtype))
-        # ---- the loss dictionary (monitoring entries on the loss stream; train/loss.py:296-304,359-373)
-        fd, fj = fams["dual"], fams["joint"]
-        out_th, bce = aux.pop("out_th"), aux.pop("bce")
-        s2 = aux.pop("s2")
-        with torch.cuda.stream(ls):
-            ls.wait_event(evs["g"])
-            for f_ in (fd, fj):
-                f_.record_stream(ls)
-            out_all = torch.empty(5, device=dev)
-            _lib.check(lib.tan_nce_tail_fwd(_p(fd.v_terms), _p(fd.t_terms), _p(fj.v_terms), _p(fj.t_terms), _p(aux["rows_pos"]),
-                                            _p(aux["cols_tail"]), C.c_int(Se), C.c_int(Sd), C.c_long(R), C.c_long(Mc), _p(out_all),
-                                            _p(out_all[3:]), None, ops._stream()), "tan_nce_tail_fwd")
-            loss = out_th[2] + bce[0]
-        main.wait_stream(ls)
-        # (allocator bookkeeping for what crossed streams: main joined `ls` just above and joined the side stream inside `_run_chains`,
-        #  so a block freed after this point is safe for main's allocator; what was allocated under `ls` / the side stream and read on
-        #  main is recorded here -- a minimal set: ~130 record_stream calls cost 0.13 ms of host time at the end of every step)
-        for t_ in (out_all, loss, aux["confidence_mask"], head["mj"], head["a_j2"]):
-            t_.record_stream(main)
-        for t_ in prep["_tensors"]:
-            t_.record_stream(main)
-        fj.record_stream(main)
-        if pipe is not None:
-            self._pipe_out = pipe["out"]
-        if self.keep_aux:
-            self.last_aux = {k: v for k, v in aux.items() if k not in ("rows_pos", "cols_tail")}
-        return {"loss-dual": out_th[0], "loss-joint": out_th[1], "loss-dual-all": out_all[0], "loss-joint-all": out_all[1],
-                "loss-total": out_all[2], "loss-joint-bce": bce[0], "alignability_top1": bce[1], "confidence-ratio": s2["scal"][3],
-                "iou-threshold": torch.full((), 0.5, device=dev), "loss": loss}
-
     def _stage2_consts(self, dev):
-        c = self.__dict__.setdefault("_s2_consts", {})
+        c = self._s2_consts
         if dev not in c:
             c[dev] = (torch.ones(1, device=dev), torch.tensor([1.0, 0.0], device=dev))      # d loss / d (mean NCE), d loss / d (bce, top-1)
         return c[dev]
@@ -814,7 +525,7 @@ class Trainer:
         ema = self.model.target._ensure_flat() if self.twin else None
         self.iteration += 1
         if self._images_in_optimizer(f, ema):
-            early = self.__dict__.pop("_early", ())          # stacks `early_update` already stepped (same step count, lr, grad_scale)
+            early, self._early = self._early, ()             # stacks `early_update` already stepped (same step count, lr, grad_scale)
             u0 = 0
             if early:
                 assert "video" in early, early              # (units: video stack, joint stack, pre-projections)
@@ -928,7 +639,7 @@ class Trainer:
     def _ddp_buckets(self, tag, layers):
         """[(lo, hi, last_layer)] in the order backward finishes them (last layers first): `bucket_layers` consecutive layers of
         one stack per bucket; the bucket is final once layer `last_layer` (its lowest) is.  Cached per stack."""
-        cache = self.__dict__.setdefault("_bucket_cache", {})
+        cache = self._bucket_cache
         key = (tag, layers, self.ddp_bucket_layers)
         if key not in cache:
             prefix = {"video": "video_temporal_encoder.", "joint": "joint_temporal_encoder."}[tag]
@@ -949,14 +660,7 @@ class Trainer:
         """Whether `forward_backward` will take the two-chain path for this batch (decided before the step touches anything)."""
         if not batch["video"].is_cuda or "text_embed" not in batch:
             return False
-        fused = self.fused_loss
-        if fused:
-            Bn, Nn = batch["text_embed"].shape[:2]
-            cols = Bn * Nn
-            if batch.get("n_text") is not None and not self.global_negatives:
-                cols = min(cols, (batch["n_text"] + 63) // 64 * 64)
-            fused = cols <= _lib.lib().tan_simnce_max_cols()
-        return self._chains_eligible(batch, fused)
+        return self._chains_eligible(batch, self._fused_sweep_fits(batch))
 
     def step(self, batch):
         """One optimizer step on an already device-resident batch (see to_device_batch): zero_grad -> forward -> loss -> backward ->
@@ -968,7 +672,7 @@ class Trainer:
         weight-gradient launches and the optimizer launches of their matrices still running on their role streams; their events wait
         in `_Flat.pending`, the next step waits for each where it needs it, anything else that touches the parameters goes through
         `_ensure_flat()` / `state_dict()`, which wait for all of them."""
-        if getattr(self, "_poisoned", None):
+        if self._poisoned:
             raise _lib.TanHipError(self._poisoned)
         if not self._params_synced:
             self.sync_parameters()
@@ -978,15 +682,14 @@ class Trainer:
         if self.online.compute_dtype == torch.bfloat16 and batch["video"].is_cuda and "text_embed" in batch:
             batch = self._pad_sentence_slots(batch)      # (before the schedule is decided: stage 2's eligibility depends on the padded N)
         piped = self.pipeline and fl.bound() and (tfl is None or tfl.bound()) and self._will_chain(batch)
-        fl.in_step = piped                     # (a pipelined step waits for what the previous one left running itself, piece by piece)
-        if tfl is not None:
-            tfl.in_step = piped
+        flats = [fl] + ([tfl] if tfl is not None else [])
+        for f_ in flats:                       # (a pipelined step waits for what the previous one left running itself, piece by piece)
+            f_.in_step = piped
         self._pipe_out = None
         try:
             dev0 = self.online._ensure_flat().flat.device        # (not pipelined: waits for everything pending)
             aside = None
             if dev0.type == "cuda":      # the gradient fill and the image refresh run on a side stream, next to the forward's first kernels
-                from .loss import _side_stream
                 aside = _side_stream(dev0)
             self.zero_grad(side=aside)
             world = dist.world_size()
@@ -1002,10 +705,10 @@ class Trainer:
             except BaseException:
                 self._ddp = None
                 self._join_role_streams(dev0)          # nothing of the failed step is recorded in `pending`: join what it enqueued
-                fl.pending = {}
-                if tfl is not None:
-                    tfl.pending = {}
-                if self.__dict__.pop("_early", None):
+                for f_ in flats:
+                    f_.pending = {}
+                early, self._early = self._early, ()
+                if early:
                     # `early_update` has already stepped a stack's matrices with this step's count: the parameters are half way between
                     # two steps and a retried step would apply AdamW to them twice -- say so instead of going on
                     self._poisoned = ("a training step failed after the early optimizer launch of a stack: parameters are inconsistent; "
@@ -1021,13 +724,12 @@ class Trainer:
                 # launches, not behind the optimizer launches that follow those on their streams
                 # (the last weight-gradient launches only write matrix gradients, which the early launches step; without those this launch
                 #  steps the matrices too and waits for them.  Single-call data parallelism reduces everything here: same)
-                if not self.__dict__.get("_early"):
+                if not self._early:
                     cur = torch.cuda.current_stream()
                     for k in ("video", "joint"):
                         cur.wait_event(out_ev[k])
-                fl.pending = {}                # (every event of the previous step has been waited for inside this one)
-                if tfl is not None:
-                    tfl.pending = {}
+                for f_ in flats:               # (every event of the previous step has been waited for inside this one)
+                    f_.pending = {}
             if self._ddp is not None:
                 ev = None
                 if self.time_comm:
@@ -1040,19 +742,16 @@ class Trainer:
                     self.comm_events.append(ev)
             self.optimizer_step(grad_scale=gscale)
             if out_ev is not None:
-                fl.run_image_hooks()           # the LayerNorm'ed position tables: one small launch, on this stream
-                fl.pending = dict(out_ev)
-                if tfl is not None:            # (the same launches wrote the twin's parameters and images)
-                    tfl.run_image_hooks()
-                    tfl.pending = dict(out_ev)
+                for f_ in flats:               # (the same launches wrote the twin's parameters and images)
+                    f_.run_image_hooks()       # the LayerNorm'ed position tables: one small launch, on this stream
+                    f_.pending = dict(out_ev)
             elif aside is not None:
                 self.online._ensure_flat_nosync().refresh_images_async(aside, backward=True)
                 if self.twin:
                     self.model.target._ensure_flat_nosync().refresh_images_async(aside, backward=False)
         finally:
-            fl.in_step = False
-            if tfl is not None:
-                tfl.in_step = False
+            for f_ in flats:
+                f_.in_step = False
             self._pipe_out = None
         self.batches_seen += 1
         self._resume_bump = 0
@@ -1062,7 +761,6 @@ class Trainer:
         """The current stream waits for everything enqueued on the step's role streams (the failure path of `step`)."""
         if dev.type != "cuda":
             return
-        from .loss import _side_stream
         cur = torch.cuda.current_stream()
         streams = [_lib.role_stream(dev, r) for r in ("loss", "opt")] + [_side_stream(dev), self.online._side_stream(dev)]
         for st in streams:
@@ -1076,7 +774,7 @@ class Trainer:
         if not dist.active():
             return None
         flat = self.online.flat_grad()
-        if self.ddp_mode == "single" or (self.ddp_mode == "flat" and not self.__dict__.get("_last_step_chains")):
+        if self.ddp_mode == "single" or (self.ddp_mode == "flat" and not self._last_step_chains):
             ranges = [(0, flat.numel())]
         elif self.ddp_mode == "flat":
             ranges = [self.online.flat_range("video_temporal_encoder."), self.online.flat_range("joint_temporal_encoder.")]

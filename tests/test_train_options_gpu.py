@@ -343,7 +343,7 @@ def test_small_batch_split_launches_match_the_whole_panel_launches(stage, tmp_pa
                                       {"TAN_STEP_PIPELINE": "0", "TAN_OPT_EARLY": "0", "TAN_OPT_IMAGES": "0"}])
 def test_stage2_chain_step_matches_the_autograd_step_under_every_schedule_switch(monkeypatch, switches):
     """Stage 2 ('cotrain': EMA forward, self-labelling, threshold 0.5, alignability head + BCE) in bf16 at B = 8: `Trainer.step` as two
-    chains with two meeting points (`_forward_backward_chains2`) against forward -> EMA forward -> get_loss -> loss.backward() under
+    chains with two meeting points (`chain_step.Stage2Step`) against forward -> EMA forward -> get_loss -> loss.backward() under
     autograd (TAN_STAGE2_CHAINS=0), with the step pipelined or joined, the stacks' optimizer launches early or at the end, the weight
     images from the optimizer launch or rebuilt: every entry of the first step's loss dict, and the online AND EMA parameters after three
     steps (same kernels on the same values up to the order of f32 atomics; a batch this small has no sentence near a threshold).

@@ -410,6 +410,25 @@ int tan_adamw_step_images(const tan_adamw_images_desc* d, void* stream);
 /* target = m*target + (1-m)*online  (TwinTemporalAligner._momentum_update, tan_model.py:339-344) */
 int tan_ema_update(float* target, const float* online, long n, float m, void* target_bf16, void* stream);
 
+/* ---- per-parameter gradient clipping over the flat f32 gradient buffer (utils/train_utils.py:3-13, called at train/main.py:115-116) ----
+ * Every parameter tensor is a SEGMENT of g [n] (n < 2^31), cut into chunks of at most tan_clip_chunk() elements.  chunk_table (DEVICE,
+ * int32 [n_chunks][4], 16-byte aligned) = (off, len, seg, 0) per chunk; seg_table (DEVICE, int32 [n_segs][2]) = (first_chunk, n_chunks)
+ * per segment, a segment's chunks consecutive.  Both calls work on the chunks [c0, c1) and the segments [s0, s1), which must hold
+ * exactly those chunks (a caller orders the tables so that one range is one group of parameters); one workgroup per chunk, no atomics:
+ * the same input gives the same bits whatever the scheduling.  A table entry outside [0, n), or a segment that is not wholly inside
+ * the ranges, is skipped.
+ *   tan_clip_sumsq   partials[chunk] = the chunk's sum of squares (f32: per-thread accumulators, wave tree, four waves through LDS).
+ *   tan_clip_apply   per segment: norm = sqrt(sum of its partials, in table order, in double) * grad_scale, coef = clip / (norm + 1e-6f);
+ *                    g[segment] *= coef if coef < 1, otherwise nothing is stored (a NaN norm leaves the segment as it is, like the
+ *                    reference's `if clip_coef < 1`); norms[seg] = norm.  g keeps the UNSCALED gradient: grad_scale (1 / world size) is
+ *                    what tan_adamw_step applies afterwards, so norm is the norm of the gradient the optimizer sees.
+ * Elements between segments (alignment padding) are never read or written. */
+int tan_clip_chunk(void);
+int tan_clip_sumsq(const float* g, const int* chunk_table, const int* seg_table, int c0, int c1, int s0, int s1, long n,
+                   float* partials, void* stream);
+int tan_clip_apply(float* g, const int* chunk_table, const int* seg_table, int c0, int c1, int s0, int s1, long n,
+                   const float* partials, float clip, float grad_scale, float* norms, void* stream);
+
 /* ---- one TemporalEncoder stack (tfm_model.py:41-55), forward and backward in one call each -----------------
  * Weights are `dtype` (f32, or the bf16 shadow copies); biases / LayerNorm affine / all gradients are f32 and
  * gradients are ACCUMULATED.  Layouts: w_qkv [3C,C] (in_proj_weight, q|k|v), w_out [C,C], w_fc [4C,C], w_proj [C,4C]. */

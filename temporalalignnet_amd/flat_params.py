@@ -145,6 +145,62 @@ class _Flat:
             self._image_table = (tab, pre_t, len(ents), prefix[-1], ranges)
         return self._image_table
 
+    def clip_tables(self):
+        """For tan_clip_sumsq / tan_clip_apply (per-parameter gradient clipping): every parameter is one SEGMENT of the flat gradient,
+        cut into chunks of at most tan_clip_chunk() elements; the padding between parameters belongs to no chunk.  Segments are ordered
+        [matrices of the video stack | the other stacks' matrices (the joint stack) | everything else] -- the three groups
+        `Trainer.early_update` / `optimizer_step` step (`video_units`, `mats_units`, the rest) -- so that one chunk range and one
+        segment range select a group.  Host side (numpy, no device needed): names [n_segs] in segment order, chunks int32
+        [n_chunks, 4] = (off, len, seg, 0), segs int32 [n_segs, 2] = (first_chunk, n_chunks), chunk_bounds / seg_bounds = the four
+        boundaries of the three groups.  Built once."""
+        t = self.__dict__.get("_clip_tables")
+        if t is None:
+            import types
+            import numpy as np
+            if self.total >= 2 ** 31:
+                raise _lib.TanHipError(f"gradient clipping: {self.total} elements do not fit the int32 chunk table")
+            chunk = ops.clip_chunk()
+            mats = [n for n in self.names if ".resblocks." in n and len(self.off[n][2]) == 2]
+            video = [n for n in mats if n.startswith("video_temporal_encoder.")]
+            other = [n for n in mats if not n.startswith("video_temporal_encoder.")]
+            in_mats = set(mats)
+            groups = [video, other, [n for n in self.names if n not in in_mats]]
+            names, chunks, segs, cb, sb = [], [], [], [0], [0]
+            for grp in groups:
+                for n in grp:
+                    o, k, _ = self.off[n]
+                    segs.append((len(chunks), (k + chunk - 1) // chunk))
+                    chunks += [(o + i, min(chunk, k - i), len(names), 0) for i in range(0, k, chunk)]
+                    names.append(n)
+                cb.append(len(chunks))
+                sb.append(len(names))
+            t = self._clip_tables = types.SimpleNamespace(
+                names=names, chunks=np.asarray(chunks, dtype=np.int32).reshape(-1, 4), segs=np.asarray(segs, dtype=np.int32).reshape(-1, 2),
+                chunk_bounds=tuple(cb), seg_bounds=tuple(sb), chunk=chunk)
+        return t
+
+    def clip_device(self):
+        """`clip_tables()` on the gradient's device, with the two buffers the launches write, allocated once: partials [n_chunks] and
+        norms [n_segs] f32.  (`Trainer` builds this on ONE thread before the two host threads of a two-chain step use it, each with
+        its own group: disjoint ranges of both buffers.)"""
+        d = self.__dict__.get("_clip_dev")
+        if d is None or d.chunks.device != self.grad.device:
+            import types
+            t, dev = self.clip_tables(), self.grad.device
+            d = self._clip_dev = types.SimpleNamespace(
+                chunks=torch.from_numpy(t.chunks).to(dev), segs=torch.from_numpy(t.segs).to(dev),
+                partials=torch.zeros(max(1, t.chunks.shape[0]), dtype=torch.float32, device=dev),
+                norms=torch.zeros(max(1, len(t.names)), dtype=torch.float32, device=dev))
+        return d
+
+    def clip_groups(self, g0, g1, clip, grad_scale):
+        """Clip the parameters of the groups [g0, g1) of `clip_tables()` (0 video stack's matrices, 1 joint stack's, 2 the rest) on the
+        current stream: two launches."""
+        t, d = self.clip_tables(), self.clip_device()
+        chunks, segs = (t.chunk_bounds[g0], t.chunk_bounds[g1]), (t.seg_bounds[g0], t.seg_bounds[g1])
+        ops.clip_sumsq(self.grad, d.chunks, d.segs, chunks, segs, d.partials)
+        ops.clip_apply(self.grad, d.chunks, d.segs, chunks, segs, d.partials, clip, grad_scale, d.norms)
+
     def images_rewritten(self, transposes=True):
         """tan_adamw_step_images has just rewritten the shadow AND the images built from it."""
         self.shadow_version = self.flat._version

@@ -349,3 +349,36 @@ def window_feat_final(acc, cnt, out):
     _lib.check(_lib.lib().tan_window_feat_final(_f32(acc), _f32(cnt), cnt.numel(), _ptr(out), _dt(out), _stream()),
                "tan_window_feat_final")
     return out
+
+
+def clip_chunk():
+    """elements per chunk of the gradient-clipping tables (tan_clip_chunk)"""
+    return int(_lib.lib().tan_clip_chunk())
+
+
+def _clip_ranges(g, chunk_table, seg_table, chunks, segs, partials, norms=None):
+    """the chunk / segment ranges of one clipping launch against the sizes of its tables and buffers: the kernels index all of them"""
+    (c0, c1), (s0, s1) = chunks, segs
+    ok = (g.dtype == torch.float32 and g.dim() == 1 and g.is_contiguous() and g.numel() < 2 ** 31
+          and chunk_table.dtype == torch.int32 and chunk_table.dim() == 2 and chunk_table.shape[1] == 4 and chunk_table.is_contiguous()
+          and seg_table.dtype == torch.int32 and seg_table.dim() == 2 and seg_table.shape[1] == 2 and seg_table.is_contiguous()
+          and 0 <= c0 <= c1 <= chunk_table.shape[0] and 0 <= s0 <= s1 <= seg_table.shape[0]
+          and partials.is_contiguous() and partials.numel() >= c1 and (norms is None or (norms.is_contiguous() and norms.numel() >= s1)))
+    if not ok:
+        raise _lib.TanHipError(f"gradient clipping: chunks {chunks} / segments {segs} do not fit the tables or buffers")
+    return c0, c1, s0, s1
+
+
+def clip_sumsq(g, chunk_table, seg_table, chunks, segs, partials):
+    """partials[c] = sum of squares of chunk c of the flat f32 gradient g, for the chunks [c0, c1) (tan_clip_sumsq; tables: include/tan_hip.h)"""
+    c0, c1, s0, s1 = _clip_ranges(g, chunk_table, seg_table, chunks, segs, partials)
+    _lib.check(_lib.lib().tan_clip_sumsq(_f32(g), _ptr(chunk_table), _ptr(seg_table), c0, c1, s0, s1, g.numel(), _f32(partials), _stream()),
+               "tan_clip_sumsq")
+
+
+def clip_apply(g, chunk_table, seg_table, chunks, segs, partials, clip, grad_scale, norms):
+    """per segment of [s0, s1): norms[s] = ||g_s|| * grad_scale from the partials; g_s *= clip / (norm + 1e-6) where that is below 1
+    (tan_clip_apply: utils/train_utils.py:3-13)"""
+    c0, c1, s0, s1 = _clip_ranges(g, chunk_table, seg_table, chunks, segs, partials, norms)
+    _lib.check(_lib.lib().tan_clip_apply(_f32(g), _ptr(chunk_table), _ptr(seg_table), c0, c1, s0, s1, g.numel(), _f32(partials),
+                                         float(clip), float(grad_scale), _f32(norms), _stream()), "tan_clip_apply")

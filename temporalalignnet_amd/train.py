@@ -518,7 +518,15 @@ class Trainer:
         a = self.args
         self._lm_allreduce()
         if a.clip_grad > 0:                            # per-parameter L2 clip, utils/train_utils.py:3-13 (language model included)
-            for p in list(f.params) + [q for _, q in self._lm_params()]:
+            rest = [q for _, q in self._lm_params()]
+            if self._clip_fused():
+                # two launches over the flat gradient (csrc/tan_clip.hip) for the groups `early_update` has not clipped and stepped
+                # in this step: [video stack's matrices | joint stack's matrices | everything else]
+                g0 = 0 if not self._early else (2 if "joint" in self._early else 1)
+                f.clip_groups(g0, 3, a.clip_grad, grad_scale)
+            else:                                      # TAN_CLIP_FUSED=0: the torch rule for every tensor (~6 launches each)
+                rest = list(f.params) + rest
+            for p in rest:                             # (the language model's few tensors live outside the flat buffer)
                 if p.grad is not None:
                     coef = a.clip_grad / (p.grad.norm(2) * grad_scale + 1e-6)
                     p.grad.mul_(torch.clamp(coef, max=1.0))
@@ -544,6 +552,21 @@ class Trainer:
             ema.shadow_epoch += 1                       # (shadow_version is left alone: the flat buffers' version counters did
             #                                             not move, the kernel writes through raw pointers)
         self._lm_step(grad_scale)
+
+    def _clip_fused(self):
+        """`clip_grad` runs as two HIP launches per group over the flat gradient (TAN_CLIP_FUSED=0: the torch rule, tensor by tensor,
+        which also keeps the optimizer launches of a two-chain step at its end)."""
+        return self.args.clip_grad > 0 and os.environ.get("TAN_CLIP_FUSED", "1") != "0"
+
+    def last_grad_norms(self):
+        """{parameter name: 0-d device tensor} -- the L2 norm of every flat-buffer parameter's gradient as the last optimizer step's
+        clip saw it (what clip_gradients returns, utils/train_utils.py:8-9), without a host synchronisation: views of the buffer
+        tan_clip_apply wrote, valid until the next step.  None with clip_grad == 0 or before the first fused clip."""
+        f = self.online._ensure_flat()       # (the current stream waits for what a pipelined step left running on its role streams)
+        d = f.__dict__.get("_clip_dev")
+        if not self._clip_fused() or d is None:
+            return None
+        return {n: d.norms[i] for i, n in enumerate(f.clip_tables().names)}
 
     def _images_in_optimizer(self, f, ema):
         """The optimizer launch writes the weight images itself (tan_adamw_step_images) when the model computes from them: bf16
@@ -589,10 +612,12 @@ class Trainer:
         f, st = self._ensure_state()
         # (data parallel: a stack is stepped behind the all-reduce of its slice -- `_GradReducer.stack_done`; not in 'single' mode)
         ok = (self._images_in_optimizer(f, self.model.target._ensure_flat_nosync() if self.twin else None)
-              and not self.args.clip_grad > 0 and not self._accum_open
+              and (not self.args.clip_grad > 0 or self._clip_fused()) and not self._accum_open
               and (not dist.active() or (self._ddp is not None and self.ddp_mode in ("flat", "buckets"))))
         if ok:
             self._adamw_tables(f, st)        # (built here, by ONE thread: the two early launches are issued from two host threads)
+            if self.args.clip_grad > 0:
+                f.clip_device()              # (the clipping tables and buffers: the same)
             self._early = set()
         return ok
 
@@ -605,6 +630,14 @@ class Trainer:
         f, st = self._ensure_state()
         lo, hi = (0, f.video_units) if which == "video" else (f.video_units, f.mats_units)
         ema = self.model.target._ensure_flat_nosync() if self.twin else None       # (stage 2: the EMA twin's stack moves in the same launch)
+        if self.args.clip_grad > 0:
+            # The stack's matrices are clipped on the stream that steps them, in front of that launch.  Data parallel: the clip
+            # coefficient is a function of the gradient SUMMED over ranks -- `chain_step`'s `stack_done` calls this only behind
+            # `_GradReducer.stack_done(which)`, which has enqueued the all-reduce of the stack's slice (and the bf16 wire's cast back)
+            # on this same stream, so the sums of squares read the reduced gradient.  The two host threads use disjoint chunk and
+            # segment ranges of the shared partials / norms buffers (groups 0 and 1 of `_Flat.clip_tables`).
+            g = 0 if which == "video" else 1
+            f.clip_groups(g, g + 1, self.args.clip_grad, grad_scale)
         self._adamw_images(f, st, ema, grad_scale, units=(lo, hi), rest=False, step=self.iteration + 1)
         self._early.add(which)
 

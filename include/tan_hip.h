@@ -731,6 +731,28 @@ int tan_window_stitch_final(float* acc_j, const float* acc_d, const float* cnt, 
 long tan_rank_topk_ws_bytes(long Q, long N, int k);
 int tan_rank_topk(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* pair, int k, int splits,
                   int* higher, int* ties, float* top_score, int* top_row, void* ws, void* stream);
+/* ---- the e4m3 index: 516 bytes per second of video instead of 1 KiB (model/tan_model.py:152, "can be used for retrieval
+ * setting": the per-second index that tan_window_feat_* build, ranked by the sweep above) ----
+ * Row format.  codes: OCP e4m3fn (gfx950's; NOT MI300's fnuz), one byte per element, [n_rows, 512].  scale: one f32 per row, a
+ * power of two.  With amax = max|x| over the row and amax = m * 2^e, m in [0.5, 1) (frexp):
+ *     s = e - 9 if m <= 0.875, else s = e - 8;  s is clamped to [-126, 127];  scale = 2^s;  amax == 0: scale = 1.
+ * Hence |x / scale| <= 448 (e4m3fn's largest finite value): the conversion never saturates, and x * 2^-s is exact in f32.
+ *     code = RNE_e4m3(x * 2^-s): round to nearest, ties to even, subnormals kept (the smallest is 2^-9) -- the function
+ *     torch.Tensor.to(torch.float8_e4m3fn) computes on the host.
+ * Inputs are finite.  A non-finite element is outside the contract: a NaN becomes a NaN code and makes every score of its row
+ * NaN; an infinity sets the row's scale to 2^120, which flushes most of the row to zero, and its own code is unspecified.
+ * Nothing is read or written out of bounds either way.
+ * tan_quantize_rows_e4m3: x [n_rows, C] (TAN_F32 or TAN_BF16, 16-byte aligned), C == 512, 1 <= n_rows < 2^31 -> codes
+ * [n_rows, 512] bytes (8-byte aligned), scale [n_rows].  One wave per row, no atomics: run-to-run identical.
+ * tan_rank_topk_e4m3: tan_rank_topk over such rows -- Tq [Q, 512] / Vn [N, 512] codes (16-byte aligned), q_scale [Q] / v_scale
+ * [N] their scales.  score(q, n) = (acc * v_scale[n]) * q_scale[q], with acc the f32 accumulation of the code products by
+ * v_mfma_f32_32x32x16_fp8_fp8 and the two multiplies in f32, in that order, in the pair launch and in the sweep alike: the
+ * sweep's own entry (q, pair[q]) has the pair score's bits, ties[q] >= 1.  pair / k / splits / higher / ties / top_score / top_row
+ * / ws (tan_rank_topk_ws_bytes(Q, N, k)), determinism and argument rules: exactly as tan_rank_topk.                               */
+int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* codes, float* scale, void* stream);
+int tan_rank_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                       const int* pair, int k, int splits, int* higher, int* ties, float* top_score, int* top_row, void* ws,
+                       void* stream);
 /* Clip pooling of test_retrieval_yc2 (:197-214).  stage: one stage of the video stack's output, window w's frame f at
  * stage + w * win_stride + f * 512 elements of `dtype` (win_stride >= T * 512, a multiple of 8); table [W, 3] int32 = (clip,
  * first_frame, n_frames) per window.  normalize != 0: every selected frame is L2-normalised (sim = 'cos').  sum [n_clips, 512] /

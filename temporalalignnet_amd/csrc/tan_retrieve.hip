@@ -15,6 +15,10 @@
 //   3. merge  : one wave per query folds the splits' lists through the same sorting network.  The order is total (no two entries
 //               share a row), so the result is the top k of all N rows whatever the split count; integer counts are summed with
 //               integer atomics, whose result does not depend on order.  No float atomics anywhere.
+// tan_rank_topk_e4m3 is the same three launches over e4m3 codes with one power-of-two f32 scale per row (the format of
+// tan_quantize_rows_e4m3, include/tan_hip.h): a third instantiation of rank_kernel.  The 64 row scales of an index tile ride into
+// LDS with the tile's last K chunk, and every accumulator becomes (acc * v_scale[n]) * q_scale[q] -- in the pair launch and in
+// the sweep alike -- before anything compares it, so thresholds, candidate buffers, sort64 and the merge see final scores.
 //
 // tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
 // of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
@@ -36,8 +40,13 @@ constexpr int SENT_ROW = 0x7fffffff;
 template <typename T> struct RCfg;
 template <> struct RCfg<bf16_t> { static constexpr int KC = 128, LD = 136; };     // 256 B of a row per chunk; 272-B pitch: b128 reads conflict-free
 template <> struct RCfg<float> { static constexpr int KC = 64, LD = 65; };        // 256 B of a row per chunk; odd pitch: b32 reads conflict-free
+// 256 B of a row per chunk; 264-B pitch = 8 B x 33: the 32 rows a half-wave reads with one ds_read_b64 (all at the same k) start 66 dwords
+// apart, i.e. on the dword pairs 2 r mod 64, r = 0..31 -- each of the 64 banks once: b64 reads conflict-free.  The pitch is no multiple
+// of 16, so the tile is staged with 8-byte stores.
+template <> struct RCfg<e4m3_t> { static constexpr int KC = 256, LD = 264; };
 
-template <typename T> constexpr int tile_bytes() { return 2 * BN * RCfg<T>::LD * (int)sizeof(T); }
+template <typename T> constexpr int scale_bytes() { return sizeof(T) == 1 ? BN * 4 : 0; }   // e4m3: a tile's row scales, after the buffers
+template <typename T> constexpr int tile_bytes() { return 2 * BN * RCfg<T>::LD * (int)sizeof(T) + scale_bytes<T>(); }
 constexpr int BUF_BYTES = 4 * 32 * CAP * 8;
 template <typename T> constexpr int sweep_lds() { return (tile_bytes<T>() + 15) / 16 * 16 + BUF_BYTES; }
 
@@ -69,6 +78,12 @@ template <> struct QFrag<float> {
     static __device__ __forceinline__ float load(const float* row, int j, int lane) { return row[j * 2 + (lane >> 5)]; }
 };
 
+template <> struct QFrag<e4m3_t> {
+    static __device__ __forceinline__ long load(const e4m3_t* row, int j, int lane) {
+        return *reinterpret_cast<const long*>(row + j * 16 + 8 * (lane >> 5));
+    }
+};
+
 template <typename T>
 __device__ __forceinline__ void stage_store(T* tile, int tid, const uint4 (&pre)[4]) {
     constexpr int LD = RCfg<T>::LD;
@@ -77,6 +92,10 @@ __device__ __forceinline__ void stage_store(T* tile, int tid, const uint4 (&pre)
         const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
         if constexpr (sizeof(T) == 2) {
             *reinterpret_cast<uint4*>(tile + row * LD + c16 * 8) = pre[i];
+        } else if constexpr (sizeof(T) == 1) {
+            uint2* d = reinterpret_cast<uint2*>(tile + row * LD + c16 * 16);
+            d[0] = make_uint2(pre[i].x, pre[i].y);
+            d[1] = make_uint2(pre[i].z, pre[i].w);
         } else {
             float* d = reinterpret_cast<float*>(tile) + row * LD + c16 * 4;
             d[0] = __uint_as_float(pre[i].x); d[1] = __uint_as_float(pre[i].y);
@@ -87,18 +106,22 @@ __device__ __forceinline__ void stage_store(T* tile, int tid, const uint4 (&pre)
 
 // PAIR = true : launch 1 (grid = query tiles); tile t of 2 holds the paired rows of the block's queries 64 t .. 64 t + 63
 // PAIR = false: launch 2 (grid = query tiles x splits)
+// q_scale / v_scale: the rows' scales, e4m3 only (the other instantiations do not read them)
 template <typename T, bool PAIR>
 __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Q, long N,
                                                    const int* __restrict__ pair, int k, long tiles_per_split, long n_tiles,
                                                    float* __restrict__ dscore, int* __restrict__ higher, int* __restrict__ ties,
-                                                   float* __restrict__ part_s, int* __restrict__ part_n) {
+                                                   float* __restrict__ part_s, int* __restrict__ part_n,
+                                                   const float* __restrict__ q_scale, const float* __restrict__ v_scale) {
     typedef Mma<T> M;
     typedef typename M::frag_t frag_t;
     constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, KS = M::KS, NCH = RC / KC, SPC = KC / KS, NFR = RC / KS;
     constexpr int TS = BN * LD;                                    // elements per tile buffer
     constexpr long ROWB = (long)RC * sizeof(T);
+    constexpr bool F8 = sizeof(T) == 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T* tile = reinterpret_cast<T*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + 2 * TS * sizeof(T));   // F8: the current tile's 64 row scales
     float* bs = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16);
     int* bn = reinterpret_cast<int*>(bs + 4 * 32 * CAP);
 
@@ -113,6 +136,9 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
 #pragma unroll
         for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(qrow, j, lane);
     }
+
+    float qs = 1.0f, psc = 0.0f;
+    if constexpr (F8) qs = q_scale[qok ? qme : Q - 1];
 
     long t0, t1;
     if (PAIR) { t0 = 0; t1 = 2; }
@@ -140,6 +166,19 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
             pre[i] = n < N ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Vn) + n * ROWB + kc * 256 + c16 * 16)
                            : make_uint4(0, 0, 0, 0);
         }
+        if constexpr (F8) {
+            if (kc == NCH - 1 && tid < BN) {                       // the row scales ride with the tile's last chunk
+                long n;
+                if (PAIR) {
+                    const long q = qblk + t * BN + tid;
+                    n = q < Q ? (long)pair[q] : 0;
+                    n = n < 0 ? 0 : (n >= N ? N - 1 : n);
+                } else {
+                    n = t * BN + tid;
+                }
+                psc = n < N ? v_scale[n] : 0.0f;
+            }
+        }
     };
 
     if (t0 < t1) issue(t0, 0);
@@ -151,6 +190,11 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
         for (int kc = 0; kc < NCH; ++kc) {
             T* cur = tile + (kc & 1) * TS;                         // NCH is even: the buffer alternates across tiles too
             stage_store<T>(cur, tid, pre);
+            if constexpr (F8) {
+                // written before the last chunk's barrier, read after it; the next write comes after the next tile's first barrier,
+                // which no wave passes before every wave has left this tile's epilogue: one buffer is enough
+                if (kc == NCH - 1 && tid < BN) sc[tid] = psc;
+            }
             __syncthreads();
             if (kc + 1 < NCH) issue(t, kc + 1);
             else if (t + 1 < t1) issue(t + 1, 0);
@@ -161,6 +205,20 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
                 M::mma(acc[0], a0, qf[kc * SPC + ks]);
                 M::mma(acc[1], a1, qf[kc * SPC + ks]);
             }
+        }
+        if constexpr (F8) {
+            // a lane's 16 rows of a 32-row half are four runs of four: 8 g + 4 (lane >> 5) + 0..3.  Two f32 multiplies in this order
+            // (powers of two: exact), the same in the pair launch and the sweep.
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 s4 = *reinterpret_cast<const float4*>(sc + rt * 32 + 8 * g + 4 * (lane >> 5));
+                    acc[rt][4 * g + 0] = (acc[rt][4 * g + 0] * s4.x) * qs;
+                    acc[rt][4 * g + 1] = (acc[rt][4 * g + 1] * s4.y) * qs;
+                    acc[rt][4 * g + 2] = (acc[rt][4 * g + 2] * s4.z) * qs;
+                    acc[rt][4 * g + 3] = (acc[rt][4 * g + 3] * s4.w) * qs;
+                }
         }
         if (PAIR) {
             if (t == (wave >> 1)) {
@@ -391,11 +449,40 @@ __global__ void __launch_bounds__(256) window_feat_final_kernel(const float* __r
     }
 }
 
+// one wave per row: amax by shuffle-reduce, the power-of-two scale of include/tan_hip.h from amax's bits, v_cvt_pk_fp8_f32 (RNE, OCP
+// e4m3fn on gfx950), one 8-byte store per lane.  amax = m 2^e with m in [0.5, 1): e = (bits >> 23) - 126 and m <= 0.875 <=> the
+// fraction field <= 0x600000.  A subnormal amax would give s < -126 and takes the clamp.
+template <typename T>
+__global__ void __launch_bounds__(256) quantize_rows_kernel(const T* __restrict__ x, long n_rows, uint2* __restrict__ codes,
+                                                            float* __restrict__ scale) {
+    const long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= n_rows) return;
+    const f8 v = ld_row8<T>(x + g * RC + lane * 8);
+    float am = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) am = fmaxf(am, fabsf(v.v[i]));
+    am = wave_max(am);
+    const unsigned bits = __float_as_uint(am);
+    const int eb = (int)(bits >> 23);
+    int s = eb - 126 - ((bits & 0x7fffffu) <= 0x600000u ? 9 : 8);
+    s = (eb == 0 || s < -126) ? -126 : s;
+    s = am == 0.0f ? 0 : s;
+    const float inv = __uint_as_float((unsigned)(127 - s) << 23);      // 2^-s; s <= 121 for any bit pattern, so this is a normal number
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v.v[0] * inv, v.v[1] * inv, lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v.v[2] * inv, v.v[3] * inv, lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v.v[4] * inv, v.v[5] * inv, hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v.v[6] * inv, v.v[7] * inv, hi, true);
+    codes[g * (RC / 8) + lane] = make_uint2((unsigned)lo, (unsigned)hi);
+    if (lane == 0) scale[g] = __uint_as_float((unsigned)(s + 127) << 23);
+}
+
 inline long n_index_tiles(long N) { return (N + BN - 1) / BN; }
 
 template <typename T>
 int rank_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair, int k, int splits, int* higher, int* ties,
-                float* top_s, int* top_n, void* ws, hipStream_t st) {
+                float* top_s, int* top_n, void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
     const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
     long want = splits > 0 ? splits : (512 + q_tiles - 1) / q_tiles;
     want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
@@ -407,14 +494,14 @@ int rank_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair,
     int* part_n = (int*)(part_s + (long)ns * Q * k);
     if (pair) {
         hipLaunchKernelGGL((rank_kernel<T, true>), dim3((unsigned)q_tiles), dim3(256), tile_bytes<T>(), st, (const T*)Tq, (const T*)Vn, Q, N,
-                           pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr);
+                           pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr, q_scale, v_scale);
         TAN_LAUNCH_CHECK();
     }
     static std::atomic<unsigned long long> lds_done{0};
     const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false>, sweep_lds<T>(), lds_done);
     if (attr != hipSuccess) return (int)attr;
     hipLaunchKernelGGL((rank_kernel<T, false>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), sweep_lds<T>(), st, (const T*)Tq,
-                       (const T*)Vn, Q, N, pair, k, tps, n_tiles, dscore, higher, ties, part_s, part_n);
+                       (const T*)Vn, Q, N, pair, k, tps, n_tiles, dscore, higher, ties, part_s, part_n, q_scale, v_scale);
     TAN_LAUNCH_CHECK();
     if (k > 0) {
         hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, Q, k, ns, top_s, top_n);
@@ -445,6 +532,33 @@ extern "C" int tan_rank_topk(const void* Tq, const void* Vn, int dtype, long Q, 
     hipStream_t st = (hipStream_t)stream;
     return dtype == TAN_BF16 ? rank_launch<bf16_t>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, st)
                              : rank_launch<float>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, st);
+}
+
+extern "C" int tan_rank_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                                  const int* pair, int k, int splits, int* higher, int* ties, float* top_score, int* top_row, void* ws,
+                                  void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && ws);
+    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 0 && k <= KMAX && k <= N);
+    TAN_REQUIRE(splits >= 0 && (pair || k > 0));
+    TAN_REQUIRE(!pair || (higher && ties));
+    TAN_REQUIRE(k == 0 || (top_score && top_row));
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
+    return rank_launch<e4m3_t>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, (hipStream_t)stream, q_scale,
+                               v_scale);
+}
+
+extern "C" int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* codes, float* scale, void* stream) {
+    TAN_REQUIRE(x && codes && scale && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(C == RC && n_rows >= 1 && n_rows < (1L << 31) && (uintptr_t)x % 16 == 0 && (uintptr_t)codes % 8 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == TAN_BF16)
+        hipLaunchKernelGGL(quantize_rows_kernel<bf16_t>, dim3(cdiv(n_rows, 4)), dim3(256), 0, st, (const bf16_t*)x, n_rows, (uint2*)codes,
+                           scale);
+    else
+        hipLaunchKernelGGL(quantize_rows_kernel<float>, dim3(cdiv(n_rows, 4)), dim3(256), 0, st, (const float*)x, n_rows, (uint2*)codes,
+                           scale);
+    TAN_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int tan_segment_pool_acc(const void* stage, int dtype, long win_stride, int T, const int* table, int W, int normalize,

@@ -315,6 +315,47 @@ def rank_topk(tq, vn, pair=None, k=0, *, splits=0, check_pair=False, out=None, w
     return higher, ties, top_s, top_r
 
 
+def quantize_rows_e4m3(x, codes=None, scale=None):
+    """x [n, 512] (f32 / bf16, contiguous) -> (codes uint8 [n, 512]: OCP e4m3fn bit patterns, scale f32 [n]: a power of two per row),
+    the row format of include/tan_hip.h (tan_quantize_rows_e4m3).  codes / scale: caller-owned outputs instead of fresh ones."""
+    assert x.dim() == 2 and x.is_contiguous()
+    n, dev = x.shape[0], x.device
+    codes = torch.empty(n, x.shape[1], dtype=torch.uint8, device=dev) if codes is None else codes
+    scale = torch.empty(n, dtype=torch.float32, device=dev) if scale is None else scale
+    assert codes.dtype == torch.uint8 and codes.shape == x.shape and codes.is_contiguous() and scale.shape == (n,) and scale.is_contiguous()
+    _lib.check(_lib.lib().tan_quantize_rows_e4m3(_ptr(x), _dt(x), n, x.shape[1], _ptr(codes), _f32(scale), _stream()),
+               "tan_quantize_rows_e4m3")
+    return codes, scale
+
+
+def rank_topk_e4m3(tq, q_scale, vn, v_scale, pair=None, k=0, *, splits=0, check_pair=False, out=None, ws=None):
+    """`rank_topk` over e4m3 rows (tan_rank_topk_e4m3): tq [Q, 512] / vn [N, 512] uint8 codes with their f32 row scales q_scale [Q] /
+    v_scale [N], as `quantize_rows_e4m3` makes them; score = (acc * v_scale[n]) * q_scale[q].  Everything else as `rank_topk`."""
+    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype == torch.uint8
+    Q, N, dev = tq.shape[0], vn.shape[0], tq.device
+    assert q_scale.shape == (Q,) and v_scale.shape == (N,) and q_scale.is_contiguous() and v_scale.is_contiguous()
+    if pair is not None:
+        assert pair.dtype == torch.int32 and pair.shape == (Q,) and pair.is_contiguous()
+        if check_pair and Q and (int(pair.min()) < 0 or int(pair.max()) >= N):
+            raise ValueError("rank_topk_e4m3: pair outside [0, N)")
+    if out is None:
+        higher = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
+        ties = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
+        top_s = torch.empty(Q, k, dtype=torch.float32, device=dev) if k > 0 else None
+        top_r = torch.empty(Q, k, dtype=torch.int32, device=dev) if k > 0 else None
+    else:
+        higher, ties, top_s, top_r = out
+    L = _lib.lib()
+    need = L.tan_rank_topk_ws_bytes(Q, N, k)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    _lib.check(L.tan_rank_topk_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(pair), k, splits,
+                                    _ptr(higher), _ptr(ties), _ptr(top_s), _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk_e4m3")
+    return higher, ties, top_s, top_r
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

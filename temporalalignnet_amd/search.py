@@ -11,6 +11,9 @@ sentence is ranked against all of it:
     dual similarity of eval_zeroshot_align.py:198,201 -- computed without knowing the sentence.
   * `search`: sentences -> `get_textual_feature`, normalised -> `tan_rank_topk` against the index (no [Q, N] score matrix) -> rows
     mapped to (vid, second) on the host.
+  * an e4m3 index (`build_index(dtype="e4m3")`, `VideoIndex.quantize`, `--index-dtype e4m3`) keeps a row as 512 OCP e4m3fn codes
+    and one power-of-two f32 scale (include/tan_hip.h): 516 bytes per second of video instead of 1 KiB.  The query is quantised by
+    the same kernel and `tan_rank_topk_e4m3` sweeps the codes.
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -27,6 +30,11 @@ from . import ops
 from .infer_align import PASSES_PER_CHUNK, WIN_FIELDS, _aligner, _prefetch, load_packed
 
 TEMPERATURE = 0.07
+E4M3 = "e4m3"
+
+
+def _is_e4m3(dtype):
+    return dtype == E4M3 or dtype == torch.float8_e4m3fn
 
 
 def plan_index_windows(vlen, seq_len=64):
@@ -74,10 +82,23 @@ def _index_chunks(videos, seq_len, windows_per_pass):
 
 
 class VideoIndex:
-    """feat [sum vlen, 512] (device, bf16 or f32): one row per second; v_off [n_videos + 1]: each video's first row; vids."""
+    """feat [sum vlen, 512] (device, bf16 or f32): one row per second; v_off [n_videos + 1]: each video's first row; vids.
+    An e4m3 index holds feat as uint8 codes and scale [sum vlen] f32, one power of two per row; scale is None otherwise."""
 
-    def __init__(self, feat, v_off, vids):
-        self.feat, self.v_off, self.vids = feat, np.asarray(v_off, dtype=np.int64), list(vids)
+    def __init__(self, feat, v_off, vids, scale=None):
+        self.feat, self.v_off, self.vids, self.scale = feat, np.asarray(v_off, dtype=np.int64), list(vids), scale
+        assert (scale is not None) == (feat.dtype == torch.uint8)
+
+    @property
+    def e4m3(self):
+        return self.scale is not None
+
+    def quantize(self):
+        """The e4m3 index of this bf16 / f32 one (tan_quantize_rows_e4m3); an e4m3 index is returned as it is."""
+        if self.e4m3:
+            return self
+        codes, scale = ops.quantize_rows_e4m3(self.feat.contiguous())
+        return VideoIndex(codes, self.v_off, self.vids, scale)
 
     def __len__(self):
         return int(self.feat.shape[0])
@@ -89,29 +110,34 @@ class VideoIndex:
         return v, rows - self.v_off[v]
 
     def save(self, path):
-        """One .npz of plain arrays (bf16 rows as their uint16 bit patterns)."""
+        """One .npz of plain arrays (bf16 rows as their uint16 bit patterns; e4m3 rows as uint8 codes plus `scale`)."""
         f = self.feat.cpu()
         bf16 = f.dtype == torch.bfloat16
+        more = dict(scale=self.scale.cpu().numpy()) if self.e4m3 else {}
         with open(path, "wb") as fh:
             np.savez(fh, feat=(f.view(torch.int16).numpy().view(np.uint16) if bf16 else f.numpy()), bf16=np.array(bf16),
-                     v_off=self.v_off, vids=np.array(self.vids, dtype=np.str_))
+                     e4m3=np.array(self.e4m3), v_off=self.v_off, vids=np.array(self.vids, dtype=np.str_), **more)
 
     @classmethod
     def load(cls, path, device="cuda"):
         with np.load(path, allow_pickle=False) as z:
             f = torch.from_numpy(z["feat"].view(np.int16)).view(torch.bfloat16) if bool(z["bf16"]) else torch.from_numpy(z["feat"])
-            return cls(f.to(device).contiguous(), z["v_off"], [str(v) for v in z["vids"]])
+            e4m3 = "e4m3" in z.files and bool(z["e4m3"])                  # files written before the e4m3 format have no such key
+            scale = torch.from_numpy(z["scale"]).to(device).contiguous() if e4m3 else None
+            return cls(f.to(device).contiguous(), z["v_off"], [str(v) for v in z["vids"]], scale)
 
 
 @torch.no_grad()
 def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfloat16):
     """`videos`: iterable of {'vid', 'video' [vlen, Dv] (array / tensor) or a callable that reads it (then 'vlen' is required)} --
     `infer_align.read_corpus` items work as they are.  Every second of every video gets one row (see the module docstring); the rows
-    do not depend on how the windows are cut into passes."""
+    do not depend on how the windows are cut into passes.  dtype: torch.bfloat16, torch.float32, or "e4m3" (torch.float8_e4m3fn):
+    each chunk's rows are finished in f32 and quantised at once; only codes and scales are kept."""
+    e4m3 = _is_e4m3(dtype)
     net = _aligner(model)
     device = torch.device("cuda", torch.cuda.current_device())
     T = seq_len
-    feats, vlens, vids = [], [], []
+    feats, scales, vlens, vids = [], [], [], []
     no_text = torch.zeros(1, 8, device=device)
     for ch in _prefetch(_index_chunks(videos, seq_len, windows_per_pass), device):
         n_rows = int(ch.v_off[-1])
@@ -126,22 +152,29 @@ def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfl
             ops.window_pack(ch.video, no_text, tab, T, 1, vid, vm, txt, tm)
             v = net.get_visual_feature(vid, vm)                                     # [W, S, T, 512]
             ops.window_feat_acc(v[:, -1], tab, acc, cnt)
-        feats.append(ops.window_feat_final(acc, cnt, torch.empty(n_rows, 512, dtype=dtype, device=device)))
+        if e4m3:
+            codes, scale = ops.quantize_rows_e4m3(ops.window_feat_final(acc, cnt, torch.empty(n_rows, 512, device=device)))
+            feats.append(codes)
+            scales.append(scale)
+        else:
+            feats.append(ops.window_feat_final(acc, cnt, torch.empty(n_rows, 512, dtype=dtype, device=device)))
         vlens += [it["vlen"] for it in ch.items]
         vids += [it.get("vid") for it in ch.items]
     if not feats:
         raise ValueError("build_index: no videos")
-    return VideoIndex(torch.cat(feats, 0), np.concatenate([[0], np.cumsum(vlens)]), vids)
+    return VideoIndex(torch.cat(feats, 0), np.concatenate([[0], np.cumsum(vlens)]), vids, torch.cat(scales, 0) if e4m3 else None)
 
 
 @torch.no_grad()
 def query_features(index, model, embed_text, queries, text_batch=1024):
-    """Unit text features [Q, 512] in the index's dtype."""
+    """Unit text features [Q, 512] in the index's dtype; for an e4m3 index (codes uint8 [Q, 512], scale f32 [Q])."""
     net = _aligner(model)
     dev = index.feat.device
     t = torch.cat([net.get_textual_feature(embed_text(list(queries[a:a + text_batch])).to(dev)).float().reshape(-1, 512)
                    for a in range(0, len(queries), text_batch)], 0).contiguous()
     t = ops.l2norm_fwd(t, torch.empty_like(t), None, t.shape[0], 512)
+    if index.e4m3:
+        return ops.quantize_rows_e4m3(t)
     return t if index.feat.dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.feat.dtype, device=dev))
 
 
@@ -156,7 +189,10 @@ def search(index, model, embed_text, queries, k=10, splits=0):
     if not 1 <= k <= 32:
         raise ValueError("search: k must lie in [1, 32]")
     tq = query_features(index, model, embed_text, queries)
-    _, _, score, row = ops.rank_topk(tq, index.feat, None, k, splits=splits)
+    if index.e4m3:
+        _, _, score, row = ops.rank_topk_e4m3(*tq, index.feat, index.scale, None, k, splits=splits)
+    else:
+        _, _, score, row = ops.rank_topk(tq, index.feat, None, k, splits=splits)
     score, row = score.cpu().numpy(), row.cpu().numpy()
     v, sec = index.locate(row)
     return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
@@ -176,6 +212,8 @@ def main(argv=None):
     p.add_argument("--asr-json", required=True)
     p.add_argument("--vlen-csv", required=True)
     p.add_argument("--out", required=True, help="index file (.npz)")
+    p.add_argument("--index-dtype", choices=("bf16", "fp32", "e4m3"), default=None,
+                   help="row format of the index (default: --dtype); e4m3: 516 bytes per second instead of 1 KiB")
     p.add_argument("--worker-id", type=int, default=0)
     p.add_argument("--num-workers", type=int, default=1)
     p = sub.choices["query"]
@@ -190,7 +228,7 @@ def main(argv=None):
         if not 0 <= a.worker_id < a.num_workers:
             ap.error("--worker-id must lie in [0, --num-workers)")
         corpus = read_corpus(a.feature_dir, a.asr_json, a.vlen_csv, a.worker_id, a.num_workers)
-        idx = build_index(model, corpus, dtype=torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+        idx = build_index(model, corpus, dtype={"bf16": torch.bfloat16, "fp32": torch.float32, "e4m3": E4M3}[a.index_dtype or a.dtype])
         idx.save(a.out)
         print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos", file=sys.stderr)
         return 0

@@ -32,7 +32,7 @@ extern "C" {
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
 int tan_version(void);
-/* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc) for which = 0..4 (binding self-check) */
+/* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
 /* Optional in-stream kernel timer (bench.py's `roofline` line): while enabled every tan_gemm / tan_attn_* launch is
@@ -204,74 +204,68 @@ int tan_agreement(const unsigned char* joint_tgt, const unsigned char* dual_tgt,
 int tan_masked_quantile(const float* x, const unsigned char* invalid, int n, float q, float* out, void* stream);
 
 /* ---- logits-free similarity + NCE (bf16 features) ---------------------------------------------------------------
- * Fused replacement of einsum (tan_model.py:118,138) + NCE terms (loss.py:240-253): vn [S,R,C], tn [S or 1,Mp,C] unit
- * features (t_stage_stride = Mp*C, or 0 when the text features are shared by all stages), other arguments as tan_nce_fwd.
- * One workgroup sweeps a 128-row panel of one stage over all text columns; logits only ever exist as MFMA accumulators.
- * tan_simnce_bwd_dl recomputes them and writes d loss/d logits [S,R,Mp] in bf16 for the two follow-up tan_gemm calls.
- * ws: tan_simnce_ws_floats() f32 scratch.  Requires C % 64 == 0, B*N <= 2048.
- * Column compaction (optional, colmap != NULL): padded text columns take part in nothing (loss.py:64-70 drops them before
- * the log-sum-exps), so the sweep may run on a COMPACTED text matrix: then `tn` holds Mc <= B*N rows per stage (a multiple of 64 keeps
- * the follow-up GEMMs on the direct-to-LDS kernel; filler rows flagged in col_invalid), col_invalid / colsum / possum_t / t_terms / g_t have Mc entries
- * per stage, dl is [S,R,Mc]; `tn_blocks` (stage stride tb_stage_stride) is the UNcompacted [B*N,C] matrix, read only for the
- * same-video blocks, and colmap[b*N+k] is that sentence's compacted column or -1.
+ * Fused replacement of einsum (tan_model.py:118,138) + NCE terms (loss.py:240-253) and of their autograd: one workgroup sweeps a
+ * 128-row panel of one stage over all text columns; logits only ever exist as MFMA accumulators.  Both calls take one descriptor;
+ * tgt / col_invalid / row_leak and the four saved sums mean what they mean for tan_nce_fwd.  Requires C % 64 == 0 and at most
+ * tan_simnce_max_cols() sweep columns.
+ *   tan_simnce_fwd  row / column / positive sums and v_terms [S,R], t_terms [S,Mp].  e_keep != NULL (tan_simnce_keeps(C) != 0: the
+ *                   LDS-resident sweep, C = 512) also stores e = exp((cos - 1)/tau) of every (frame, sentence) pair as bf16,
+ *                   tan_simnce_keep_elems() elements: S * ceil(R/128) * ceil(Mp/128) tiles of 128 x 128 in accumulator order.
+ *   tan_simnce_bwd  g_v [S,R], g_t [S,Mp] -> dl = d loss/d logits [S,R,Mp] bf16 for the follow-up tan_gemm calls.  e_keep NULL: a
+ *                   second sweep recomputes the logits; e_keep != NULL: one element-wise pass over the kept exponentials (2 x
+ *                   S*R*Mp*2 bytes of HBM traffic instead of 2*S*R*Mp*C FLOP).  d_vn != NULL (needs e_keep, TAN_SIM_SWEEP, C = 512,
+ *                   16-byte alignment, sweep columns % 8 == 0 and < 32768, N <= 32): that pass also returns d_vn [S,R,C] bf16 =
+ *                   dl . t_hat, the gradient of the unit video features (autograd of tan_model.py:116-119,136-139's einsum towards
+ *                   its first operand) -- the 128 x 128 d-logits tiles are the MFMA operand while they are in the LDS, so the
+ *                   [S*R, Mp] x [Mp, C] GEMM and its read of dl go away.  dl is still written for the text-feature gradient (NULL:
+ *                   not written); the sweep's text image inside `ws` is overwritten and (unless TAN_SIM_CORR_KEEP) the dense
+ *                   same-video correction array is built there.
+ * Column compaction (colmap != NULL; NULL: Mc is ignored): padded text columns take part in nothing (loss.py:64-70 drops them before
+ * the log-sum-exps), so the sweep may run on a COMPACTED text matrix: `tn` then holds Mc <= B*N rows per stage (a multiple of 64 keeps
+ * the follow-up GEMMs on the direct-to-LDS kernel; filler rows flagged in col_invalid), col_invalid / colsum / possum_t / t_terms / g_t
+ * have Mc entries per stage, dl is [S,R,Mc]; `tn_blocks` is the UNcompacted [B*N,C] matrix, read only for the same-video blocks, and
+ * colmap[b*N+k] is that sentence's compacted column or -1.
  * `phases` (0 = everything) selects the steps, for sweeps over SEVERAL column blocks (global negatives across ranks, row f3):
  *   TAN_SIM_SWEEP  the tile sweep (fwd: row sums += valid columns, column sums of this block -> colsum; bwd: d logits)
  *   TAN_SIM_ACC_ROWS  with SWEEP: keep accumulating into rowsum instead of zeroing it first
  *   TAN_SIM_DIAG   same-video blocks: positives + padded-frame quirk (only the block that holds the rows' own sentences)
  *   TAN_SIM_TERMS  (fwd) v_terms / t_terms from the final sums
  *   TAN_SIM_DIAG_KEEP  (bwd, with DIAG) `ws` still holds the same-video blocks tan_simnce_fwd computed for these features: do
- *                  not recompute them                                                                                      */
+ *                  not recompute them
+ *   TAN_SIM_CORR_KEEP  (bwd, d_vn != NULL) `ws` already holds the correction array of these upstream gradients                  */
 #define TAN_SIM_SWEEP 1
 #define TAN_SIM_DIAG 2
 #define TAN_SIM_TERMS 4
 #define TAN_SIM_ACC_ROWS 8
 #define TAN_SIM_DIAG_KEEP 16
-#define TAN_SIM_CORR_KEEP 32 /* (tan_simnce_bwd_dl_dvn_kept) `ws` already holds the correction array of these upstream gradients */
+#define TAN_SIM_CORR_KEEP 32
+typedef struct tan_simnce_desc {
+    int S, B, T, N, C, Mc, phases;
+    const void* vn;                                    /* [S,R,C] unit video features, R = B*T */
+    const void* tn; long t_stage_stride;               /* [S or 1,Mp,C] unit text features; Mp*C, or 0: shared by all stages */
+    const void* tn_blocks; long tb_stage_stride;       /* with colmap: the uncompacted text features and their stage stride */
+    const int* colmap;                                 /* [B*N] or NULL */
+    const float* tgt; const unsigned char* col_invalid; const unsigned char* row_leak;   /* [B,T,N] | [Mp] | [R] or NULL */
+    float *rowsum, *colsum, *possum_v, *possum_t;      /* [S,R], [S,Mp], [S,R], [S,Mp]: written by fwd, read by bwd */
+    float *v_terms, *t_terms;                          /* fwd out */
+    const float *g_v, *g_t; void* dl; void* d_vn;      /* bwd: in, in, out, optional out */
+    void* e_keep;                                      /* optional: kept exponentials, written by fwd, read by bwd */
+    float* ws;                                         /* tan_simnce_ws_floats() f32 scratch */
+} tan_simnce_desc;
 long tan_simnce_ws_floats(int S, int B, int T, int N);
 int tan_simnce_max_cols(void);   /* most text columns (B*N, or Mc when compacted) one sweep accepts: callers fall back to tan_nce_* above it */
-int tan_simnce_fwd(const void* vn, const void* tn, long t_stage_stride, const float* tgt, const unsigned char* col_invalid,
-                   const unsigned char* row_leak, float* rowsum, float* colsum, float* possum_v, float* possum_t,
-                   float* v_terms, float* t_terms, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks,
-                   long tb_stage_stride, const int* colmap, int Mc, int phases, void* stream);
-int tan_simnce_bwd_dl(const void* vn, const void* tn, long t_stage_stride, const float* tgt, const unsigned char* col_invalid,
-                      const unsigned char* row_leak, const float* rowsum, const float* colsum, const float* possum_v,
-                      const float* possum_t, const float* g_v, const float* g_t, void* dl, float* ws, int S, int B, int T, int N,
-                      int C, const void* tn_blocks, long tb_stage_stride, const int* colmap, int Mc, int phases, void* stream);
-
-/* The same pair with the exponentials KEPT: tan_simnce_fwd_keep also stores e = exp((cos - 1)/tau) of every (frame, sentence) pair of
- * the sweep as bf16, S * ceil(R/128) * ceil(Mp/128) tiles of 128 x 128 in the sweep's accumulator order (Mp = Mc when compacted:
- * tan_simnce_keep_elems() elements); tan_simnce_bwd_dl_kept turns them into d loss/d logits with one element-wise
- * pass (2 x S*R*Mp*2 bytes of HBM traffic) instead of a second 2*S*R*Mp*C-FLOP sweep.  tan_simnce_keeps(C) != 0 says whether the
- * pair is available for C channels (the LDS-resident sweep: C = 512); all other arguments as above.                          */
-int tan_simnce_keeps(int C);
+int tan_simnce_keeps(int C);     /* != 0: tan_simnce_fwd can keep its exponentials for C channels */
 long tan_simnce_keep_elems(int S, int R, int Mp);
-int tan_simnce_fwd_keep(const void* vn, const void* tn, long t_stage_stride, const float* tgt, const unsigned char* col_invalid,
-                        const unsigned char* row_leak, float* rowsum, float* colsum, float* possum_v, float* possum_t,
-                        float* v_terms, float* t_terms, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks,
-                        long tb_stage_stride, const int* colmap, int Mc, int phases, void* e_keep, void* stream);
-int tan_simnce_bwd_dl_kept(const void* e_keep, const void* vn, const void* tn, long t_stage_stride, const float* tgt,
-                           const unsigned char* col_invalid, const unsigned char* row_leak, const float* rowsum, const float* colsum,
-                           const float* possum_v, const float* possum_t, const float* g_v, const float* g_t, void* dl, float* ws,
-                           int S, int B, int T, int N, int C, const void* tn_blocks, long tb_stage_stride, const int* colmap, int Mc,
-                           int phases, void* stream);
-/* tan_simnce_bwd_dl_kept that also returns d_vn [S, R, C] (bf16) = dl . t_hat, the gradient of the unit video features
- * (the autograd of tan_model.py:116-119,136-139's einsum towards its first operand): the 128 x 128 d-logits tiles are the MFMA operand
- * while they are in the LDS, so the [S*R, Mp] x [Mp, C] GEMM behind the element-wise pass and its read of the d-logits go away.  dl is
- * still written (the text-feature gradient contracts it over the rows; dl = NULL: not written).  C = 512 (tan_simnce_keeps), sweep
- * columns % 8 == 0 and < 32768, N <= 32; overwrites the sweep's text image inside `ws` and (unless phases has TAN_SIM_CORR_KEEP)
- * builds the dense same-video correction array there.                                                                                                          */
-int tan_simnce_bwd_dl_dvn_kept(const void* e_keep, const void* vn, const void* tn, long t_stage_stride, const float* tgt,
-                               const unsigned char* col_invalid, const unsigned char* row_leak, const float* rowsum, const float* colsum,
-                               const float* possum_v, const float* possum_t, const float* g_v, const float* g_t, void* dl, void* d_vn,
-                               float* ws, int S, int B, int T, int N, int C, const void* tn_blocks, long tb_stage_stride,
-                               const int* colmap, int Mc, int phases, void* stream);
+int tan_simnce_fwd(const tan_simnce_desc* d, void* stream);
+int tan_simnce_bwd(const tan_simnce_desc* d, void* stream);
+
 /* ---- one feature FAMILY (dual or joint) of the logits-free NCE, from the stacks' stage outputs to their gradients --------------
  * Everything between an encoder stack's forward and its backward in the training step, for one family of tan_model.py:116-119
  * (dual: video stack stages x the one text embedding) or :136-139 (joint: video rows x text rows of the joint stack's stages), with
  * loss.py:240-253 and its autograd:
  *   tan_simfam_fwd  L2-normalise the stage rows (video: one launch, or inside the sweep's panel load with TAN_SIMFAM_NORM_IN_SWEEP;
  *                   text: normalise + column compaction + both fragment-major text images in ONE launch), the statistics sweep keeping
- *                   its exponentials (tan_simnce_fwd_keep's kernel), and ONE finishing launch: same-video cosine blocks, column sums
+ *                   its exponentials (tan_simnce_fwd's kernel, e_keep set), and ONE finishing launch: same-video cosine blocks, column sums
  *                   over the row panels, positives / leaked frames, v_terms / t_terms -- and, when g_v / g_t are already known (the
  *                   two-chain step: they depend on the batch's masks only), the same-video corrections of the backward.
  *   tan_simfam_bwd  d logits + d v_hat in one pass over the kept exponentials whose epilogue applies the L2-normalisation's backward
@@ -321,6 +315,8 @@ typedef struct tan_simfam_desc {
     int dtn_split_k;   /* K slices of the text-gradient GEMM; 0: default (St = 1: 8 slices of tan_gemm; St = S: 2 of tan_gemm_atb), < 0: -n slices of tan_gemm_atb */
 } tan_simfam_desc;
 long tan_simfam_ws_bytes(int S, int St, int B, int T, int N, int Mc);
+/* != 0: the shape limits above hold (stages, N, Mc, the finishing launch's LDS bound): what both calls check of the dims before a launch */
+int tan_simfam_accepts(int S, int St, int B, int T, int N, int Mc);
 int tan_simfam_fwd(tan_simfam_desc* d, void* stream);
 /* byte offset inside `ws` of stage s's same-video cosine blocks [B, T, N] f32 written by the finishing launch (every stage; entries of
  * padded sentences are their cosines without compaction and undefined with it: a dropped sentence has no sweep column) */

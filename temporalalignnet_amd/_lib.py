@@ -153,6 +153,20 @@ class SimFamDesc(C.Structure):
     ]
 
 
+class SimNceDesc(C.Structure):
+    """tan_simnce_desc (include/tan_hip.h): the logits-free similarity + NCE sweeps; a field left unset is NULL / 0"""
+    _fields_ = [
+        ("S", C.c_int), ("B", C.c_int), ("T", C.c_int), ("N", C.c_int), ("C", C.c_int), ("Mc", C.c_int), ("phases", C.c_int),
+        ("vn", C.c_void_p), ("tn", C.c_void_p), ("t_stage_stride", C.c_long),
+        ("tn_blocks", C.c_void_p), ("tb_stage_stride", C.c_long), ("colmap", C.c_void_p),
+        ("tgt", C.c_void_p), ("col_invalid", C.c_void_p), ("row_leak", C.c_void_p),
+        ("rowsum", C.c_void_p), ("colsum", C.c_void_p), ("possum_v", C.c_void_p), ("possum_t", C.c_void_p),
+        ("v_terms", C.c_void_p), ("t_terms", C.c_void_p),
+        ("g_v", C.c_void_p), ("g_t", C.c_void_p), ("dl", C.c_void_p), ("d_vn", C.c_void_p),
+        ("e_keep", C.c_void_p), ("ws", C.c_void_p),
+    ]
+
+
 class MlpDesc(C.Structure):
     _fields_ = [
         ("rows", C.c_long), ("C", C.c_int), ("FF", C.c_int),

@@ -63,6 +63,7 @@ extern "C" int tan_abi_sizeof(int which) {
         case 2: return (int)sizeof(tan_layer_bufs);
         case 3: return (int)sizeof(tan_encoder_desc);
         case 4: return (int)sizeof(tan_simfam_desc);
+        case 5: return (int)sizeof(tan_simnce_desc);
         default: return TAN_ERR_BAD_ARG;
     }
 }

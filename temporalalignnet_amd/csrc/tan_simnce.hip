@@ -1108,33 +1108,26 @@ extern "C" int tan_simnce_max_cols(void) {
     return res_enabled(a) ? S_MAXCOLS_RES : S_MAXCOLS;       // (C = 512, what the aligner runs; other channel counts: 2048)
 }
 
-static long simnce_corr_floats(int S, int B, int T, int N) { return (long)S * B * T * N + 128 * 32 + 8; }
+// Where everything lives in `ws`: the column partials (two per row panel, sized for the padded column count), the same-video blocks
+// [S, B, T, N], the fragment-major text image of the resident sweep (bf16, per stage, columns rounded up to 128; 16-byte aligned --
+// the one-pass backward puts its transposed image TpT where the sweep's Tp was), and the same-video corrections of the one-pass
+// backward ([S, R, N] f32, simnce_corr_kernel; slack for its 1-KiB LDS-DMA pieces; 16-byte aligned)
+struct SimWs { float* colpart; float* diag; char* img; float* corr; long floats; };
+static SimWs simnce_ws(float* ws, int S, int B, int T, int N) {
+    auto up16 = [](float* p) { return ((uintptr_t)p + 15) & ~(uintptr_t)15; };
+    const long R = (long)B * T, Mp = (long)B * N;
+    const long o_diag = 2 * (long)cdiv(R, 128) * S * Mp, o_img = o_diag + (long)S * R * N;
+    const long o_corr = o_img + (long)S * cdiv(Mp, 128) * 128 * 512 / 2 + 4;
+    return {ws, ws + o_diag, (char*)up16(ws + o_img), (float*)up16(ws + o_corr), o_corr + (long)S * R * N + 128 * 32 + 8};
+}
 
-extern "C" long tan_simnce_ws_floats(int S, int B, int T, int N) {
-    const long R = (long)B * T, Mp = (long)B * N;
-    // column partials (two per row panel) + same-video blocks + the fragment-major text image of the resident sweep (bf16, per stage,
-    // columns rounded up to 128)
-    // ... + the same-video corrections of the one-pass backward kernels ([S, R, N] f32, simnce_corr_kernel; slack for its 1-KiB LDS-DMA pieces)
-    return 2 * (long)cdiv(R, 128) * S * Mp + (long)S * B * T * N + (long)S * cdiv(Mp, 128) * 128 * 512 / 2 + 4 + simnce_corr_floats(S, B, T, N);
-}
-// where the corrections live in `ws` (behind the text image; 16-byte aligned)
-static float* simnce_corr_ptr(float* ws, int S, int B, int T, int N) {
-    const long R = (long)B * T, Mp = (long)B * N;
-    float* p = ws + 2 * (long)cdiv(R, 128) * S * Mp + (long)S * B * T * N + (long)S * cdiv(Mp, 128) * 128 * 512 / 2 + 4;
-    return (float*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-}
+extern "C" long tan_simnce_ws_floats(int S, int B, int T, int N) { return simnce_ws(nullptr, S, B, T, N).floats; }
+
 static int simnce_corr_launch(const SimArgs& a, const float* diag, float* corr, hipStream_t st) {
     hipLaunchKernelGGL(simnce_corr_kernel, dim3(a.B, a.S), dim3(256), 0, st, diag, a.tgt, a.col_invalid, a.row_leak, (const float*)a.possum_v,
                        a.possum_t, a.g_v, a.g_t, corr, a.B, a.T, a.N, a.colmap, a.Mp);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
-}
-
-static int simnce_common(SimArgs& a, int S, int B, int T, int N, int C) {
-    a.S = S; a.B = B; a.T = T; a.N = N; a.C = C; a.R = B * T; a.Mp = B * N;
-    if (S <= 0 || B <= 0 || T <= 0 || N <= 0 || C <= 0 || C % 64 != 0) return TAN_ERR_BAD_ARG;
-    if (((uintptr_t)a.V % 16) || ((uintptr_t)a.Tt % 16)) return TAN_ERR_BAD_ARG;
-    return 0;
 }
 
 // same-video cosine blocks diag[s,b,t,n] = <vn[s,b*T+t], tn[s,b*N+n]>, C = 512: one WAVE per 32 frame rows of a (video, stage),
@@ -1196,14 +1189,8 @@ static int simnce_diag_blocks(const SimArgs& a, const bf16_t* tn_blocks, long tb
     return 0;
 }
 
-static int simnce_cus() {
-    static const int n = [] { int dev = 0, v = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256; return v; }();
-    return n;
-}
-
-// the resident sweep's text image lives behind the same-video blocks in `ws` (tan_simnce_ws_floats); a.Mp = columns of the sweep
-static int simnce_pack_text(SimArgs& a, float* ws_after_diag, hipStream_t st, float* zero = nullptr, long nzero = 0) {
-    char* base = (char*)(((uintptr_t)ws_after_diag + 15) & ~(uintptr_t)15);
+// the resident sweep's text image (SimWs::img); a.Mp = columns of the sweep
+static int simnce_pack_text(SimArgs& a, char* base, hipStream_t st, float* zero = nullptr, long nzero = 0) {
     const int nblk = cdiv(a.Mp, 128) * 4;
     const bool shared = a.t_stage_stride == 0;
     a.Tp = base;
@@ -1213,74 +1200,7 @@ static int simnce_pack_text(SimArgs& a, float* ws_after_diag, hipStream_t st, fl
     return e == hipSuccess ? 0 : (int)e;
 }
 
-// v_terms / t_terms of loss.py:240-253 straight from unit features (no logits); sums are kept for tan_simnce_bwd_dl.
-static int simnce_fwd_impl(const void* vn, const void* tn, long t_stage_stride, const float* tgt, const unsigned char* col_invalid,
-                           const unsigned char* row_leak, float* rowsum, float* colsum, float* possum_v, float* possum_t,
-                           float* v_terms, float* t_terms, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks,
-                           long tb_stage_stride, const int* colmap, int Mc, int phases, void* ekeep, void* stream) {
-    TAN_REQUIRE(vn && tn && tgt && col_invalid && rowsum && colsum && possum_v && possum_t && v_terms && t_terms && ws);
-    TAN_REQUIRE(!colmap || (tn_blocks && Mc > 0 && Mc <= B * N));
-    if (phases == 0) phases = TAN_SIM_SWEEP | TAN_SIM_DIAG | TAN_SIM_TERMS;
-    SimArgs a{};
-    a.V = (const bf16_t*)vn; a.Tt = (const bf16_t*)tn; a.t_stage_stride = t_stage_stride;
-    a.tgt = tgt; a.col_invalid = col_invalid; a.row_leak = row_leak;
-    a.rowsum = rowsum; a.possum_v = possum_v;
-    int rc = simnce_common(a, S, B, T, N, C);
-    if (rc) return rc;
-    const int npanel = cdiv(a.R, 128);
-    a.colpart = ws;
-    float* diag = ws + 2 * (long)npanel * S * a.Mp;      // sized for the padded column count
-    if (colmap) a.Mp = Mc;
-    else { tn_blocks = tn; tb_stage_stride = t_stage_stride; }
-    if (a.Mp > (res_enabled(a) ? S_MAXCOLS_RES : S_MAXCOLS)) return TAN_ERR_BAD_ARG;        // columns of the sweep (compacted or not)
-    hipStream_t st = (hipStream_t)stream;
-    const long SM = (long)S * a.Mp, SR = (long)S * a.R;
-    if (phases & TAN_SIM_SWEEP) {
-        const bool res = res_enabled(a);
-        const bool zero_rows = !(phases & TAN_SIM_ACC_ROWS);
-        if (zero_rows && !res) {
-            hipError_t e = hipMemsetAsync(rowsum, 0, sizeof(float) * (size_t)S * a.R, st);
-            if (e != hipSuccess) return (int)e;
-        }
-        const int prec = prof_begin(st, TAN_PROF_SIMNCE, 2.0 * S * a.R * (double)a.Mp * C);
-        if (ekeep && !res) return TAN_ERR_BAD_ARG;          // tan_simnce_keeps() said no
-        a.ekeep = (bf16_t*)ekeep;
-        if (res && (rc = simnce_pack_text(a, diag + (long)S * B * T * N, st, zero_rows ? rowsum : nullptr, (long)S * a.R))) return rc;
-        if (res) {
-            const int items = npanel * S, ncu = simnce_cus(), rem = items % ncu;
-            a.npanel = npanel;
-            // (cutting the items of the last partial round in two column halves -- a.nfull = items - rem, the kernel supports it -- was
-            // measured: 130 vs 125 us per sweep, no gain: off)
-            a.nfull = items; (void)ncu; (void)rem;
-            hipLaunchKernelGGL((simnce_res_kernel<0>), dim3(a.nfull + 2 * (items - a.nfull)), dim3(512), 0, st, a);
-        }
-        else hipLaunchKernelGGL((simnce_kernel<0>), dim3(npanel, S), dim3(256), 0, st, a);
-        prof_end(st, prec);
-        TAN_LAUNCH_CHECK();
-        hipLaunchKernelGGL(simnce_col_finalize, dim3(cdiv(SM, 64)), dim3(64), 0, st, a.colpart, colsum, res ? 2 * npanel : npanel, SM);
-    }
-    if (phases & TAN_SIM_DIAG) {
-        if ((rc = simnce_diag_blocks(a, (const bf16_t*)tn_blocks, tb_stage_stride, diag, st))) return rc;
-        hipLaunchKernelGGL((simnce_diag_kernel<false>), dim3(B, S), dim3(256), sizeof(float) * 2 * (size_t)(T + N), st, diag, tgt, col_invalid, row_leak, rowsum, colsum,
-                           possum_v, possum_t, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, B, T, N, colmap, a.Mp);
-    }
-    if (phases & TAN_SIM_TERMS) {
-        hipLaunchKernelGGL(simnce_terms2, dim3(cdiv(SR + SM, 256)), dim3(256), 0, st, rowsum, possum_v, v_terms, SR, a.col_invalid, a.Mp, colsum,
-                           possum_t, t_terms, SM, logf((float)a.R));
-    }
-    TAN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int tan_simnce_fwd(const void* vn, const void* tn, long t_stage_stride, const float* tgt, const unsigned char* col_invalid,
-                              const unsigned char* row_leak, float* rowsum, float* colsum, float* possum_v, float* possum_t,
-                              float* v_terms, float* t_terms, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks,
-                              long tb_stage_stride, const int* colmap, int Mc, int phases, void* stream) {
-    return simnce_fwd_impl(vn, tn, t_stage_stride, tgt, col_invalid, row_leak, rowsum, colsum, possum_v, possum_t, v_terms, t_terms, ws,
-                           S, B, T, N, C, tn_blocks, tb_stage_stride, colmap, Mc, phases, nullptr, stream);
-}
-
-// 1 when tan_simnce_fwd_keep / tan_simnce_bwd_dl_kept are available for this channel count
+// 1 when tan_simnce_fwd can keep its exponentials for this channel count
 extern "C" int tan_simnce_keeps(int C) {
     SimArgs a{}; a.C = C;
     return res_enabled(a) ? 1 : 0;
@@ -1288,122 +1208,142 @@ extern "C" int tan_simnce_keeps(int C) {
 
 extern "C" long tan_simnce_keep_elems(int S, int R, int Mp) { return (long)S * cdiv(R, 128) * cdiv(Mp, 128) * 16384; }
 
-extern "C" int tan_simnce_fwd_keep(const void* vn, const void* tn, long t_stage_stride, const float* tgt, const unsigned char* col_invalid,
-                                   const unsigned char* row_leak, float* rowsum, float* colsum, float* possum_v, float* possum_t,
-                                   float* v_terms, float* t_terms, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks,
-                                   long tb_stage_stride, const int* colmap, int Mc, int phases, void* e_keep, void* stream) {
-    TAN_REQUIRE(e_keep);
-    return simnce_fwd_impl(vn, tn, t_stage_stride, tgt, col_invalid, row_leak, rowsum, colsum, possum_v, possum_t, v_terms, t_terms, ws,
-                           S, B, T, N, C, tn_blocks, tb_stage_stride, colmap, Mc, phases, e_keep, stream);
+// What tan_simnce_fwd and tan_simnce_bwd share: the checks of the descriptor, the kernels' arguments, where things are in `ws`, and
+// which text matrix holds the same-video blocks' sentences (the uncompacted one under column compaction, else `tn` itself)
+struct SimCall { SimArgs a; SimWs w; const bf16_t* tn_blocks; long tb_stage_stride; int phases; };
+static int simnce_call(const tan_simnce_desc* d, int all_phases, SimCall& c) {
+    TAN_REQUIRE(d && d->vn && d->tn && d->tgt && d->col_invalid && d->rowsum && d->colsum && d->possum_v && d->possum_t && d->ws);
+    TAN_REQUIRE(d->S > 0 && d->B > 0 && d->T > 0 && d->N > 0 && d->C > 0 && d->C % 64 == 0);
+    TAN_REQUIRE((uintptr_t)d->vn % 16 == 0 && (uintptr_t)d->tn % 16 == 0);
+    TAN_REQUIRE(!d->colmap || (d->tn_blocks && d->Mc > 0 && d->Mc <= d->B * d->N));
+    SimArgs& a = c.a;
+    a.V = (const bf16_t*)d->vn; a.Tt = (const bf16_t*)d->tn; a.t_stage_stride = d->t_stage_stride;
+    a.tgt = d->tgt; a.col_invalid = d->col_invalid; a.row_leak = d->row_leak;
+    a.rowsum = d->rowsum; a.possum_v = d->possum_v;
+    a.S = d->S; a.B = d->B; a.T = d->T; a.N = d->N; a.C = d->C; a.R = d->B * d->T;
+    a.Mp = d->colmap ? d->Mc : d->B * d->N;                 // columns of the sweep (compacted or not)
+    TAN_REQUIRE(a.Mp <= (res_enabled(a) ? S_MAXCOLS_RES : S_MAXCOLS));
+    c.w = simnce_ws(d->ws, d->S, d->B, d->T, d->N);
+    c.tn_blocks = (const bf16_t*)(d->colmap ? d->tn_blocks : d->tn);
+    c.tb_stage_stride = d->colmap ? d->tb_stage_stride : d->t_stage_stride;
+    c.phases = d->phases ? d->phases : all_phases;
+    return 0;
 }
 
-// d loss / d logits [S, R, Mp] in bf16 from upstream g_v [S,R], g_t [S,Mp] (recomputes every logit tile); ws as in fwd
-static int simnce_bwd_impl(const void* vn, const void* tn, long t_stage_stride, const float* tgt,
-                           const unsigned char* col_invalid, const unsigned char* row_leak, const float* rowsum,
-                           const float* colsum, const float* possum_v, const float* possum_t, const float* g_v, const float* g_t,
-                           void* dl, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks, long tb_stage_stride,
-                           const int* colmap, int Mc, int phases, const void* ekeep, void* dvn, void* stream) {
-    TAN_REQUIRE(vn && tn && tgt && col_invalid && rowsum && colsum && possum_v && possum_t && g_v && g_t && (dl || dvn) && ws);
-    TAN_REQUIRE(!colmap || (tn_blocks && Mc > 0 && Mc <= B * N));
-    if (phases == 0) phases = TAN_SIM_SWEEP | TAN_SIM_DIAG;
-    TAN_REQUIRE(!dvn || (ekeep && (phases & TAN_SIM_SWEEP) && (uintptr_t)dvn % 16 == 0));
-    SimArgs a{};
-    a.V = (const bf16_t*)vn; a.Tt = (const bf16_t*)tn; a.t_stage_stride = t_stage_stride;
-    a.tgt = tgt; a.col_invalid = col_invalid; a.row_leak = row_leak;
-    a.rowsum = (float*)rowsum; a.possum_v = (float*)possum_v; a.colsum = colsum; a.possum_t = possum_t;
-    a.g_v = g_v; a.g_t = g_t; a.dl = (bf16_t*)dl;
-    int rc = simnce_common(a, S, B, T, N, C);
+// v_terms / t_terms of loss.py:240-253 straight from unit features (no logits); sums are kept for tan_simnce_bwd.
+extern "C" int tan_simnce_fwd(const tan_simnce_desc* d, void* stream) {
+    SimCall c{};
+    int rc = simnce_call(d, TAN_SIM_SWEEP | TAN_SIM_DIAG | TAN_SIM_TERMS, c);
     if (rc) return rc;
+    TAN_REQUIRE(d->v_terms && d->t_terms);
+    SimArgs& a = c.a;
+    const bool res = res_enabled(a);
+    TAN_REQUIRE(!(d->e_keep && (c.phases & TAN_SIM_SWEEP)) || res);          // tan_simnce_keeps() said no
+    const int S = a.S, B = a.B, T = a.T, N = a.N, npanel = cdiv(a.R, 128);
+    a.colpart = c.w.colpart;
     hipStream_t st = (hipStream_t)stream;
-    float* diag = ws + 2 * (long)cdiv(a.R, 128) * S * a.Mp;
-    if (colmap) a.Mp = Mc;
-    else { tn_blocks = tn; tb_stage_stride = t_stage_stride; }
-    if (a.Mp > (res_enabled(a) ? S_MAXCOLS_RES : S_MAXCOLS)) return TAN_ERR_BAD_ARG;        // columns of the sweep (compacted or not)
-    if (ekeep && (phases & TAN_SIM_SWEEP)) {        // the statistics sweep kept its exponentials: one element-wise pass, corrections as its tail
-        const bool tail = (phases & TAN_SIM_DIAG) != 0;
-        if (tail && !(phases & TAN_SIM_DIAG_KEEP) && (rc = simnce_diag_blocks(a, (const bf16_t*)tn_blocks, tb_stage_stride, diag, st))) return rc;
-        a.ekeep = (bf16_t*)ekeep; a.diag = tail ? diag : nullptr; a.colmap = colmap;
-        if (dvn && tail) {          // the corrections as a dense array (once per backward: TAN_SIM_CORR_KEEP = the other one-pass call made it)
-            float* corr = simnce_corr_ptr(ws, S, B, T, N);
-            if (!(phases & TAN_SIM_CORR_KEEP) && (rc = simnce_corr_launch(a, diag, corr, st))) return rc;
-            a.corr = corr;
+    const long SM = (long)S * a.Mp, SR = (long)S * a.R;
+    if (c.phases & TAN_SIM_SWEEP) {
+        const bool zero_rows = !(c.phases & TAN_SIM_ACC_ROWS);
+        if (zero_rows && !res) {
+            hipError_t e = hipMemsetAsync(d->rowsum, 0, sizeof(float) * (size_t)S * a.R, st);
+            if (e != hipSuccess) return (int)e;
         }
-        if (dvn && (a.Mp % 8 || N > DV_MAX_N || a.Mp > 32767)) return TAN_ERR_BAD_ARG;          // (16-byte row pieces of dl; corrections in the LDS)
-        if (dvn) {          // d logits + d v_hat in one pass; the transposed text image takes the place of the sweep's (not read again)
-            const int npanel = cdiv(a.R, 128), nct = cdiv(a.Mp, 128);
-            char* TpT = (char*)(((uintptr_t)(diag + (long)S * B * T * N) + 15) & ~(uintptr_t)15);
-            const bool shared = a.t_stage_stride == 0;
-            const long tpt_stride = shared ? 0 : (long)nct * 128 * 1024;
-            hipLaunchKernelGGL(simnce_pack_textT_kernel, dim3(nct * 4, shared ? 1 : S), dim3(256), 0, st, a.Tt, a.t_stage_stride, TpT, tpt_stride, a.Mp);
-            TAN_LAUNCH_CHECK();
-            static std::atomic<unsigned long long> lds_done{0};
-        const hipError_t attr = ensure_dyn_lds((const void*)simnce_dl_dvn_kernel, DV_LDS_B, lds_done);
-            if (attr != hipSuccess) return (int)attr;
-            const int prec = prof_begin(st, TAN_PROF_GEMM_BF16 + 1, 2.0 * S * a.R * (double)a.Mp * C);
-            hipLaunchKernelGGL(simnce_dl_dvn_kernel, dim3(npanel * S), dim3(512), DV_LDS_B, st, a, npanel, nct, (const char*)TpT, tpt_stride, (bf16_t*)dvn, FamL2{});
-            prof_end(st, prec);
+        const int prec = prof_begin(st, TAN_PROF_SIMNCE, 2.0 * S * a.R * (double)a.Mp * a.C);
+        a.ekeep = (bf16_t*)d->e_keep;
+        if (res && (rc = simnce_pack_text(a, c.w.img, st, zero_rows ? d->rowsum : nullptr, SR))) return rc;
+        if (res) {
+            // (cutting the items of the last partial round in two column halves -- a.nfull = items minus items % CUs, the kernel supports
+            // it -- was measured: 130 vs 125 us per sweep, no gain: off)
+            a.npanel = npanel; a.nfull = npanel * S;
+            hipLaunchKernelGGL((simnce_res_kernel<0>), dim3(a.nfull), dim3(512), 0, st, a);
+        }
+        else hipLaunchKernelGGL((simnce_kernel<0>), dim3(npanel, S), dim3(256), 0, st, a);
+        prof_end(st, prec);
+        TAN_LAUNCH_CHECK();
+        hipLaunchKernelGGL(simnce_col_finalize, dim3(cdiv(SM, 64)), dim3(64), 0, st, a.colpart, d->colsum, res ? 2 * npanel : npanel, SM);
+    }
+    if (c.phases & TAN_SIM_DIAG) {
+        if ((rc = simnce_diag_blocks(a, c.tn_blocks, c.tb_stage_stride, c.w.diag, st))) return rc;
+        hipLaunchKernelGGL((simnce_diag_kernel<false>), dim3(B, S), dim3(256), sizeof(float) * 2 * (size_t)(T + N), st, c.w.diag, d->tgt, d->col_invalid,
+                           d->row_leak, d->rowsum, d->colsum, d->possum_v, d->possum_t, (const float*)nullptr, (const float*)nullptr,
+                           (bf16_t*)nullptr, B, T, N, d->colmap, a.Mp);
+    }
+    if (c.phases & TAN_SIM_TERMS) {
+        hipLaunchKernelGGL(simnce_terms2, dim3(cdiv(SR + SM, 256)), dim3(256), 0, st, d->rowsum, d->possum_v, d->v_terms, SR, a.col_invalid, a.Mp,
+                           d->colsum, d->possum_t, d->t_terms, SM, logf((float)a.R));
+    }
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// d loss / d logits [S, R, Mp] in bf16 from upstream g_v [S,R], g_t [S,Mp]; ws as in fwd.  e_keep NULL: recomputes every logit tile;
+// e_keep: one element-wise pass; d_vn as well: that pass ALSO returns d v_hat [S, R, C] = dl . t_hat (simnce_dl_dvn_kernel).
+extern "C" int tan_simnce_bwd(const tan_simnce_desc* d, void* stream) {
+    SimCall c{};
+    int rc = simnce_call(d, TAN_SIM_SWEEP | TAN_SIM_DIAG, c);
+    if (rc) return rc;
+    TAN_REQUIRE(d->g_v && d->g_t && (d->dl || d->d_vn));
+    TAN_REQUIRE(!d->d_vn || (d->e_keep && d->C == 512 && (c.phases & TAN_SIM_SWEEP) && (uintptr_t)d->d_vn % 16 == 0));
+    SimArgs& a = c.a;
+    int phases = c.phases;
+    float* const diag = c.w.diag;
+    const int S = a.S, B = a.B, T = a.T, N = a.N, npanel = cdiv(a.R, 128);
+    a.colsum = d->colsum; a.possum_t = d->possum_t; a.g_v = d->g_v; a.g_t = d->g_t; a.dl = (bf16_t*)d->dl;
+    hipStream_t st = (hipStream_t)stream;
+    if (d->e_keep && (phases & TAN_SIM_SWEEP)) {        // the statistics sweep kept its exponentials: one element-wise pass, corrections as its tail
+        const bool tail = (phases & TAN_SIM_DIAG) != 0;
+        // (16-byte row pieces of dl; corrections in the LDS)
+        TAN_REQUIRE(!d->d_vn || (a.Mp % 8 == 0 && N <= DV_MAX_N && a.Mp <= 32767));
+        if (tail && !(phases & TAN_SIM_DIAG_KEEP) && (rc = simnce_diag_blocks(a, c.tn_blocks, c.tb_stage_stride, diag, st))) return rc;
+        a.ekeep = (bf16_t*)d->e_keep; a.diag = tail ? diag : nullptr; a.colmap = d->colmap;
+        const int nct = cdiv(a.Mp, 128);
+        if (!d->d_vn) {
+            hipLaunchKernelGGL(simnce_dl_kept_kernel, dim3(npanel * nct, S), dim3(256), 0, st, a, npanel, nct);
             TAN_LAUNCH_CHECK();
             return 0;
         }
-        hipLaunchKernelGGL(simnce_dl_kept_kernel, dim3(cdiv(a.R, 128) * cdiv(a.Mp, 128), S), dim3(256), 0, st, a, cdiv(a.R, 128), cdiv(a.Mp, 128));
+        if (tail) {          // the corrections as a dense array (once per backward: TAN_SIM_CORR_KEEP = the other one-pass call made it)
+            if (!(phases & TAN_SIM_CORR_KEEP) && (rc = simnce_corr_launch(a, diag, c.w.corr, st))) return rc;
+            a.corr = c.w.corr;
+        }
+        // d logits + d v_hat in one pass; the transposed text image takes the place of the sweep's (not read again)
+        const bool shared = a.t_stage_stride == 0;
+        const long tpt_stride = shared ? 0 : (long)nct * 128 * 1024;
+        hipLaunchKernelGGL(simnce_pack_textT_kernel, dim3(nct * 4, shared ? 1 : S), dim3(256), 0, st, a.Tt, a.t_stage_stride, c.w.img, tpt_stride, a.Mp);
+        TAN_LAUNCH_CHECK();
+        static std::atomic<unsigned long long> lds_done{0};
+        const hipError_t attr = ensure_dyn_lds((const void*)simnce_dl_dvn_kernel, DV_LDS_B, lds_done);
+        if (attr != hipSuccess) return (int)attr;
+        const int prec = prof_begin(st, TAN_PROF_GEMM_BF16 + 1, 2.0 * S * a.R * (double)a.Mp * a.C);
+        hipLaunchKernelGGL(simnce_dl_dvn_kernel, dim3(npanel * S), dim3(512), DV_LDS_B, st, a, npanel, nct, (const char*)c.w.img, tpt_stride,
+                           (bf16_t*)d->d_vn, FamL2{});
+        prof_end(st, prec);
         TAN_LAUNCH_CHECK();
         return 0;
     }
     if (phases & TAN_SIM_SWEEP) {
         const bool res = res_enabled(a);
         const bool tail = res && (phases & TAN_SIM_DIAG);      // corrections as the sweep kernel's tail
-        if (tail && !(phases & TAN_SIM_DIAG_KEEP) && (rc = simnce_diag_blocks(a, (const bf16_t*)tn_blocks, tb_stage_stride, diag, st))) return rc;
-        const int prec = prof_begin(st, TAN_PROF_SIMNCE, 2.0 * S * a.R * (double)a.Mp * C);
+        if (tail && !(phases & TAN_SIM_DIAG_KEEP) && (rc = simnce_diag_blocks(a, c.tn_blocks, c.tb_stage_stride, diag, st))) return rc;
+        const int prec = prof_begin(st, TAN_PROF_SIMNCE, 2.0 * S * a.R * (double)a.Mp * a.C);
         if (res) {
-            a.diag = tail ? diag : nullptr; a.colmap = colmap;
-            if ((rc = simnce_pack_text(a, diag + (long)S * B * T * N, st))) return rc;
-            a.npanel = cdiv(a.R, 128); a.nfull = a.npanel * S;
+            a.diag = tail ? diag : nullptr; a.colmap = d->colmap;
+            if ((rc = simnce_pack_text(a, c.w.img, st))) return rc;
+            a.npanel = npanel; a.nfull = npanel * S;
             hipLaunchKernelGGL((simnce_res_kernel<1>), dim3(a.nfull), dim3(512), 0, st, a);
             if (tail) phases &= ~TAN_SIM_DIAG;
-        } else hipLaunchKernelGGL((simnce_kernel<1>), dim3(cdiv(a.R, 128), S), dim3(256), 0, st, a);
+        } else hipLaunchKernelGGL((simnce_kernel<1>), dim3(npanel, S), dim3(256), 0, st, a);
         prof_end(st, prec);
         TAN_LAUNCH_CHECK();
     }
     if (phases & TAN_SIM_DIAG) {
-        if (!(phases & TAN_SIM_DIAG_KEEP) && (rc = simnce_diag_blocks(a, (const bf16_t*)tn_blocks, tb_stage_stride, diag, st))) return rc;
-        hipLaunchKernelGGL((simnce_diag_kernel<true>), dim3(B, S), dim3(256), 0, st, diag, tgt, col_invalid, row_leak, (float*)rowsum,
-                           (float*)colsum, (float*)possum_v, (float*)possum_t, g_v, g_t, (bf16_t*)dl, B, T, N, colmap, a.Mp);
+        if (!(phases & TAN_SIM_DIAG_KEEP) && (rc = simnce_diag_blocks(a, c.tn_blocks, c.tb_stage_stride, diag, st))) return rc;
+        hipLaunchKernelGGL((simnce_diag_kernel<true>), dim3(B, S), dim3(256), 0, st, diag, d->tgt, d->col_invalid, d->row_leak, d->rowsum,
+                           d->colsum, d->possum_v, d->possum_t, d->g_v, d->g_t, (bf16_t*)d->dl, B, T, N, d->colmap, a.Mp);
     }
     TAN_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int tan_simnce_bwd_dl(const void* vn, const void* tn, long t_stage_stride, const float* tgt,
-                                 const unsigned char* col_invalid, const unsigned char* row_leak, const float* rowsum,
-                                 const float* colsum, const float* possum_v, const float* possum_t, const float* g_v, const float* g_t,
-                                 void* dl, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks, long tb_stage_stride,
-                                 const int* colmap, int Mc, int phases, void* stream) {
-    return simnce_bwd_impl(vn, tn, t_stage_stride, tgt, col_invalid, row_leak, rowsum, colsum, possum_v, possum_t, g_v, g_t, dl, ws,
-                           S, B, T, N, C, tn_blocks, tb_stage_stride, colmap, Mc, phases, nullptr, nullptr, stream);
-}
-
-extern "C" int tan_simnce_bwd_dl_kept(const void* e_keep, const void* vn, const void* tn, long t_stage_stride, const float* tgt,
-                                      const unsigned char* col_invalid, const unsigned char* row_leak, const float* rowsum,
-                                      const float* colsum, const float* possum_v, const float* possum_t, const float* g_v,
-                                      const float* g_t, void* dl, float* ws, int S, int B, int T, int N, int C, const void* tn_blocks,
-                                      long tb_stage_stride, const int* colmap, int Mc, int phases, void* stream) {
-    TAN_REQUIRE(e_keep);
-    return simnce_bwd_impl(vn, tn, t_stage_stride, tgt, col_invalid, row_leak, rowsum, colsum, possum_v, possum_t, g_v, g_t, dl, ws,
-                           S, B, T, N, C, tn_blocks, tb_stage_stride, colmap, Mc, phases, e_keep, nullptr, stream);
-}
-
-// tan_simnce_bwd_dl_kept that ALSO returns d v_hat [S, R, C] = dl . t_hat (bf16; C = 512): the d-logits tile feeds the MFMAs while it
-// is in the LDS (simnce_dl_dvn_kernel), so the [S*R, Mp] x [Mp, C] GEMM and its read of the d-logits are gone.  dl is still written
-// (row-major [S, R, Mp]) for the text-feature gradient.  Overwrites the sweep's text image in `ws` (tan_simnce_ws_floats).
-extern "C" int tan_simnce_bwd_dl_dvn_kept(const void* e_keep, const void* vn, const void* tn, long t_stage_stride, const float* tgt,
-                                          const unsigned char* col_invalid, const unsigned char* row_leak, const float* rowsum,
-                                          const float* colsum, const float* possum_v, const float* possum_t, const float* g_v,
-                                          const float* g_t, void* dl, void* d_vn, float* ws, int S, int B, int T, int N, int C,
-                                          const void* tn_blocks, long tb_stage_stride, const int* colmap, int Mc, int phases, void* stream) {
-    TAN_REQUIRE(e_keep && d_vn && C == 512);
-    if (phases == 0) phases = TAN_SIM_SWEEP | TAN_SIM_DIAG;
-    return simnce_bwd_impl(vn, tn, t_stage_stride, tgt, col_invalid, row_leak, rowsum, colsum, possum_v, possum_t, g_v, g_t, dl, ws,
-                           S, B, T, N, C, tn_blocks, tb_stage_stride, colmap, Mc, phases, e_keep, d_vn, stream);
 }
 
 // =================================================================================================================================
@@ -1697,16 +1637,12 @@ static FamWs simfam_ws(void* ws, int S, int St, int B, int T, int N, int Mc) {
 }
 
 // dynamic LDS of simfam_finish_kernel: the [T, N] cosine block twice + its row / column arrays
-// (restated by `simfam_ok` of temporalalignnet_amd/loss.py, which keeps such shapes away from here: change the two together)
 static size_t simfam_fin_lds(int T, int N) {
     return sizeof(float) * (2 * (size_t)T * N + T + 256 + 96) + 4 * 32 + 32 + (size_t)T + 16;
 }
 
 static int simfam_check(const tan_simfam_desc* d) {
-    TAN_REQUIRE(d && d->S >= 1 && d->S <= 8 && (d->St == 1 || d->St == d->S) && d->B > 0 && d->T > 0 && d->N > 0 && d->N <= DV_MAX_N);
-    TAN_REQUIRE(d->C == 512 && d->Mc > 0 && d->Mc % 8 == 0 && d->Mc <= S_MAXCOLS_RES && d->Mc <= 32767);
-    // (here and not in front of the finishing launch: a block that launch cannot hold must be refused before the sweep has run)
-    TAN_REQUIRE(simfam_fin_lds(d->T, d->N) <= 160 * 1024);
+    TAN_REQUIRE(d && d->C == 512 && tan_simfam_accepts(d->S, d->St, d->B, d->T, d->N, d->Mc));
     TAN_REQUIRE((d->idx != nullptr) == (d->colmap != nullptr));
     TAN_REQUIRE(d->idx || d->Mc == d->B * d->N);
     TAN_REQUIRE(d->col_invalid && d->tgt && d->vn && d->inv_v && d->tn && d->inv_t && d->rowsum && d->colsum && d->possum_v && d->possum_t);
@@ -1727,6 +1663,14 @@ static void simfam_args(const tan_simfam_desc* d, const FamWs& w, SimArgs& a) {
 }
 
 }  // namespace tal
+
+// the shape half of simfam_check; callers ask it before they choose this path
+extern "C" int tan_simfam_accepts(int S, int St, int B, int T, int N, int Mc) {
+    return S >= 1 && S <= 8 && (St == 1 || St == S) && B > 0 && T > 0 && N > 0 && N <= DV_MAX_N
+        && Mc > 0 && Mc % 8 == 0 && Mc <= S_MAXCOLS_RES && Mc <= 32767
+        // (here and not in front of the finishing launch: a block that launch cannot hold must be refused before the sweep has run)
+        && simfam_fin_lds(T, N) <= 160 * 1024;
+}
 
 extern "C" long tan_simfam_ws_bytes(int S, int St, int B, int T, int N, int Mc) {
     return simfam_ws(nullptr, S, St, B, T, N, Mc).bytes;

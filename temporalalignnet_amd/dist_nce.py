@@ -11,7 +11,7 @@ Scheme ("W blocks per rank"): every rank keeps its own video rows and sweeps the
               all-reduce  column-sum table [W,S,B*N] f32           (tiny)
               tan_simnce_fwd(TERMS)                                v_terms for local rows, t_terms for local sentences
     backward  all-gather  g_t                                      (tiny)
-              for q in ranks:  tan_simnce_bwd_dl(SWEEP [| DIAG])   d logits of block q, bf16
+              for q in ranks:  tan_simnce_bwd(SWEEP [| DIAG])      d logits of block q, bf16
                                d_vn += dl_q tn_q ;  d_tn_part[q] = dl_q^T vn
               reduce-scatter d_tn_part                             (text side again)
 The per-rank cost is W similarity sweeps instead of one: that is what global negatives are.  Loss normalisation is global:
@@ -36,10 +36,6 @@ from . import _lib, ops
 SWEEP, DIAG, TERMS, ACC_ROWS = 1, 2, 4, 8          # TAN_SIM_* of include/tan_hip.h
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class BlockNCE:
     """One rank, one logits family.  vn [S,R,C] bf16 unit video features (local rows), tgt [B,T,N] f32 positives of the local
     videos, row_leak u8 [R] or None.  Text blocks are passed per call: tn_q [1|S, Mp, C] bf16, pad flags u8 [Mp]."""
@@ -52,22 +48,28 @@ class BlockNCE:
         dev = vn.device
         L = _lib.lib()
         self.ws = torch.empty(L.tan_simnce_ws_floats(C.c_int(self.S), C.c_int(B), C.c_int(T), C.c_int(N)), device=dev)
-        self.rowsum = torch.empty(self.S, self.R, device=dev)
-        self.possum_v = torch.empty(self.S, self.R, device=dev)
+        self.rowsum, self.possum_v = torch.empty(self.S, self.R, device=dev), torch.empty(self.S, self.R, device=dev)
         self.possum_t = torch.empty(self.S, self.Mp, device=dev)
         self._dummy_v, self._dummy_t = torch.empty(self.S, self.R, device=dev), torch.empty(self.S, self.Mp, device=dev)
+        d = self.d = _lib.SimNceDesc()           # what stays the same from block to block; `_block` sets the rest
+        d.S, d.B, d.T, d.N, d.C = self.S, B, T, N, self.C
+        d.vn, d.t_stage_stride = vn.data_ptr(), self._stride()
+        d.tgt, d.row_leak = tgt.data_ptr(), row_leak.data_ptr() if row_leak is not None else None
+        d.rowsum, d.possum_v, d.possum_t, d.ws = self.rowsum.data_ptr(), self.possum_v.data_ptr(), self.possum_t.data_ptr(), self.ws.data_ptr()
 
     def _stride(self):
         return 0 if self.shared else self.Mp * self.C
 
+    def _block(self, tn, ci, colsum, phases, keep=None):
+        d = self.d
+        d.tn, d.col_invalid, d.colsum, d.phases = tn.data_ptr(), ci.data_ptr(), colsum.data_ptr(), phases
+        d.e_keep = keep.data_ptr() if keep is not None else None      # the sweep also stores its exponentials (bf16): the backward is an element-wise pass
+        return d
+
     def _fwd(self, tn, ci, colsum, v_terms, t_terms, phases, keep=None):
-        args = (_p(self.vn), _p(tn), C.c_long(self._stride()), _p(self.tgt), _p(ci), _p(self.row_leak), _p(self.rowsum), _p(colsum),
-                _p(self.possum_v), _p(self.possum_t), _p(v_terms), _p(t_terms), _p(self.ws), C.c_int(self.S), C.c_int(self.B),
-                C.c_int(self.T), C.c_int(self.N), C.c_int(self.C), None, C.c_long(0), None, C.c_int(0), C.c_int(phases))
-        if keep is not None:      # the sweep also stores its exponentials (bf16): the backward is an element-wise pass
-            _lib.check(_lib.lib().tan_simnce_fwd_keep(*args, _p(keep), ops._stream()), "tan_simnce_fwd_keep")
-        else:
-            _lib.check(_lib.lib().tan_simnce_fwd(*args, ops._stream()), "tan_simnce_fwd")
+        d = self._block(tn, ci, colsum, phases, keep)
+        d.v_terms, d.t_terms = v_terms.data_ptr(), t_terms.data_ptr()
+        _lib.check(_lib.lib().tan_simnce_fwd(C.byref(d), ops._stream()), "tan_simnce_fwd")
 
     # ------------------------------------------------------------------ forward phases
     def sweep(self, tn_blocks, ci_blocks, own: int):
@@ -107,14 +109,11 @@ class BlockNCE:
         dl = torch.empty(S, R, Mp, dtype=torch.bfloat16, device=dev)
         g_v = g_v.contiguous()
         for q in range(W):
-            args = (_p(self.vn), _p(self._tn[q]), C.c_long(self._stride()), _p(self.tgt), _p(self._ci[q]), _p(self.row_leak),
-                    _p(self.rowsum), _p(self.colsum_all[q]), _p(self.possum_v), _p(self.possum_t), _p(g_v), _p(g_t_all[q].contiguous()),
-                    _p(dl), _p(self.ws), C.c_int(S), C.c_int(self.B), C.c_int(self.T), C.c_int(self.N), C.c_int(Cw), None, C.c_long(0),
-                    None, C.c_int(0), C.c_int(SWEEP | (DIAG if q == self._own else 0)), ops._stream())
-            if self._keep:
-                _lib.check(_lib.lib().tan_simnce_bwd_dl_kept(_p(self._keep[q]), *args), "tan_simnce_bwd_dl_kept")
-            else:
-                _lib.check(_lib.lib().tan_simnce_bwd_dl(*args), "tan_simnce_bwd_dl")
+            g_t = g_t_all[q].contiguous()
+            d = self._block(self._tn[q], self._ci[q], self.colsum_all[q], SWEEP | (DIAG if q == self._own else 0),
+                            keep=self._keep[q] if self._keep else None)
+            d.g_v, d.g_t, d.dl = g_v.data_ptr(), g_t.data_ptr(), dl.data_ptr()
+            _lib.check(_lib.lib().tan_simnce_bwd(C.byref(d), ops._stream()), "tan_simnce_bwd")
             ops.gemm(dl, self._tn[q], d_vn, M=R, N=Cw, K=Mp, a_kc=True, b_kc=False, lda=Mp, ldb=Cw, batch=S, sA=R * Mp,
                      sB=self._stride(), sC=R * Cw, residual=d_vn if q else None)
             if self.shared:

@@ -26,7 +26,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from . import _lib, ops
 
-# A/B switch of the one-pass d-logits + d_vn kernel (tan_simnce_bwd_dl_dvn_kept); 0 = element-wise pass + GEMM
+# A/B switch of the one-pass d-logits + d_vn kernel (tan_simnce_bwd with d_vn set); 0 = element-wise pass + GEMM
 _FUSED_DVN = os.environ.get("TAN_FUSED_DVN", "1") != "0"
 
 _KIND = {"i": 0, "u": 1, "keep": 2, "keep-joint": 3}
@@ -71,6 +71,11 @@ def _stage_major(logits):
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _dp(t):
+    """a descriptor's pointer field: the tensor's address, or NULL"""
+    return t.data_ptr() if t is not None else None
 
 
 class _NCEFn(torch.autograd.Function):
@@ -240,7 +245,7 @@ def _pos_masks(tgt, tpad_u8, B, T, N):
 
 
 class _FusedNCEFn(torch.autograd.Function):
-    """_NCEFn without the logits: tan_simnce_fwd / tan_simnce_bwd_dl + the two d-feature GEMMs.
+    """_NCEFn without the logits: tan_simnce_fwd / tan_simnce_bwd + the two d-feature GEMMs.
 
     `n_valid` (host int, optional) = number of real sentences in the batch.  Padded text columns take part in nothing
     (loss.py:64-70 drops them before the log-sum-exps), so when it is known the sweep runs on the COMPACTED text matrix
@@ -258,7 +263,7 @@ class _FusedNCEFn(torch.autograd.Function):
             Mc = idx.shape[0]
             tn_run = tn.index_select(1, idx)
         else:
-            idx = colmap = None
+            colmap = None
             Mc, tn_run, ci_run = Mp, tn, col_invalid
         stats = torch.empty(2 * S * R + 2 * S * Mc, device=dev)
         rowsum, possum_v = stats[:S * R], stats[S * R:2 * S * R]
@@ -271,47 +276,41 @@ class _FusedNCEFn(torch.autograd.Function):
         ekeep = None
         if want_bwd and L.tan_simnce_keeps(C.c_int(Cw)):
             ekeep = torch.empty(L.tan_simnce_keep_elems(C.c_int(S), C.c_int(R), C.c_int(Mc)), dtype=torch.bfloat16, device=dev)
-        fwd_args = (_p(vn), _p(tn_run), C.c_long(0 if shared else Mc * Cw), _p(tgt), _p(ci_run), _p(row_leak),
-                    _p(rowsum), _p(colsum), _p(possum_v), _p(possum_t), _p(v_terms), _p(t_run), _p(ws),
-                    C.c_int(S), C.c_int(B), C.c_int(T), C.c_int(N), C.c_int(Cw), _p(tn) if compact else None,
-                    C.c_long(0 if shared else Mp * Cw), _p(colmap), C.c_int(Mc), C.c_int(0))
-        if ekeep is not None:
-            _lib.check(L.tan_simnce_fwd_keep(*fwd_args, _p(ekeep), ops._stream()), "tan_simnce_fwd_keep")
-        else:
-            _lib.check(L.tan_simnce_fwd(*fwd_args, ops._stream()), "tan_simnce_fwd")
+        d = ctx.desc = _lib.SimNceDesc()
+        d.S, d.B, d.T, d.N, d.C, d.Mc = S, B, T, N, Cw, Mc
+        d.vn, d.tn, d.t_stage_stride = vn.data_ptr(), tn_run.data_ptr(), 0 if shared else Mc * Cw
+        if compact:
+            d.tn_blocks, d.tb_stage_stride, d.colmap = tn.data_ptr(), 0 if shared else Mp * Cw, colmap.data_ptr()
+        d.tgt, d.col_invalid, d.row_leak = tgt.data_ptr(), ci_run.data_ptr(), _dp(row_leak)
+        d.rowsum, d.colsum, d.possum_v, d.possum_t = rowsum.data_ptr(), colsum.data_ptr(), possum_v.data_ptr(), possum_t.data_ptr()
+        d.v_terms, d.t_terms, d.e_keep, d.ws = v_terms.data_ptr(), t_run.data_ptr(), _dp(ekeep), ws.data_ptr()
+        _lib.check(L.tan_simnce_fwd(C.byref(d), ops._stream()), "tan_simnce_fwd")
         # compacted sweeps return the text terms in COMPACTED column order ([S, Mc]; get_loss compacts the column masks of the tail
         # instead, once and off the critical path): scattering them back to [S, B*N] was a fill + an index_copy per sweep here and
         # a gather per sweep in the backward, all on the serial chain between the stacks and the backward
         t_terms = t_run
-        ctx.saved = (vn, tn, tn_run, tgt, ci_run, row_leak, rowsum, colsum, possum_v, possum_t, ws, idx, colmap, ekeep)
+        ctx.saved = (vn, tn, tn_run, colmap, ekeep, (tgt, ci_run, row_leak, stats, ws))       # (the last: alive for the descriptor)
         ctx.dims = (S, B, T, N, Cw, shared, Mc)
         return v_terms, t_terms
 
     @staticmethod
     def backward(ctx, g_v, g_t):
-        vn, tn, tn_run, tgt, ci_run, row_leak, rowsum, colsum, possum_v, possum_t, ws, idx, colmap, ekeep = ctx.saved
+        vn, tn, tn_run, colmap, ekeep, _ = ctx.saved
         S, B, T, N, Cw, shared, Mc = ctx.dims
         R, Mp, dev = B * T, B * N, vn.device
-        compact = idx is not None
+        compact = colmap is not None
         g_v = torch.zeros(S, R, device=dev) if g_v is None else g_v.contiguous()
         g_t = torch.zeros(S, Mc, device=dev) if g_t is None else g_t.contiguous()           # [S, Mc]: compacted order, like t_terms
         fusable = ekeep is not None and vn.dtype == torch.bfloat16 and Mc % 8 == 0 and N <= 32 and Mc < 32768
         dl = torch.empty(S, R, Mc, dtype=torch.bfloat16, device=dev)
-        bwd_args = (_p(vn), _p(tn_run), C.c_long(0 if shared else Mc * Cw), _p(tgt), _p(ci_run),
-                    _p(row_leak), _p(rowsum), _p(colsum), _p(possum_v), _p(possum_t), _p(g_v),
-                    _p(g_t), _p(dl), _p(ws), C.c_int(S), C.c_int(B), C.c_int(T), C.c_int(N),
-                    C.c_int(Cw), _p(tn) if compact else None, C.c_long(0 if shared else Mp * Cw),
-                    _p(colmap), C.c_int(Mc), C.c_int(TAN_SIM_SWEEP | TAN_SIM_DIAG | TAN_SIM_DIAG_KEEP), ops._stream())      # `ws` still holds the forward's same-video blocks
         d_vn = torch.empty_like(vn)
-        if fusable and _FUSED_DVN:
-            # d logits and d_vn = dl . tn_run in one pass over the kept exponentials (the tile is the MFMA operand while it is in the LDS)
-            _lib.check(_lib.lib().tan_simnce_bwd_dl_dvn_kept(_p(ekeep), *bwd_args[:13], _p(d_vn), *bwd_args[13:]),
-                       "tan_simnce_bwd_dl_dvn_kept")
-        else:
-            if ekeep is not None:
-                _lib.check(_lib.lib().tan_simnce_bwd_dl_kept(_p(ekeep), *bwd_args), "tan_simnce_bwd_dl_kept")
-            else:
-                _lib.check(_lib.lib().tan_simnce_bwd_dl(*bwd_args), "tan_simnce_bwd_dl")
+        d = ctx.desc
+        d.g_v, d.g_t, d.dl = g_v.data_ptr(), g_t.data_ptr(), dl.data_ptr()
+        # d logits and d_vn = dl . tn_run in one pass over the kept exponentials (the tile is the MFMA operand while it is in the LDS)
+        d.d_vn = d_vn.data_ptr() if fusable and _FUSED_DVN else None
+        d.phases = TAN_SIM_SWEEP | TAN_SIM_DIAG | TAN_SIM_DIAG_KEEP          # `ws` still holds the forward's same-video blocks
+        _lib.check(_lib.lib().tan_simnce_bwd(C.byref(d), ops._stream()), "tan_simnce_bwd")
+        if d.d_vn is None:
             ops.gemm(dl, tn_run, d_vn, M=R, N=Cw, K=Mc, a_kc=True, b_kc=False, lda=Mc, ldb=Cw, batch=S, sA=R * Mc,
                      sB=0 if shared else Mc * Cw, sC=R * Cw)
         if shared:       # one text feature for every stage: contract over (stage, row) in a single split-K GEMM
@@ -362,10 +361,8 @@ def simfam_ok(S, N, Mc, dtype, T=64):
     """Shapes `tan_simfam_fwd / bwd` take (include/tan_hip.h): bf16, <= 8 stages, <= 32 sentences per video, sweep columns a multiple
     of 8 within the resident sweep's limit, and a [T, N] same-video block the finishing launch can hold twice in a CU's LDS (the bound
     of `tan_simfam_fwd`: anything larger takes the separate-launch path instead of failing with BAD_ARG -- ADVICE r5)."""
-    # (restates `simfam_fin_lds` of csrc/tan_simnce.hip: change the two together)
-    fin_lds = 4 * (2 * T * N + T + 256 + 96) + 4 * 32 + 32 + T + 16
-    return (_SIMFAM and dtype == torch.bfloat16 and S <= 8 and N <= 32 and Mc % 8 == 0 and Mc < 32768
-            and fin_lds <= 160 * 1024 and Mc <= _lib.lib().tan_simnce_max_cols())
+    # (St and B only have to be valid here: `simfam_stages_ok` checks the text stages, and no limit depends on B)
+    return bool(_SIMFAM and dtype == torch.bfloat16 and _lib.lib().tan_simfam_accepts(S, S, 1, T, N, Mc))
 
 
 def _ptr8(tensors):

@@ -24,6 +24,7 @@ def test_ctypes_mirrors_have_the_c_layout():
     assert L.tan_abi_sizeof(2) == C.sizeof(_lib.LayerBufs)
     assert L.tan_abi_sizeof(3) == C.sizeof(_lib.EncoderDesc)
     assert L.tan_abi_sizeof(4) == C.sizeof(_lib.SimFamDesc)
+    assert L.tan_abi_sizeof(5) == C.sizeof(_lib.SimNceDesc)
 
 
 def test_bad_arguments_are_rejected_without_touching_a_device():
@@ -32,6 +33,21 @@ def test_bad_arguments_are_rejected_without_touching_a_device():
     assert L.tan_gemm(C.byref(d), None) == -1
     assert L.tan_layernorm_fwd(None, None, None, None, None, None, None, 0, C.c_long(4), 512, C.c_float(1e-5), 0, None) == -1
     assert L.tan_masked_quantile(None, None, 5, C.c_float(0.3), None, None) == -1
+    s = _lib.SimNceDesc()          # all-null descriptor
+    assert L.tan_simnce_fwd(C.byref(s), None) == -1 and L.tan_simnce_bwd(C.byref(s), None) == -1
+
+
+def test_simfam_accepts_agrees_with_the_limits_written_out():
+    """tan_simfam_accepts (what `loss.simfam_ok` asks) against the shape limits and the finishing launch's LDS bytes spelled out here."""
+    L = _lib.lib()
+
+    def restated(S, N, Mc, T):
+        fin_lds = 4 * (2 * T * N + T + 256 + 96) + 4 * 32 + 32 + T + 16
+        return S <= 8 and N <= 32 and Mc % 8 == 0 and Mc < 32768 and fin_lds <= 160 * 1024 and Mc <= L.tan_simnce_max_cols()
+
+    assert restated(6, 16, 1344, 64) and L.tan_simfam_accepts(6, 6, 128, 64, 16, 1344) == 1
+    assert not restated(6, 32, 1344, 622) and L.tan_simfam_accepts(6, 6, 128, 622, 32, 1344) == 0       # the LDS bound: T <= 621 at N = 32
+    assert restated(6, 32, 1344, 621) and L.tan_simfam_accepts(6, 6, 128, 621, 32, 1344) == 1
 
 
 def test_header_cites_reference_lines_and_has_no_torch_types():

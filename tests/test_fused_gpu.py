@@ -126,8 +126,8 @@ def test_compaction_lifts_the_padded_column_count_over_the_sweep_limit():
 @pytest.mark.parametrize("S,B,T,N,shared,compact,leak", [(2, 3, 70, 5, False, False, False), (3, 4, 64, 9, True, True, True),
                                                          (1, 5, 40, 16, False, True, False), (2, 6, 64, 30, True, False, True)])
 def test_kept_exponentials_match_the_recomputing_backward(S, B, T, N, shared, compact, leak):
-    """_FusedNCEFn with the exponentials kept by the statistics sweep (tan_simnce_fwd_keep / tan_simnce_bwd_dl_kept: one element-wise
-    pass) against the recomputing backward (tan_simnce_bwd_dl) on the same inputs: ragged R = B*T and column counts that are not
+    """_FusedNCEFn with the exponentials kept by the statistics sweep (tan_simnce_desc.e_keep: one element-wise
+    pass) against the recomputing backward (e_keep NULL) on the same inputs: ragged R = B*T and column counts that are not
     multiples of the 128 x 128 tiles, shared and per-stage text features, column compaction, leaked (padded) frames.  Terms are
     the same sweep's; the feature gradients differ by one extra bf16 rounding of e."""
     from temporalalignnet_amd import _lib, loss as L
@@ -183,8 +183,8 @@ def test_kept_exponentials_match_the_recomputing_backward(S, B, T, N, shared, co
                                                          (1, 5, 40, 16, False, True, False), (2, 6, 64, 30, True, False, True),
                                                          (2, 40, 64, 10, False, True, False), (3, 24, 64, 16, True, False, False)])
 def test_one_pass_dlogits_and_dvn_match_the_pass_plus_gemm(S, B, T, N, shared, compact, leak):
-    """tan_simnce_bwd_dl_dvn_kept (d logits + d_vn = dl . tn in one pass: the tile is the MFMA operand while it is in the LDS; same-video
-    corrections from the dense array of simnce_corr_kernel) against tan_simnce_bwd_dl_kept + the GEMM it replaces, same kept exponentials.  d_tn is computed from the d-logits either path wrote by the
+    """tan_simnce_bwd with d_vn set (d logits + d_vn = dl . tn in one pass: the tile is the MFMA operand while it is in the LDS; same-video
+    corrections from the dense array of simnce_corr_kernel) against the element-wise pass + the GEMM it replaces, same kept exponentials.  d_tn is computed from the d-logits either path wrote by the
     same GEMM (equal up to the run-to-run last-bit noise of the sweep's atomically summed row sums); d_vn differs by the f32 summation
     order only (one bf16 ulp)."""
     from temporalalignnet_amd import _lib, loss as L
@@ -226,3 +226,36 @@ def test_one_pass_dlogits_and_dvn_match_the_pass_plus_gemm(S, B, T, N, shared, c
         assert (dt0 - dt1).abs().max().item() <= 1e-2 * dt1.abs().max().item() + 1e-7
         assert (dv0 - dv1).norm().item() <= 3e-3 * dv1.norm().item() + 1e-7, (dv0 - dv1).norm().item() / dv1.norm().item()
         assert (dv0 - dv1).abs().max().item() <= 1e-2 * dv1.abs().max().item() + 1e-7
+
+
+def test_non_resident_sweep_matches_fp64():
+    """A channel count other than 512 through _FusedNCEFn: the re-staging sweep (simnce_kernel<0> / <1>: no kept exponentials, the
+    backward recomputes; same-video blocks through tan_gemm) against fp64 autograd of einsum + NCE on the same bf16 features.
+    B = 3, T = 40, N = 5, S = 2, C = 256: ragged R = 120 (one partial 128-row panel), Mp = 15 columns.  Tolerances are this file's for
+    its bf16 comparisons: 2e-3 relative on term values (the row sums meet in f32 atomics: not bitwise), 6e-3 of the norm on the
+    feature gradients (bf16 d-logits and bf16 gradients: two roundings of 2^-9, about 1.6e-3 of the norm)."""
+    from temporalalignnet_amd import _lib, loss as L
+    S, B, T, N, Cw = 2, 3, 40, 5, 256
+    assert not _lib.lib().tan_simnce_keeps(Cw)
+    g = torch.Generator(device="cpu").manual_seed(77)
+    R, Mp = B * T, B * N
+    vn = torch.nn.functional.normalize(torch.randn(S, R, Cw, generator=g), dim=-1).cuda().bfloat16()
+    tn = torch.nn.functional.normalize(torch.randn(S, Mp, Cw, generator=g), dim=-1).cuda().bfloat16()
+    tgt = (torch.rand(B, T, N, generator=g) < 0.15).float().cuda()
+    tpad = torch.zeros(B, N, dtype=torch.bool).cuda()
+    gv, gt = torch.randn(S, R, generator=g).cuda(), torch.randn(S, Mp, generator=g).cuda()
+    v = vn.clone().requires_grad_(True); t = tn.clone().requires_grad_(True)
+    v_terms, t_terms = L._FusedNCEFn.apply(v, t, tgt, tpad.view(-1).to(torch.uint8), None, B, T, N, None)
+    (v_terms * gv).sum().add((t_terms * gt).sum()).backward()
+    v64 = vn.double().requires_grad_(True); t64 = tn.double().requires_grad_(True)
+    v_ref, t_ref = loss_ref.nce_ref(torch.einsum("src,smc->srm", v64, t64), tgt, tpad, None)
+    (v_ref * gv.double()).sum().add((t_ref * gt.double()).sum()).backward()
+    for name, got, want in (("v_terms", v_terms, v_ref), ("t_terms", t_terms, t_ref)):
+        err = ((got.detach().double() - want.detach()).abs() / want.detach().abs().clamp(min=1.0)).max().item()
+        print(name, "max error relative to max(1, |ref|):", err)
+        assert err <= 2e-3, (name, err)
+    for name, got, want in (("d_vn", v.grad, v64.grad), ("d_tn", t.grad, t64.grad)):
+        assert torch.isfinite(got).all()
+        rel = (got.double() - want).norm().item() / want.norm().item()
+        print(name, "relative error of the norm:", rel)
+        assert rel <= 6e-3, (name, rel)

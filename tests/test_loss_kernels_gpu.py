@@ -168,7 +168,7 @@ def test_materialised_nce_rejects_more_columns_than_its_lds_holds():
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# 2. fused similarity + NCE: _FusedNCEFn (tan_simnce_fwd[_keep], tan_simnce_bwd_dl[_kept | _dvn_kept] + the d-feature GEMMs)
+# 2. fused similarity + NCE: _FusedNCEFn (tan_simnce_fwd, tan_simnce_bwd with and without e_keep / d_vn + the d-feature GEMMs)
 
 class _NoKeep:
     """The library with tan_simnce_keeps() answering 0: the forward keeps no exponentials, the backward recomputes them."""

@@ -1,4 +1,4 @@
-"""Stand-alone time of the similarity statistics sweep (tan_simnce_fwd / tan_simnce_fwd_keep) at the headline shape: what keeping the
+"""Stand-alone time of the similarity statistics sweep (tan_simnce_fwd without / with e_keep) at the headline shape: what keeping the
 exponentials costs the forward.  Run under `rocprofv3 --kernel-trace --stats` for the kernel's own duration."""
 import sys, torch
 from temporalalignnet_amd import _lib, loss as L

@@ -84,7 +84,9 @@ typedef struct tan_gemm_desc {
     int split_k;
     float alpha;
     int batch; long sA, sB, sC;
-    float* colsum; /* optional [N] f32: += column sums of the stored output (fused bias gradient); batch must be 1 */
+    float* colsum; /* optional [N] f32: += column sums of the stored elements of C (fused bias gradient; rows ldc apart); batch must be 1.
+                      A bf16 C whose epilogue is vectorised (N % 8 == 0, 16-byte aligned C / residual / aux rows) adds the f32 values
+                      BEFORE the rounding of the store; every other path adds the values it reads back from C */
 } tan_gemm_desc;
 int tan_gemm(const tan_gemm_desc* d, void* stream);
 

@@ -242,6 +242,7 @@ static int launch_gemm(const tan_gemm_desc* d, const GemmArgs& a, dim3 grid, hip
 }
 
 int gemm_glds_try(const tan_gemm_desc* d, hipStream_t st);   // tan_gemm_glds.hip
+int colsum_acc_ld(const void* x, float* out, long rows, int C, long ld, int dtype, void* stream);   // tan_norm.hip
 
 }  // namespace tal
 
@@ -278,12 +279,12 @@ extern "C" int tan_gemm(const tan_gemm_desc* d, void* stream) {
     const int rec = prof_begin(st, kind, 2.0 * d->M * d->N * (double)d->K * d->batch);
     if (d->colsum) TAN_REQUIRE(d->batch == 1 && !d->accumulate);
     int rc = gemm_glds_try(d, st);            // aligned bf16: direct-to-LDS kernel (fuses colsum when its epilogue is vectorised)
-    if (rc == -3) { prof_end(st, rec); return tan_colsum_acc(d->C, d->colsum, d->M, d->N, d->out_dtype, stream); }
+    if (rc == -3) { prof_end(st, rec); return colsum_acc_ld(d->C, d->colsum, d->M, d->N, d->ldc, d->out_dtype, stream); }
     if (rc != -2) { prof_end(st, rec); return rc; }
     if (d->dtype == TAN_F32) rc = launch_gemm<float, float>(d, a, grid, st);
     else if (d->out_dtype == TAN_F32) rc = launch_gemm<bf16_t, float>(d, a, grid, st);
     else rc = launch_gemm<bf16_t, bf16_t>(d, a, grid, st);
     prof_end(st, rec);
-    if (rc == 0 && d->colsum) rc = tan_colsum_acc(d->C, d->colsum, d->M, d->N, d->out_dtype, stream);
+    if (rc == 0 && d->colsum) rc = colsum_acc_ld(d->C, d->colsum, d->M, d->N, d->ldc, d->out_dtype, stream);
     return rc;
 }

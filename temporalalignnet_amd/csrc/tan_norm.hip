@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void l2n_bwd_kernel(const T* __restrict__ dy, 
 // threads span one row with 16-byte loads (8 bf16 / 2x4 f32), the remaining 256/TPR thread groups take alternate rows;
 // partial sums meet in LDS and leave as one atomic per column per block.
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, float* __restrict__ out, long rows, int C,
+__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, float* __restrict__ out, long rows, int C, long ld,
                                                      int rows_per_block, int tpr) {
     __shared__ float red[256 * 8];
     const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, ny = 256 / tpr;
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, fl
     if (c < C && ty < ny) {
 #pragma unroll 4
         for (long r = r0 + ty; r < r1; r += ny) {
-            const float4 a = ld4(x + r * C + c), b = ld4(x + r * C + c + 4);
+            const float4 a = ld4(x + r * ld + c), b = ld4(x + r * ld + c + 4);
             acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
             acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
         }
@@ -413,12 +413,13 @@ __global__ __launch_bounds__(256) void transpose_batch_kernel(const bf16_t* __re
 
 // generic fallback (any C): one thread per column, 64 rows per block
 template <typename T>
-__global__ __launch_bounds__(256) void colsum_generic_kernel(const T* __restrict__ x, float* __restrict__ out, long rows, int C) {
+__global__ __launch_bounds__(256) void colsum_generic_kernel(const T* __restrict__ x, float* __restrict__ out, long rows, int C,
+                                                             long ld) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     const long r0 = (long)blockIdx.y * 64, r1 = min(rows, r0 + 64);
     float s = 0.f;
-    for (long r = r0; r < r1; ++r) s += ld_f(x + r * C + c);
+    for (long r = r0; r < r1; ++r) s += ld_f(x + r * ld + c);
     unsafeAtomicAdd(out + c, s);
 }
 
@@ -738,12 +739,14 @@ extern "C" int tan_l2norm_bwd(const void* dy, const void* y, const float* inv_no
     return tan_l2norm_bwd_multi(dy, y, inv_norm, &ds, 1, rows, C, grp, dst_grp_rows, dst_off, dtype, stream);
 }
 
-extern "C" int tan_colsum_acc(const void* x, float* out, long rows, int C, int dtype, void* stream) {
-    TAN_REQUIRE(x && out && rows > 0 && C > 0);
+// out[c] += sum_r x[r * ld + c]: tan_colsum_acc for rows that are `ld` >= C elements apart (the output of a tan_gemm with ldc > N)
+namespace tal {
+int colsum_acc_ld(const void* x, float* out, long rows, int C, long ld, int dtype, void* stream) {
+    TAN_REQUIRE(x && out && rows > 0 && C > 0 && ld >= C);
     hipStream_t st = (hipStream_t)stream;
-    if (C % 8 != 0 || ((uintptr_t)x % 16) != 0) {
+    if (C % 8 != 0 || ld % 8 != 0 || ((uintptr_t)x % 16) != 0) {
         DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_generic_kernel<T>), dim3(cdiv(C, 256), cdiv(rows, 64)), dim3(256), 0, st,
-                                             (const T*)x, out, rows, C));
+                                             (const T*)x, out, rows, C, ld));
         TAN_LAUNCH_CHECK();
         return 0;
     }
@@ -753,9 +756,14 @@ extern "C" int tan_colsum_acc(const void* x, float* out, long rows, int C, int d
     if (C % 512 == 0) tpr = 64;           // one wave = 1-KiB row segments, 4 row lanes: fewer, fatter blocks and 4x fewer atomics
     const int rpb = (C % 512 == 0 ? 16 : 8) * (256 / tpr);      // rows per thread group
     dim3 grid(cdiv(C, tpr * 8), cdiv(rows, rpb));
-    DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T>), grid, dim3(256), 0, st, (const T*)x, out, rows, C, rpb, tpr));
+    DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T>), grid, dim3(256), 0, st, (const T*)x, out, rows, C, ld, rpb, tpr));
     TAN_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace tal
+
+extern "C" int tan_colsum_acc(const void* x, float* out, long rows, int C, int dtype, void* stream) {
+    return tal::colsum_acc_ld(x, out, rows, C, C, dtype, stream);
 }
 
 extern "C" int tan_rows_copy(const void* src, void* dst, int G, int R, int C, long src_grp_rows, long src_off,

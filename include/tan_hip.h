@@ -709,6 +709,29 @@ int tan_window_stitch_acc(const float* sim_j, const float* sim_d, const float* a
  * max of its softmax over time, score (a_sum / max(tcnt, 1e-5) with the head, else the row max, :219-223), tcnt > 0.          */
 int tan_window_stitch_final(float* acc_j, const float* acc_d, const float* cnt, const float* tcnt, const float* a_sum,
                             const int* rows, long n_rows, long n_acc, float* res, void* stream);
+/* Order-preserving timestamps: a monotonic decode over the stitched rows, in place of the independent per-row arg-max of
+ * eval_zeroshot_align.py:222,237 (ASR sentences are spoken in order; nothing in an arg-max per row respects that).  Per video, with
+ * its kept rows r_0 .. r_{m-1} in decode order, V = vlen and x_i[t] = sim[r_i][t] (the f32 rows tan_window_stitch_final leaves,
+ * -6e4 cells included, used as they are):
+ *     D_0[t] = x_0[t];   D_i[t] = x_i[t] + M_{i-1}[t]   -- one f32 add, round to nearest, never contracted
+ *     M_i[t] = max_{t' <= t} D_i[t'];   A_i[t] = the SMALLEST t' <= t with D_i[t'] == M_i[t]
+ *     t_{m-1} = A_{m-1}[V-1];   t_{i-1} = A_{i-1}[t_i];   path score = D_{m-1}[t_{m-1}]
+ * The seconds are non-decreasing (equal seconds allowed) and maximise the summed similarity; ties go to the smallest t_{m-1}, then
+ * the smallest t_{m-2}, and so on.  The maximum is exact, so a plain f32 restatement gives the same bits whatever its scan order.
+ * A constant added to a row does not move the path: it is also the Viterbi path under each row's log-softmax over time.
+ *   rows [n_rows, 2] int32 (offset into sim, vlen) as for tan_window_stitch_final; order [n_rows] int32: packed row ids, a video's
+ *   rows contiguous and in decode order; vtab [n_videos, 3] int32: first index into order, count, offset of the video's row in
+ *   `run`; keep [n_rows] bytes indexed by packed row id (0 = the row is skipped while walking the video) or NULL = all.
+ *   bp [n_acc] int32 (the back-pointers A, laid out like sim) and run [n_run] f32 (n_run >= sum of vlen: each video's M row,
+ *   updated in place) are scratch and need no initialisation.
+ *   ts [n_rows] int32 <- the second of every kept row, -1 for every other row a video lists (a row no video lists is not
+ *   written); path [n_videos] f32 <- the path score, 0 for a video without a kept row.
+ * Any vlen >= 1.  One workgroup per video, no atomics, no host synchronisation.  A video's rows share one vlen; a table entry that
+ * points outside n_rows / n_acc / n_run, or a row of another vlen, takes no part (nothing is read or written out of bounds).
+ * NULL pointers (other than keep) or non-positive counts: TAN_ERR_BAD_ARG, nothing launched.                                     */
+int tan_monotonic_decode(const float* sim, const int* rows, const int* order, const int* vtab, int n_videos,
+                         const unsigned char* keep, long n_rows, long n_acc, long n_run, int* bp, float* run, int* ts,
+                         float* path, void* stream);
 
 /* ---- zero-shot retrieval (eval/eval_zeroshot_retrieval.py:13-27,157-256) and corpus search over a per-second index ----
  * tan_rank_topk: a matrix-free sweep over scores[q, n] = <Tq[q, :], Vn[n, :]>, Tq [Q, C], Vn [N, C], C == 512, both `dtype`

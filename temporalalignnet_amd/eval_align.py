@@ -120,11 +120,38 @@ def plan_windows(start, end, vlen, seq_len=64, candidates=None, *, max_sentences
 
 
 @torch.no_grad()
+def monotonic_seconds(sim, start, keep=None):
+    """One video's order-preserving timestamps (tan_monotonic_decode): sim [K, vlen] f32 on the device, `start` [K] the ASR starts
+    that order the sentences (equal starts by sentence index), keep [K] bool or None = all.  Returns ([K] int64 on the host, -1
+    where not kept; the path's score).  A constant added to a row does not move the path: decoding `sim` is decoding its
+    log-softmax over time, the quantity the reference arg-maxes row by row."""
+    from . import ops
+    K, vlen = sim.shape
+    if K == 0:
+        return torch.zeros(0, dtype=torch.int64), 0.0
+    dev = sim.device
+    sim = sim.float().contiguous()
+    tab = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)                 # noqa: E731
+    rows = tab(np.stack([np.arange(K) * vlen, np.full(K, vlen)], 1))
+    order = tab(np.argsort(np.asarray(start, dtype=np.float64), kind="stable"))
+    keep_d = None if keep is None else torch.from_numpy(np.asarray(keep).astype(bool)).to(dev)
+    ts = torch.empty(K, dtype=torch.int32, device=dev)
+    path = torch.empty(1, device=dev)
+    ops.monotonic_decode(sim.view(-1), rows, order, tab([[0, K, 0]]), keep_d, torch.empty(K * vlen, dtype=torch.int32, device=dev),
+                         torch.empty(vlen, device=dev), ts, path)
+    return ts.cpu().long(), float(path)
+
+
+@torch.no_grad()
 def test_alignment_htm(get_text_visual_sim, videos, device="cuda", seq_len=64, use_alignability_head=True,
-                       method="overlap-seq", return_per_video=False, batched_sim=None):
+                       method="overlap-seq", return_per_video=False, batched_sim=None, decode=None):
     """`videos`: iterable of {'video' [vlen, Dv], 'start' [K], 'end' [K], 'aligned' [K] 0/1, 'str' list[str]}
     (htm_align.json schema, htm_align/readme.md:11-20).  Returns {'Recall', 'AUC'}.  `batched_sim` (make_batched_sim_fn): the
-    windows of a video are evaluated together instead of one model call per window (same results, see the GPU tests)."""
+    windows of a video are evaluated together instead of one model call per window (same results, see the GPU tests).
+    `decode="monotonic"` (either method): the aligned sentences' seconds come from `monotonic_seconds` -- non-decreasing in ASR start
+    order -- instead of each row's own arg-max (:222,237), so Recall shows what the ordering does to R@1; AUC is not affected."""
+    if decode not in (None, "monotonic"):
+        raise ValueError(f"decode: None or 'monotonic', not {decode!r}")
     recall, scores, tgts, per_video = [], [], [], []
     for item in videos:
         video = torch.as_tensor(item["video"]).float().to(device)[None]
@@ -177,7 +204,10 @@ def test_alignment_htm(get_text_visual_sim, videos, device="cuda", seq_len=64, u
         score = a_j if use_alignability_head else sim.max(-1)[0]
         scores.append(score.cpu().numpy().copy())
         tgts.append(aligned.astype(np.int64))
-        am = prob[torch.from_numpy(aligned).to(device)].argmax(-1).cpu()
+        if decode is None:
+            am = prob[torch.from_numpy(aligned).to(device)].argmax(-1).cpu()
+        else:
+            am = monotonic_seconds(sim, start, aligned)[0][torch.from_numpy(aligned)]
         for k, (s, e) in enumerate(zip(start[aligned], end[aligned])):
             recall.append(math.floor(s) <= int(am[k]) <= math.ceil(e))
         per_video.append({"sim": sim.cpu(), "argmax": am, "score": score.cpu()})

@@ -11,6 +11,8 @@ every sentence as a window candidate (a corpus has no ground truth):
   * per chunk of videos: one `tan_window_stitch_final` launch (stitched rows, first arg-max, softmax maximum, score, coverage) and
     one read-back.  Sentences are embedded once per chunk; the next chunk's feature files are read on a background thread into
     pinned memory and copied on a side stream while the current chunk computes.
+  * on request (`decode="monotonic"`, `--decode monotonic`): one `tan_monotonic_decode` launch per chunk between the two, a
+    dynamic program over the stitched rows that gives every video's sentences non-decreasing seconds in ASR start order.
 
     python -m temporalalignnet_amd.infer_align --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out X.csv
 """
@@ -48,8 +50,8 @@ def _aligner(model):
 class _Chunk:
     """Videos evaluated together: their windows (table rows in plan order), packed features and accumulator layout."""
 
-    def __init__(self, items, plans, seq_len, windows_per_pass):
-        self.items = items
+    def __init__(self, items, plans, seq_len, windows_per_pass, ordered=False):
+        self.items, self.ordered = items, ordered
         K = np.array([len(it["str"]) for it in items], dtype=np.int64)
         V = np.array([it["vlen"] for it in items], dtype=np.int64)
         self.k_off = np.concatenate([[0], np.cumsum(K)])
@@ -73,12 +75,28 @@ class _Chunk:
             self.passes.append((p0, p1, _round8(int(self.table[p0:p1, 3].max()))))
         self.seq_len = seq_len
 
+    # the monotonic decode's tables (tan_monotonic_decode), built when asked for: a run without the decode does not pay for them
+    @property
+    def order(self):
+        """[n_rows] int32: per video its packed rows by ASR start, equal starts by sentence index."""
+        order = [self.k_off[i] + np.argsort(np.asarray(it["start"], dtype=np.float64), kind="stable") for i, it in enumerate(self.items)]
+        return torch.from_numpy(np.concatenate(order + [np.zeros(0, np.int64)]).astype(np.int32))
+
+    @property
+    def vtab(self):
+        """[n_videos, 3] int32: first index into order, count, offset of the video's row in the [sum vlen] scratch."""
+        return torch.from_numpy(np.stack([self.k_off[:-1], np.diff(self.k_off), self.v_off[:-1]], 1).astype(np.int32).reshape(-1, 3))
+
     def load(self, device, stream):
         """Feature files -> one pinned [sum vlen, Dv] buffer -> device on `stream` (the prefetch thread)."""
         host = load_packed(self.items, self.v_off)
         self.host = (host, self.table.pin_memory(), self.rows.pin_memory())     # alive until the copies have run
+        if self.ordered:
+            self.host += (self.order.pin_memory(), self.vtab.pin_memory())
         with torch.cuda.stream(stream):
-            self.video, self.table_d, self.rows_d = self.tensors = tuple(t.to(device, non_blocking=True) for t in self.host)
+            self.tensors = tuple(t.to(device, non_blocking=True) for t in self.host)
+            self.video, self.table_d, self.rows_d = self.tensors[:3]
+            self.order_d, self.vtab_d = self.tensors[3:] if self.ordered else (None, None)
             self.ready = torch.cuda.Event()
             self.ready.record(stream)
 
@@ -101,7 +119,7 @@ def load_packed(items, v_off):
     return host
 
 
-def _chunks(videos, seq_len, windows_per_pass, candidates, max_sentences, on_reject):
+def _chunks(videos, seq_len, windows_per_pass, candidates, max_sentences, on_reject, ordered=False):
     items, plans, n = [], [], 0
     for it in videos:
         it = dict(it)
@@ -120,10 +138,10 @@ def _chunks(videos, seq_len, windows_per_pass, candidates, max_sentences, on_rej
         plans.append(plan)
         n += len(plan)
         if n >= windows_per_pass * PASSES_PER_CHUNK:
-            yield _Chunk(items, plans, seq_len, windows_per_pass)
+            yield _Chunk(items, plans, seq_len, windows_per_pass, ordered)
             items, plans, n = [], [], 0
     if items:
-        yield _Chunk(items, plans, seq_len, windows_per_pass)
+        yield _Chunk(items, plans, seq_len, windows_per_pass, ordered)
 
 
 def _prefetch(chunks, device):
@@ -168,7 +186,8 @@ def _prefetch(chunks, device):
 
 
 @torch.no_grad()
-def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, candidates=None, return_sim=False, on_reject=None):
+def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, candidates=None, return_sim=False, on_reject=None,
+                 decode=None, keep_threshold=None):
     """Yield per video {'vid', 'str', 'timestamp' [K] int64, 'confidence' [K], 'score' [K], 'covered' [K] bool, ('sim' [K, vlen])}.
 
     `videos`: iterable of {'vid', 'start' [K], 'end' [K], 'str' [K], 'video'} -- 'video' is [vlen, Dv] (array / tensor, f32 / f16 /
@@ -177,7 +196,18 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
     HTM-Align evaluation's ~aligned); None = every sentence.  timestamp = first arg-max of the stitched row, confidence = max of its
     softmax over time, score = mean joint alignability logit over the windows holding the sentence (with the alignability head)
     else the row maximum (eval_zeroshot_align.py:219-223); covered = some window holds the sentence.  A video whose windows would
-    hold more sentences than the joint stack accepts raises ValueError, or is passed to `on_reject(vid, message)` and skipped."""
+    hold more sentences than the joint stack accepts raises ValueError, or is passed to `on_reject(vid, message)` and skipped.
+
+    `decode="monotonic"`: order-preserving timestamps on top of the above (one `tan_monotonic_decode` launch per chunk).  Per video,
+    the kept sentences -- covered, and with `keep_threshold` also score > keep_threshold -- taken by ASR start (equal starts by
+    sentence index) get the non-decreasing seconds t_0 <= t_1 <= ... that maximise the summed stitched similarity sum_i sim[i][t_i];
+    ties go to the earliest seconds, last sentence first (include/tan_hip.h has the recurrence).  A constant added to a row does
+    not move the path, so it is also the Viterbi path under each row's log-softmax over time, the quantity 'timestamp' arg-maxes.
+    Results gain 'ordered_timestamp' [K] int64 (-1 where not kept), 'ordered' [K] bool (kept) and 'path_score' (float, the sum
+    along the path; 0.0 without a kept sentence); the other keys are what they are without `decode`."""
+    if decode not in (None, "monotonic"):
+        raise ValueError(f"decode: None or 'monotonic', not {decode!r}")
+    ordered = decode is not None
     net = _aligner(model)
     head = bool(net.use_alignability_head)
     if head and net.num_decoder_layers < 3:
@@ -185,11 +215,12 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
     max_sentences = (JOINT_MAX_LEN[net.compute_dtype] - seq_len) // 8 * 8
     device = torch.device("cuda", torch.cuda.current_device())
     T = seq_len
-    chunks = _chunks(videos, seq_len, windows_per_pass, candidates, max_sentences, on_reject)
+    chunks = _chunks(videos, seq_len, windows_per_pass, candidates, max_sentences, on_reject, ordered)
     for ch in _prefetch(chunks, device):
         if ch.n_rows == 0:
             for it in ch.items:
-                yield _result(it, np.zeros((4, 0), np.float32), None if not return_sim else np.zeros((0, it["vlen"]), np.float32))
+                yield _result(it, np.zeros((4, 0), np.float32), None if not return_sim else np.zeros((0, it["vlen"]), np.float32),
+                              (np.zeros(0, np.int32), 0.0) if ordered else None)
             continue
         emb = embed_text([s for it in ch.items for s in it["str"]]).contiguous()
         acc_j, acc_d, cnt = (torch.zeros(ch.n_acc, device=device) for _ in range(3))
@@ -208,24 +239,40 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
             ops.window_stitch_acc(last(r["sim"]), last(r["dual-sim"]), a_j, tab, acc_j, acc_d, cnt, tcnt, a_sum)
         res = torch.empty(4, ch.n_rows, device=device)
         ops.window_stitch_final(acc_j, acc_d, cnt, tcnt, a_sum, ch.rows_d, res)
+        if ordered:
+            keep = res[3] > 0                         # covered; the threshold compares as write_rows does, in f64
+            if keep_threshold is not None:
+                keep = keep & (res[2].double() > float(keep_threshold))
+            ts = torch.empty(ch.n_rows, dtype=torch.int32, device=device)
+            path = torch.empty(len(ch.items), device=device)
+            ops.monotonic_decode(acc_j, ch.rows_d, ch.order_d, ch.vtab_d, keep, torch.empty(ch.n_acc, dtype=torch.int32, device=device),
+                                 torch.empty(int(ch.v_off[-1]), device=device), ts, path)
         res_h = torch.empty(res.shape, pin_memory=True)
         res_h.copy_(res, non_blocking=True)
         if return_sim:
             sim_h = torch.empty(acc_j.shape, pin_memory=True)
             sim_h.copy_(acc_j, non_blocking=True)
+        if ordered:
+            ts_h, path_h = torch.empty(ts.shape, dtype=ts.dtype, pin_memory=True), torch.empty(path.shape, pin_memory=True)
+            ts_h.copy_(ts, non_blocking=True)
+            path_h.copy_(path, non_blocking=True)
         torch.cuda.current_stream(device).synchronize()
         res_h = res_h.numpy()
         for i, it in enumerate(ch.items):
             k0, k1 = ch.k_off[i], ch.k_off[i + 1]
             sim = sim_h.numpy()[ch.a_off[i]:ch.a_off[i + 1]].reshape(k1 - k0, it["vlen"]).copy() if return_sim else None
-            yield _result(it, res_h[:, k0:k1], sim)
+            yield _result(it, res_h[:, k0:k1], sim, (ts_h.numpy()[k0:k1], float(path_h[i])) if ordered else None)
 
 
-def _result(it, res, sim):
+def _result(it, res, sim, decoded=None):
     out = {"vid": it.get("vid"), "str": it["str"], "timestamp": res[0].astype(np.int64), "confidence": res[1].copy(),
            "score": res[2].copy(), "covered": res[3] > 0}
     if sim is not None:
         out["sim"] = sim
+    if decoded is not None:                           # (seconds [K] int32 with -1 where not kept, path score)
+        out["ordered_timestamp"] = decoded[0].astype(np.int64)
+        out["ordered"] = decoded[0] >= 0
+        out["path_score"] = decoded[1]
     return out
 
 
@@ -264,12 +311,15 @@ CSV_COLUMNS = ("vid", "timestamp", "text", "score", "confidence")
 
 
 def write_rows(writer, result, threshold=None):
-    """HTM-AA rows of one video: covered sentences only, and with `threshold` only those with score > threshold."""
+    """HTM-AA rows of one video: covered sentences only, and with `threshold` only those with score > threshold.  A result of
+    `align_corpus(decode="monotonic")` writes its ordered timestamps in the `timestamp` column (decode it with the same threshold as
+    `keep_threshold`: the rows written are then exactly the decoded ones); rows and columns are the same either way."""
+    stamp = result["ordered_timestamp"] if "ordered_timestamp" in result else result["timestamp"]
     n = 0
     for k, text in enumerate(result["str"]):
         if not result["covered"][k] or (threshold is not None and not float(result["score"][k]) > threshold):
             continue
-        writer.writerow([result["vid"], int(result["timestamp"][k]), text, repr(float(result["score"][k])),
+        writer.writerow([result["vid"], int(stamp[k]), text, repr(float(result["score"][k])),
                          repr(float(result["confidence"][k]))])
         n += 1
     return n
@@ -326,6 +376,9 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=None, help="keep rows with score > threshold (default: every covered sentence)")
     ap.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
     ap.add_argument("--model", choices=("init", "cotrain"), default="init")
+    ap.add_argument("--decode", choices=("argmax", "monotonic"), default="argmax",
+                    help="timestamp column: each sentence's own arg-max (default), or per video the non-decreasing seconds in ASR "
+                         "start order with the largest summed similarity over the rows written (--threshold picks them)")
     a = ap.parse_args(argv)
     if not 0 <= a.worker_id < a.num_workers:
         ap.error("--worker-id must lie in [0, --num-workers)")
@@ -344,7 +397,8 @@ def main(argv=None):
     with open(a.out, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(CSV_COLUMNS)
-        for res in align_corpus(model, corpus, embed, on_reject=on_reject):
+        for res in align_corpus(model, corpus, embed, on_reject=on_reject, decode=None if a.decode == "argmax" else a.decode,
+                                keep_threshold=a.threshold if a.decode == "monotonic" else None):
             n_rows += write_rows(w, res, a.threshold)
             n_vid += 1
     print(f"{a.out}: {n_rows} sentences from {n_vid} videos" + (f", {len(rejected)} skipped" if rejected else ""), file=sys.stderr)

@@ -278,6 +278,24 @@ def window_stitch_final(acc_j, acc_d, cnt, tcnt, a_sum, rows, res):
                                                   acc_j.numel(), _f32(res), _stream()), "tan_window_stitch_final")
 
 
+def monotonic_decode(sim, rows, order, vtab, keep, bp, run, ts, path):
+    """ts [sum K] int32 <- per video the non-decreasing seconds with the largest summed similarity over its kept rows, -1 for the
+    rows not kept; path [n_videos] f32 <- the path's score (tan_monotonic_decode).  sim [sum K*vlen] f32: the stitched rows; rows
+    [sum K, 2] int32 as for window_stitch_final; order [sum K] int32: packed row ids, each video's contiguous and in decode order;
+    vtab [n_videos, 3] int32 = (first index into order, count, offset of the video's row in run); keep [sum K] bool / uint8 or None
+    = every row.  Scratch: bp [sim.numel()] int32, run [>= sum vlen] f32."""
+    n = rows.shape[0]
+    assert rows.dtype == torch.int32 and rows.shape == (n, 2) and rows.is_contiguous() and sim.is_contiguous()
+    assert order.dtype == torch.int32 and order.shape == (n,) and order.is_contiguous()
+    assert vtab.dtype == torch.int32 and vtab.dim() == 2 and vtab.shape[1] == 3 and vtab.is_contiguous()
+    assert keep is None or (keep.dtype in (torch.bool, torch.uint8) and keep.shape == (n,) and keep.is_contiguous())
+    assert bp.dtype == torch.int32 and bp.numel() == sim.numel() and bp.is_contiguous() and run.is_contiguous()
+    assert ts.dtype == torch.int32 and ts.shape == (n,) and ts.is_contiguous() and path.shape == (vtab.shape[0],)
+    _lib.check(_lib.lib().tan_monotonic_decode(_f32(sim), _ptr(rows), _ptr(order), _ptr(vtab), vtab.shape[0], _ptr(keep), n,
+                                               sim.numel(), run.numel(), _ptr(bp), _f32(run), _ptr(ts), _f32(path), _stream()),
+               "tan_monotonic_decode")
+
+
 def rank_topk_ws_bytes(Q, N, k):
     n = _lib.lib().tan_rank_topk_ws_bytes(Q, N, k)
     if n < 0:

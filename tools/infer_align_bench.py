@@ -2,11 +2,13 @@
 `make_batched_sim_fn`, every sentence a candidate), same model, same synthetic corpus, one process, ABBA order, device-synchronised
 wall clocks.  Prints one JSON line.
 
-    python tools/infer_align_bench.py [--videos 256] [--reps 2] [--only corpus]
+    python tools/infer_align_bench.py [--videos 256] [--reps 2] [--only corpus] [--decode monotonic]
 
 Corpus: seeded, vlen uniform in [120, 900] s, one sentence per ~8 s, [vlen, 1024] f16 features, random [K, 512] sentence embeddings
 (looked up, so neither path pays for a language model).  Model: E6D6, bf16, alignability head, random weights.
 `--only corpus` runs align_corpus alone (for a `rocprofv3 --kernel-trace --stats` run of its own).
+`--decode monotonic` measures instead what the order-preserving decode costs: align_corpus with it against align_corpus without,
+ABBA in one process (with `--only corpus`: align_corpus with the decode alone).
 """
 import argparse
 import json
@@ -45,7 +47,9 @@ def main():
     ap.add_argument("--reps", type=int, default=2, help="ABBA blocks")
     ap.add_argument("--windows-per-pass", type=int, default=256)
     ap.add_argument("--only", choices=("corpus",), default=None)
+    ap.add_argument("--decode", choices=("argmax", "monotonic"), default="argmax")
     a = ap.parse_args()
+    decode = None if a.decode == "argmax" else a.decode
     torch.manual_seed(0)
     model = build_model(default_args(model="init", num_encoder_layers=6, num_decoder_layers=6, use_alignability_head=1),
                         compute_dtype="bf16", random_pos_start=0).cuda().eval()
@@ -56,6 +60,10 @@ def main():
     n_win = sum(len(plan_windows(v["start"], v["end"], len(v["video"]))) for v in vids)
 
     def run_corpus():
+        for _ in align_corpus(model, vids, embed, windows_per_pass=a.windows_per_pass, decode=decode):
+            pass
+
+    def run_argmax():
         for _ in align_corpus(model, vids, embed, windows_per_pass=a.windows_per_pass):
             pass
 
@@ -64,11 +72,12 @@ def main():
             warnings.simplefilter("ignore")
             test_alignment_htm(None, vids, return_per_video=True, batched_sim=make_batched_sim_fn(model, embed))
 
-    paths = {"corpus": run_corpus} if a.only else {"corpus": run_corpus, "per_video": run_per_video}
+    other = "per_video" if decode is None else "argmax"             # what `corpus` is measured against
+    paths = {"corpus": run_corpus} if a.only else {"corpus": run_corpus, other: run_per_video if decode is None else run_argmax}
     for f in paths.values():                   # warm-up: code objects, workspaces of every pass shape
         f()
     times = {k: [] for k in paths}
-    order = ["corpus"] if a.only else ["corpus", "per_video", "per_video", "corpus"]
+    order = ["corpus"] if a.only else ["corpus", other, other, "corpus"]
     for _ in range(a.reps):
         for k in order:
             torch.cuda.synchronize()
@@ -77,12 +86,14 @@ def main():
             torch.cuda.synchronize()
             times[k].append(time.perf_counter() - t0)
     out = {"videos": len(vids), "windows": n_win, "sentences": len(names), "windows_per_pass": a.windows_per_pass,
-           "model": "E6D6 bf16 head", "gpu": torch.cuda.get_device_name(0)}
+           "model": "E6D6 bf16 head", "decode": a.decode, "gpu": torch.cuda.get_device_name(0)}
     for k, ts in times.items():
         best, med = min(ts), float(np.median(ts))
         out[k] = {"s": [round(t, 4) for t in ts], "videos_per_s": round(len(vids) / med, 2), "windows_per_s": round(n_win / med, 1)}
     if "per_video" in out:
         out["speedup_median"] = round(float(np.median(times["per_video"]) / np.median(times["corpus"])), 2)
+    if "argmax" in out:
+        out["decode_cost_median"] = round(float(np.median(times["corpus"]) / np.median(times["argmax"])), 4)
     print(json.dumps(out))
 
 

@@ -774,6 +774,49 @@ int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* c
 int tan_rank_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
                        const int* pair, int k, int splits, int* higher, int* ties, float* top_score, int* top_row, void* ws,
                        void* stream);
+/* ---- moment search: the k best DISTINCT videos per query, each with its best second and the extent of the moment around it ----
+ * tan_rank_topk_video: tan_rank_topk's sweep (Tq [Q, C], Vn [N, C], C == 512, `dtype` TAN_F32 or TAN_BF16, 16-byte aligned) over
+ * an index whose rows are grouped into videos: v_off [n_videos + 1] int32 on the device, v_off[0] == 0, v_off[n_videos] == N,
+ * strictly increasing (video v owns the rows [v_off[v], v_off[v + 1]); every video has at least one row); 1 <= n_videos <= N.
+ *   top_score / top_row / top_video [Q, k], 1 <= k <= 32, k <= n_videos: the k videos with the largest
+ *     max over n in [v_off[v], v_off[v + 1]) of score(q, n), by descending maximum, equal maxima by ascending top_row (videos are
+ *     contiguous row ranges, so that is ascending video number too).  top_score (f32) is that maximum, top_row (int32) the
+ *     SMALLEST row of v that attains it -- a global index row; the second is top_row - v_off[v] -- and top_video (int32) is v.
+ *   score(q, n) comes from the same instruction sequence as tan_rank_topk's sweep (the same MFMA chains in the same order): the
+ *     returned scores have that sweep's bits.  Nothing whose size grows with Q * N or Q * n_videos is stored.
+ *   splits: as tan_rank_topk.  Scores, rows, videos and order are bit-identical from run to run and for every `splits`; a video
+ *     may straddle 64-row tiles and split boundaries.  No float atomics.
+ *   ws: tan_rank_topk_video_ws_bytes(Q, N, n_videos, k) bytes of scratch, 16-byte aligned: the videos of every 64-row tile's first and
+ *     last row (N / 8 bytes) and the splits' lists (at most 256 * Q * k * 12 bytes); it does not depend on `splits`; -1 for invalid
+ *     sizes.
+ * A v_off that breaks its contract is the CALLER's error: every video lookup is clamped to [0, n_videos), nothing is read or
+ * written out of bounds, and the lists are unspecified (a slot may then hold score -inf, row 0x7fffffff, video -1).  The Python
+ * wrapper checks v_off on request.
+ * Any Q >= 1, 1 <= N < 2^31; tails are masked in the kernel.  Another width, k outside [1, min(32, n_videos)], an unknown dtype, a
+ * NULL pointer, negative splits, n_videos outside [1, N]: TAN_ERR_BAD_ARG, nothing launched.
+ * tan_rank_topk_video_e4m3: the same over the e4m3 rows of tan_rank_topk_e4m3, score(q, n) = (acc * v_scale[n]) * q_scale[q].
+ * tan_moment_extent / _e4m3: for every hit (q, i) of such lists (top_score / top_row / top_video [Q, k], the same Tq, Vn, v_off,
+ * n_videos, k) and width >= 0 (f32): start / end [Q, k] int32 <- the moment around the peak as GLOBAL index rows, inclusive.  With
+ * p = top_row[q, i], v = top_video[q, i] and thr = top_score[q, i] - width (one f32 subtraction):
+ *     start = the smallest row >= v_off[v] such that every row n in [start, p) has s(q, n) >= thr,
+ *     end   = the largest row < v_off[v + 1] such that every row n in (p, end] has s(q, n) >= thr;
+ * row p itself is inside and is not tested again.  s(q, n) is the f32 dot product of the stored operands (bf16 / f32 values, or
+ * e4m3 codes with (acc * v_scale[n]) * q_scale[q]) in this kernel's own summation order; it need not have the sweep's bits.  One
+ * wave per hit walks outward from p and stops at the first failing row: the cost follows the moment's length, any vlen >= 1, no
+ * scratch, no atomics, run-to-run identical.  A top_row / top_video outside the index is clamped for memory safety and gives
+ * unspecified extents.  Argument rules as tan_rank_topk_video (no splits, no ws), and width < 0 or NaN: TAN_ERR_BAD_ARG.         */
+long tan_rank_topk_video_ws_bytes(long Q, long N, long n_videos, int k);
+int tan_rank_topk_video(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos, int k,
+                        int splits, float* top_score, int* top_row, int* top_video, void* ws, void* stream);
+int tan_rank_topk_video_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                             const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_row, int* top_video,
+                             void* ws, void* stream);
+int tan_moment_extent(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos, int k,
+                      const float* top_score, const int* top_row, const int* top_video, float width, int* start, int* end,
+                      void* stream);
+int tan_moment_extent_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                           const int* v_off, long n_videos, int k, const float* top_score, const int* top_row,
+                           const int* top_video, float width, int* start, int* end, void* stream);
 /* Clip pooling of test_retrieval_yc2 (:197-214).  stage: one stage of the video stack's output, window w's frame f at
  * stage + w * win_stride + f * 512 elements of `dtype` (win_stride >= T * 512, a multiple of 8); table [W, 3] int32 = (clip,
  * first_frame, n_frames) per window.  normalize != 0: every selected frame is L2-normalised (sim = 'cos').  sum [n_clips, 512] /

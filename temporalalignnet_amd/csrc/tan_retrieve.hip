@@ -19,6 +19,9 @@
 // tan_quantize_rows_e4m3, include/tan_hip.h): a third instantiation of rank_kernel.  The 64 row scales of an index tile ride into
 // LDS with the tile's last K chunk, and every accumulator becomes (acc * v_scale[n]) * q_scale[q] -- in the pair launch and in
 // the sweep alike -- before anything compares it, so thresholds, candidate buffers, sort64 and the merge see final scores.
+// tan_rank_topk_video ranks VIDEOS (contiguous row ranges, v_off) by their best row with the same sweep (rank_kernel's VIDEO mode):
+// a candidate slot also holds its video, compaction keeps one entry per video (distinct64), and the merge folds the splits' lists the
+// same way.  tan_moment_extent then walks outward from each hit's best row while the score stays within `width` of the peak.
 //
 // tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
 // of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
@@ -48,7 +51,10 @@ template <> struct RCfg<e4m3_t> { static constexpr int KC = 256, LD = 264; };
 template <typename T> constexpr int scale_bytes() { return sizeof(T) == 1 ? BN * 4 : 0; }   // e4m3: a tile's row scales, after the buffers
 template <typename T> constexpr int tile_bytes() { return 2 * BN * RCfg<T>::LD * (int)sizeof(T) + scale_bytes<T>(); }
 constexpr int BUF_BYTES = 4 * 32 * CAP * 8;
-template <typename T> constexpr int sweep_lds() { return (tile_bytes<T>() + 15) / 16 * 16 + BUF_BYTES; }
+constexpr int VID_BYTES = 4 * 32 * CAP * 4 + 2 * BN * 4;          // the video sweep: a video per candidate slot, and per row of two tiles
+template <typename T, bool VIDEO = false> constexpr int sweep_lds() {
+    return (tile_bytes<T>() + 15) / 16 * 16 + BUF_BYTES + (VIDEO ? VID_BYTES : 0);
+}
 
 __device__ __forceinline__ bool better(float s, int n, float os, int on) { return s > os || (s == os && n < on); }
 
@@ -66,6 +72,44 @@ __device__ __forceinline__ void sort64(float& s, int& n, int lane) {
             if (!keep) { s = os; n = on; }
         }
     }
+}
+
+// sort64 with a payload: the entry's video
+__device__ __forceinline__ void sort64v(float& s, int& n, int& v, int lane) {
+#pragma unroll
+    for (int size = 2; size <= 64; size <<= 1) {
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const float os = __shfl_xor(s, stride, 64);
+            const int on = __shfl_xor(n, stride, 64), ov = __shfl_xor(v, stride, 64);
+            const bool lower = (lane & stride) == 0, desc = (lane & size) == 0;
+            const bool mine = better(s, n, os, on);
+            const bool keep = (lower == desc) ? mine : !mine;
+            if (!keep) { s = os; n = on; v = ov; }
+        }
+    }
+}
+
+// sort64v, then every entry whose video already appears at a better rank is dropped: lane j holds the j-th best DISTINCT video's
+// best entry, (-inf, SENT_ROW) after the last one.  All 64 lanes must be active.
+__device__ __forceinline__ void distinct64(float& s, int& n, int& v, int lane) {
+    sort64v(s, n, v, lane);
+    bool dup = false;
+#pragma unroll
+    for (int i = 0; i < 63; ++i) dup |= lane > i && v == __builtin_amdgcn_readlane(v, i);
+    if (__any(dup && n != SENT_ROW)) {                             // the empty slots are last already: no duplicate, no second sort
+        if (dup) { s = -INFINITY; n = SENT_ROW; }
+        sort64v(s, n, v, lane);
+    }
+}
+
+// the largest v in [lo, hi] with v_off[v] <= n (lo if there is none): whatever v_off holds, the result lies in [lo, hi]
+__device__ __forceinline__ int video_search(const int* __restrict__ v_off, long n, int lo, int hi) {
+    while (lo < hi) {
+        const int mid = (int)(((long)lo + hi + 1) >> 1);
+        if (v_off[mid] <= n) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 template <typename T> struct QFrag;
@@ -107,12 +151,22 @@ __device__ __forceinline__ void stage_store(T* tile, int tid, const uint4 (&pre)
 // PAIR = true : launch 1 (grid = query tiles); tile t of 2 holds the paired rows of the block's queries 64 t .. 64 t + 63
 // PAIR = false: launch 2 (grid = query tiles x splits)
 // q_scale / v_scale: the rows' scales, e4m3 only (the other instantiations do not read them)
-template <typename T, bool PAIR>
+// VIDEO = true: the sweep of tan_rank_topk_video -- the same tiles and MFMA chains, but a query's list holds at most one entry per
+// video, and a candidate slot holds its video next to score and row.  tvid [tiles] holds the videos of every tile's first and last
+// row (tile_video_kernel; the next tile's pair is fetched while this tile's MFMAs run).  A tile that lies inside one video (most
+// do) gives a query ONE candidate, its (max, first arg-max) over the tile's rows.  A tile with a video boundary takes the per-row
+// path: its 64 rows' videos are searched in v_off between the tile's two videos before the MFMA loop and wait in LDS (two
+// buffers: a wave may start tile t + 1 while another still reads tile t's).  Compaction keeps the k best distinct videos
+// (distinct64) and the threshold is the k-th distinct video's score, -inf while fewer are held: a row below it cannot enter the
+// final list, and a dropped entry is dominated by a kept row of its own video.  Nothing in the compaction touches global memory.
+template <typename T, bool PAIR, bool VIDEO = false>
 __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Q, long N,
                                                    const int* __restrict__ pair, int k, long tiles_per_split, long n_tiles,
                                                    float* __restrict__ dscore, int* __restrict__ higher, int* __restrict__ ties,
                                                    float* __restrict__ part_s, int* __restrict__ part_n,
-                                                   const float* __restrict__ q_scale, const float* __restrict__ v_scale) {
+                                                   const float* __restrict__ q_scale, const float* __restrict__ v_scale,
+                                                   const int2* __restrict__ tvid, const int* __restrict__ v_off,
+                                                   int* __restrict__ part_v) {
     typedef Mma<T> M;
     typedef typename M::frag_t frag_t;
     constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, KS = M::KS, NCH = RC / KC, SPC = KC / KS, NFR = RC / KS;
@@ -124,6 +178,8 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
     float* sc = reinterpret_cast<float*>(smem + 2 * TS * sizeof(T));   // F8: the current tile's 64 row scales
     float* bs = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16);
     int* bn = reinterpret_cast<int*>(bs + 4 * 32 * CAP);
+    int* bv = bn + 4 * 32 * CAP;                                   // VIDEO only: the candidates' videos, then the rows' videos of two tiles
+    int* vt = bv + 4 * 32 * CAP;
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
     const long qblk = (long)blockIdx.x * BQ;
@@ -144,7 +200,7 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
     if (PAIR) { t0 = 0; t1 = 2; }
     else { t0 = (long)blockIdx.y * tiles_per_split; t1 = t0 + tiles_per_split < n_tiles ? t0 + tiles_per_split : n_tiles; }
 
-    const bool counting = !PAIR && pair != nullptr;
+    const bool counting = !PAIR && !VIDEO && pair != nullptr;
     const float dq = (counting && qok) ? dscore[qme] : 0.0f;
     int hi = 0, eq = 0, fill = 0;
     float thr = -INFINITY, dval = 0.0f;
@@ -181,8 +237,47 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
         }
     };
 
+    // sorts every buffer of the wave that `need` more entries would overflow, keeps its k best and raises the query's threshold
+    auto compact = [&](int need) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int qi = 0; qi < 32; ++qi) {
+            const int f = __builtin_amdgcn_readlane(fill, qi), nd = __builtin_amdgcn_readlane(need, qi);
+            if (f + nd <= CAP) continue;
+            const int b = (wave * 32 + qi) * CAP;
+            float s = lane < f ? bs[b + lane] : -INFINITY;
+            int n = lane < f ? bn[b + lane] : SENT_ROW;
+            int nf;
+            if constexpr (VIDEO) {
+                int v = lane < f ? bv[b + lane] : -1;
+                distinct64(s, n, v, lane);
+                const int held = __popcll(__ballot(n != SENT_ROW));
+                nf = held < k ? held : k;
+                if (lane < nf) bv[b + lane] = v;
+            } else {
+                sort64(s, n, lane);
+                nf = f < k ? f : k;
+            }
+            if (lane < nf) { bs[b + lane] = s; bn[b + lane] = n; }
+            const float th = __shfl(s, k - 1, 64);
+            if (col == qi) { fill = nf; thr = th; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    };
+
+    int2 tv_next = make_int2(0, 0);
+    if constexpr (VIDEO) {
+        if (t0 < t1) tv_next = tvid[t0];
+    }
     if (t0 < t1) issue(t0, 0);
     for (long t = t0; t < t1; ++t) {
+        const int2 tv = tv_next;
+        if constexpr (VIDEO) {
+            if (t + 1 < t1) tv_next = tvid[t + 1];
+            if (tv.x != tv.y && tid < BN) {                        // a video boundary in the tile: every row's video, for the epilogue
+                const long n = t * BN + tid;
+                vt[(t & 1) * BN + tid] = video_search(v_off, n < N ? n : N - 1, tv.x, tv.y);
+            }
+        }
         f32x16 acc[2];
         acc_zero(acc[0]);
         acc_zero(acc[1]);
@@ -229,6 +324,28 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
             }
             continue;
         }
+        if constexpr (VIDEO) {
+            const long r0 = t * BN;
+            if (tv.x == tv.y) {                                    // block-uniform: the tile lies inside one video
+                float ms = -INFINITY;
+                int mn = SENT_ROW;
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const long n = r0 + rt * 32 + acc_row(r, lane);
+                        if (n < N && better(acc[rt][r], (int)n, ms, mn)) { ms = acc[rt][r]; mn = (int)n; }
+                    }
+                const float os = __shfl_xor(ms, 32, 64);
+                const int on = __shfl_xor(mn, 32, 64);
+                if (better(os, on, ms, mn)) { ms = os; mn = on; }
+                const int need = (mn != SENT_ROW && ms >= thr) ? 1 : 0;
+                if (__any(fill + need > CAP)) compact(need);
+                if (need && lane < 32) { bs[bbase + fill] = ms; bn[bbase + fill] = mn; bv[bbase + fill] = tv.x; }
+                fill += need;
+                continue;
+            }
+        }
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
             const long nbase = t * BN + rt * 32;
@@ -243,28 +360,14 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
             }
             if (k == 0) continue;
             const int c_me = __popc(mask), c_pt = __shfl_xor(c_me, 32, 64), need = c_me + c_pt;
-            if (__any(fill + need > CAP)) {
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                for (int qi = 0; qi < 32; ++qi) {
-                    const int f = __builtin_amdgcn_readlane(fill, qi), nd = __builtin_amdgcn_readlane(need, qi);
-                    if (f + nd <= CAP) continue;
-                    const int b = (wave * 32 + qi) * CAP;
-                    float s = lane < f ? bs[b + lane] : -INFINITY;
-                    int n = lane < f ? bn[b + lane] : SENT_ROW;
-                    sort64(s, n, lane);
-                    const int nf = f < k ? f : k;
-                    if (lane < nf) { bs[b + lane] = s; bn[b + lane] = n; }
-                    const float th = __shfl(s, k - 1, 64);
-                    if (col == qi) { fill = nf; thr = th; }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            }
+            if (__any(fill + need > CAP)) compact(need);
             int off = bbase + fill + ((lane >> 5) ? c_pt : 0);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 if ((mask >> r) & 1) {
                     bs[off] = acc[rt][r];
                     bn[off] = (int)(nbase + acc_row(r, lane));
+                    if constexpr (VIDEO) bv[off] = vt[(t & 1) * BN + rt * 32 + acc_row(r, lane)];
                     ++off;
                 }
             fill += need;
@@ -293,12 +396,19 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
             const int b = (wave * 32 + qi) * CAP;
             float s = lane < f ? bs[b + lane] : -INFINITY;
             int n = lane < f ? bn[b + lane] : SENT_ROW;
-            sort64(s, n, lane);
+            int v = -1;
+            if constexpr (VIDEO) {
+                v = lane < f ? bv[b + lane] : -1;
+                distinct64(s, n, v, lane);
+            } else {
+                sort64(s, n, lane);
+            }
             const long q = qblk + wave * 32 + qi;
             if (q < Q && lane < k) {
                 const long o = ((long)blockIdx.y * Q + q) * k + lane;
                 part_s[o] = s;
                 part_n[o] = n;
+                if constexpr (VIDEO) part_v[o] = v;
             }
         }
     }
@@ -324,9 +434,130 @@ __global__ void __launch_bounds__(256) rank_merge_kernel(const float* __restrict
     if (lane < k) { top_s[q * k + lane] = s; top_n[q * k + lane] = n; }
 }
 
+// tan_rank_topk_video's merge: the same fold, each step by distinct64 -- a video that straddles splits is in several lists and keeps
+// its best entry.  A video of the global top k is in the list of the split that holds its best row (every video ahead of it in that
+// split is ahead of it globally), so the result does not depend on the split count.
+__global__ void __launch_bounds__(256) rank_merge_video_kernel(const float* __restrict__ part_s, const int* __restrict__ part_n,
+                                                               const int* __restrict__ part_v, long Q, int k, int splits,
+                                                               float* __restrict__ top_s, int* __restrict__ top_n, int* __restrict__ top_v) {
+    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (q >= Q) return;
+    float s = -INFINITY;
+    int n = SENT_ROW, v = -1;
+    for (int sp = 0; sp < splits; ++sp) {
+        if (lane >= 32) {
+            const bool real = lane - 32 < k;
+            const long o = ((long)sp * Q + q) * k + (lane - 32);
+            s = real ? part_s[o] : -INFINITY;
+            n = real ? part_n[o] : SENT_ROW;
+            v = real ? part_v[o] : -1;
+        }
+        distinct64(s, n, v, lane);
+    }
+    if (lane < k) {                                                // an empty slot (-inf, 0x7fffffff, -1): only under a broken v_off
+        top_s[q * k + lane] = s;
+        top_n[q * k + lane] = n;
+        top_v[q * k + lane] = n != SENT_ROW ? v : -1;
+    }
+}
+
+// tvid[t] = the videos of tile t's first and last row: the largest v in [0, n_videos) with v_off[v] <= row, so a v_off that breaks
+// its contract still gives videos in range
+__global__ void __launch_bounds__(256) tile_video_kernel(const int* __restrict__ v_off, int n_videos, long N, long n_tiles,
+                                                         int2* __restrict__ tvid) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_tiles) return;
+    int found[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const long n = e == 0 ? t * BN : (t * BN + BN < N ? t * BN + BN : N) - 1;
+        found[e] = video_search(v_off, n, 0, n_videos - 1);
+    }
+    tvid[t] = make_int2(found[0], found[1]);
+}
+
 // ---- one wave per frame row: 64 lanes x 8 channels
 template <typename T> __device__ __forceinline__ f8 ld_row8(const T* p) {
     if constexpr (sizeof(T) == 2) return ld8(p); else return ld8f(p);
+}
+template <> __device__ __forceinline__ f8 ld_row8<e4m3_t>(const e4m3_t* p) {               // 8 e4m3fn codes -> f32 (exact)
+    const uint2 u = *reinterpret_cast<const uint2*>(p);
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.x, true);
+    const auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.y, true);
+    f8 r;
+    r.v[0] = a[0]; r.v[1] = a[1]; r.v[2] = b[0]; r.v[3] = b[1]; r.v[4] = c[0]; r.v[5] = c[1]; r.v[6] = d[0]; r.v[7] = d[1];
+    return r;
+}
+
+// tan_moment_extent: one wave per hit walks outward from the peak row, EB rows per step (their loads in flight together), and stops
+// at the first row below the threshold: the cost follows the moment's length.  s(q, n): a lane's 8 products summed in element order,
+// then wave_sum; e4m3: (acc * v_scale[n]) * q_scale[q].  No atomics, no scratch.
+constexpr int EB = 4;
+template <typename T>
+__global__ void __launch_bounds__(256) moment_extent_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Q, long N, int k,
+                                                            const int* __restrict__ v_off, int n_videos,
+                                                            const float* __restrict__ top_s, const int* __restrict__ top_n,
+                                                            const int* __restrict__ top_v, float width,
+                                                            const float* __restrict__ q_scale, const float* __restrict__ v_scale,
+                                                            int* __restrict__ start, int* __restrict__ end) {
+    constexpr bool F8 = sizeof(T) == 1;
+    const long h = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (h >= Q * k) return;
+    const long q = h / k;
+    long p = top_n[h];
+    p = p < 0 ? 0 : (p >= N ? N - 1 : p);                          // memory safety only: hits outside the index are the caller's error
+    int v = top_v[h];
+    v = v < 0 ? 0 : (v >= n_videos ? n_videos - 1 : v);
+    long lo = v_off[v], hi = v_off[v + 1];                         // the video's rows [lo, hi), cut to the index and around p
+    lo = lo < 0 ? 0 : (lo > p ? p : lo);
+    hi = hi > N ? N : hi;
+    hi = hi < p + 1 ? p + 1 : hi;
+    const float thr = top_s[h] - width;
+    const f8 qv = ld_row8<T>(Tq + q * RC + lane * 8);
+    float qs = 1.0f;
+    if constexpr (F8) qs = q_scale[q];
+    auto score = [&](const f8& x, long n) {
+        float a = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a += x.v[i] * qv.v[i];
+        a = wave_sum(a);
+        if constexpr (F8) a = (a * v_scale[n]) * qs;
+        return a;
+    };
+    long s0 = p, e0 = p;
+    while (s0 > lo) {                                              // wave-uniform
+        const int nb = s0 - lo < EB ? (int)(s0 - lo) : EB;
+        f8 x[EB];
+#pragma unroll
+        for (int j = 0; j < EB; ++j) x[j] = ld_row8<T>(Vn + (s0 - 1 - (j < nb ? j : nb - 1)) * RC + lane * 8);
+        int ok = 0;
+        bool open = true;
+#pragma unroll
+        for (int j = 0; j < EB; ++j) {
+            open = open && j < nb && score(x[j], s0 - 1 - (j < nb ? j : nb - 1)) >= thr;
+            ok += open ? 1 : 0;
+        }
+        s0 -= ok;
+        if (ok < nb) break;
+    }
+    while (e0 + 1 < hi) {
+        const int nb = hi - 1 - e0 < EB ? (int)(hi - 1 - e0) : EB;
+        f8 x[EB];
+#pragma unroll
+        for (int j = 0; j < EB; ++j) x[j] = ld_row8<T>(Vn + (e0 + 1 + (j < nb ? j : nb - 1)) * RC + lane * 8);
+        int ok = 0;
+        bool open = true;
+#pragma unroll
+        for (int j = 0; j < EB; ++j) {
+            open = open && j < nb && score(x[j], e0 + 1 + (j < nb ? j : nb - 1)) >= thr;
+            ok += open ? 1 : 0;
+        }
+        e0 += ok;
+        if (ok < nb) break;
+    }
+    if (lane == 0) { start[h] = (int)s0; end[h] = (int)e0; }
 }
 template <typename T> __device__ __forceinline__ f8 unit_row(const T* row, int lane, bool normalize) {
     f8 x = ld_row8<T>(row + lane * 8);
@@ -480,34 +711,85 @@ __global__ void __launch_bounds__(256) quantize_rows_kernel(const T* __restrict_
 
 inline long n_index_tiles(long N) { return (N + BN - 1) / BN; }
 
-template <typename T>
-int rank_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair, int k, int splits, int* higher, int* ties,
-                float* top_s, int* top_n, void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
+// how many splits a sweep launches (`splits` = 0: chosen from Q and N) and the index tiles each one takes
+inline int n_splits(long Q, long N, int splits, long* tiles_per_split) {
     const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
     long want = splits > 0 ? splits : (512 + q_tiles - 1) / q_tiles;
     want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
     want = want > n_tiles ? n_tiles : want;
-    const long tps = (n_tiles + want - 1) / want;
-    const int ns = (int)((n_tiles + tps - 1) / tps);
+    *tiles_per_split = (n_tiles + want - 1) / want;
+    return (int)((n_tiles + *tiles_per_split - 1) / *tiles_per_split);
+}
+
+template <typename T>
+int rank_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair, int k, int splits, int* higher, int* ties,
+                float* top_s, int* top_n, void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
+    const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
+    long tps;
+    const int ns = n_splits(Q, N, splits, &tps);
     float* dscore = (float*)ws;
     float* part_s = dscore + (Q + 3) / 4 * 4;
     int* part_n = (int*)(part_s + (long)ns * Q * k);
     if (pair) {
         hipLaunchKernelGGL((rank_kernel<T, true>), dim3((unsigned)q_tiles), dim3(256), tile_bytes<T>(), st, (const T*)Tq, (const T*)Vn, Q, N,
-                           pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr, q_scale, v_scale);
+                           pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr, q_scale, v_scale, (const int2*)nullptr,
+                           (const int*)nullptr, (int*)nullptr);
         TAN_LAUNCH_CHECK();
     }
     static std::atomic<unsigned long long> lds_done{0};
     const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false>, sweep_lds<T>(), lds_done);
     if (attr != hipSuccess) return (int)attr;
     hipLaunchKernelGGL((rank_kernel<T, false>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), sweep_lds<T>(), st, (const T*)Tq,
-                       (const T*)Vn, Q, N, pair, k, tps, n_tiles, dscore, higher, ties, part_s, part_n, q_scale, v_scale);
+                       (const T*)Vn, Q, N, pair, k, tps, n_tiles, dscore, higher, ties, part_s, part_n, q_scale, v_scale,
+                       (const int2*)nullptr, (const int*)nullptr, (int*)nullptr);
     TAN_LAUNCH_CHECK();
     if (k > 0) {
         hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, Q, k, ns, top_s, top_n);
         TAN_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// ws: tvid [tiles rounded up to 2] int2, then the splits' lists (score, row, video)
+template <typename T>
+int video_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_off, int n_videos, int k, int splits, float* top_s,
+                 int* top_n, int* top_v, void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
+    long tps;
+    const int ns = n_splits(Q, N, splits, &tps);
+    const long n_tiles = n_index_tiles(N);
+    int2* tvid = (int2*)ws;
+    float* part_s = (float*)(tvid + (n_tiles + 1) / 2 * 2);
+    int* part_n = (int*)(part_s + (long)ns * Q * k);
+    int* part_v = part_n + (long)ns * Q * k;
+    hipLaunchKernelGGL(tile_video_kernel, dim3(cdiv(n_tiles, 256)), dim3(256), 0, st, v_off, n_videos, N, n_tiles, tvid);
+    TAN_LAUNCH_CHECK();
+    static std::atomic<unsigned long long> lds_done{0};
+    constexpr int lds = sweep_lds<T, true>();
+    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, true>, lds, lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((rank_kernel<T, false, true>), dim3((unsigned)((Q + BQ - 1) / BQ), (unsigned)ns), dim3(256), lds, st,
+                       (const T*)Tq, (const T*)Vn, Q, N, (const int*)nullptr, k, tps, n_tiles, (float*)nullptr, (int*)nullptr,
+                       (int*)nullptr, part_s, part_n, q_scale, v_scale, (const int2*)tvid, v_off, part_v);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, Q, k, ns, top_s,
+                       top_n, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int extent_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_off, int n_videos, int k, const float* top_s,
+                  const int* top_n, const int* top_v, float width, int* start, int* end, hipStream_t st,
+                  const float* q_scale = nullptr, const float* v_scale = nullptr) {
+    hipLaunchKernelGGL(moment_extent_kernel<T>, dim3(cdiv(Q * k, 4)), dim3(256), 0, st, (const T*)Tq, (const T*)Vn, Q, N, k, v_off,
+                       n_videos, top_s, top_n, top_v, width, q_scale, v_scale, start, end);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+inline bool video_sizes_ok(long Q, long N, int C, long n_videos, int k) {
+    return C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && n_videos >= 1 && n_videos <= N && k >= 1 && k <= KMAX &&
+           k <= n_videos;
 }
 
 }  // namespace
@@ -545,6 +827,55 @@ extern "C" int tan_rank_topk_e4m3(const void* Tq, const float* q_scale, const vo
     TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
     return rank_launch<e4m3_t>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, (hipStream_t)stream, q_scale,
                                v_scale);
+}
+
+extern "C" long tan_rank_topk_video_ws_bytes(long Q, long N, long n_videos, int k) {
+    if (!video_sizes_ok(Q, N, RC, n_videos, k)) return TAN_ERR_BAD_ARG;
+    const long ns = n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS;
+    return ((n_index_tiles(N) + 1) / 2 * 2) * 8 + ns * Q * k * 12;
+}
+
+extern "C" int tan_rank_topk_video(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos,
+                                   int k, int splits, float* top_score, int* top_row, int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && Vn && v_off && top_score && top_row && top_video && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16
+               ? video_launch<bf16_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, st)
+               : video_launch<float>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, st);
+}
+
+extern "C" int tan_rank_topk_video_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                                        const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_row,
+                                        int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && v_off && top_score && top_row && top_video && ws);
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
+    return video_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, (hipStream_t)stream,
+                                q_scale, v_scale);
+}
+
+extern "C" int tan_moment_extent(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos, int k,
+                                 const float* top_score, const int* top_row, const int* top_video, float width, int* start, int* end,
+                                 void* stream) {
+    TAN_REQUIRE(Tq && Vn && v_off && top_score && top_row && top_video && start && end && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && width >= 0.0f);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16
+               ? extent_launch<bf16_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end, st)
+               : extent_launch<float>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end, st);
+}
+
+extern "C" int tan_moment_extent_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                                      const int* v_off, long n_videos, int k, const float* top_score, const int* top_row,
+                                      const int* top_video, float width, int* start, int* end, void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && v_off && top_score && top_row && top_video && start && end);
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && width >= 0.0f);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0);
+    return extent_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end,
+                                 (hipStream_t)stream, q_scale, v_scale);
 }
 
 extern "C" int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* codes, float* scale, void* stream) {

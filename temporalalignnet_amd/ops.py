@@ -374,6 +374,84 @@ def rank_topk_e4m3(tq, q_scale, vn, v_scale, pair=None, k=0, *, splits=0, check_
     return higher, ties, top_s, top_r
 
 
+def rank_topk_video_ws_bytes(Q, N, n_videos, k):
+    n = _lib.lib().tan_rank_topk_video_ws_bytes(Q, N, n_videos, k)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_rank_topk_video_ws_bytes({Q}, {N}, {n_videos}, {k}): bad argument")
+    return n
+
+
+def _video_args(what, tq, vn, v_off, q_scale, v_scale):
+    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype
+    assert v_off.dtype == torch.int32 and v_off.dim() == 1 and v_off.numel() >= 2 and v_off.is_contiguous()
+    e4m3 = tq.dtype == torch.uint8
+    if (q_scale is not None) != e4m3 or (v_scale is not None) != e4m3:
+        raise TypeError(f"{what}: q_scale / v_scale go with uint8 e4m3 codes, and only with them")
+    if e4m3:
+        assert q_scale.shape == (tq.shape[0],) and v_scale.shape == (vn.shape[0],) and q_scale.is_contiguous() and v_scale.is_contiguous()
+    return e4m3
+
+
+def rank_topk_video(tq, vn, v_off, k, *, q_scale=None, v_scale=None, splits=0, check_v_off=False, out=None, ws=None):
+    """The k best DISTINCT videos per query (tan_rank_topk_video / _e4m3): tq [Q, 512], vn [N, 512], both bf16, both f32, or both
+    uint8 e4m3 codes with q_scale [Q] / v_scale [N]; v_off [n_videos + 1] int32 (device): each video's first row, then N.
+    Returns (top_score [Q, k] f32: the video's best score, top_row [Q, k] int32: the first index row that attains it,
+    top_video [Q, k] int32), by descending score, equal scores by ascending row.  splits: 0 = automatic; the result does not depend
+    on it.  check_v_off: verify on the host (one synchronisation) that v_off starts at 0, ends at N and strictly increases;
+    otherwise that is the caller's contract.  out / ws: caller-owned outputs (the same 3-tuple) and scratch (uint8,
+    >= rank_topk_video_ws_bytes) instead of fresh ones."""
+    e4m3 = _video_args("rank_topk_video", tq, vn, v_off, q_scale, v_scale)
+    Q, N, nv, dev = tq.shape[0], vn.shape[0], v_off.numel() - 1, tq.device
+    if check_v_off:
+        v = v_off.cpu()
+        if int(v[0]) != 0 or int(v[-1]) != N or not bool((v[1:] > v[:-1]).all()):
+            raise ValueError("rank_topk_video: v_off must start at 0, end at N and strictly increase")
+    if out is None:
+        out = (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev),
+               torch.empty(Q, k, dtype=torch.int32, device=dev))
+    top_s, top_r, top_v = out
+    L = _lib.lib()
+    need = L.tan_rank_topk_video_ws_bytes(Q, N, nv, k)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    if e4m3:
+        _lib.check(L.tan_rank_topk_video_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(v_off), nv, k,
+                                              splits, _f32(top_s), _ptr(top_r), _ptr(top_v), _ptr(ws), _stream()),
+                   "tan_rank_topk_video_e4m3")
+    else:
+        _lib.check(L.tan_rank_topk_video(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(v_off), nv, k, splits, _f32(top_s),
+                                         _ptr(top_r), _ptr(top_v), _ptr(ws), _stream()), "tan_rank_topk_video")
+    return top_s, top_r, top_v
+
+
+def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scale=None, v_scale=None, out=None):
+    """(start, end) int32 [Q, k]: for every hit of `rank_topk_video`'s lists, the contiguous run of index rows around top_row,
+    inside the hit's video, whose score is >= top_score - width -- global rows, inclusive (tan_moment_extent / _e4m3; the exact
+    definition is in include/tan_hip.h).  tq / vn / v_off / q_scale / v_scale as for `rank_topk_video`; width >= 0.
+    out: caller-owned (start, end) instead of fresh ones."""
+    e4m3 = _video_args("moment_extent", tq, vn, v_off, q_scale, v_scale)
+    Q, N, nv, dev = tq.shape[0], vn.shape[0], v_off.numel() - 1, tq.device
+    k = top_row.shape[1]
+    for t, dt in ((top_score, torch.float32), (top_row, torch.int32), (top_video, torch.int32)):
+        assert t.dtype == dt and t.shape == (Q, k) and t.is_contiguous()
+    if out is None:
+        out = (torch.empty(Q, k, dtype=torch.int32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev))
+    start, end = out
+    assert all(t.dtype == torch.int32 and t.shape == (Q, k) and t.is_contiguous() for t in out)
+    L = _lib.lib()
+    if e4m3:
+        _lib.check(L.tan_moment_extent_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(v_off), nv, k,
+                                            _f32(top_score), _ptr(top_row), _ptr(top_video), float(width), _ptr(start), _ptr(end),
+                                            _stream()), "tan_moment_extent_e4m3")
+    else:
+        _lib.check(L.tan_moment_extent(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(v_off), nv, k, _f32(top_score),
+                                       _ptr(top_row), _ptr(top_video), float(width), _ptr(start), _ptr(end), _stream()),
+                   "tan_moment_extent")
+    return start, end
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

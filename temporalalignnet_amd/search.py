@@ -14,14 +14,19 @@ sentence is ranked against all of it:
   * an e4m3 index (`build_index(dtype="e4m3")`, `VideoIndex.quantize`, `--index-dtype e4m3`) keeps a row as 512 OCP e4m3fn codes
     and one power-of-two f32 scale (include/tan_hip.h): 516 bytes per second of video instead of 1 KiB.  The query is quantised by
     the same kernel and `tan_rank_topk_e4m3` sweeps the codes.
+  * `search_moments`: neighbouring seconds of a video score almost alike, so the k best ROWS are a few videos' adjacent seconds.
+    `tan_rank_topk_video` ranks VIDEOS by their best second in the same matrix-free sweep, and `tan_moment_extent` measures how
+    far the matching moment extends around that second (`query --moments`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
+    python -m temporalalignnet_amd.search query ... --moments [--width 0.07] "crack two eggs" ...
 """
 from __future__ import annotations
 
 import argparse
 import sys
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -31,6 +36,9 @@ from .infer_align import PASSES_PER_CHUNK, WIN_FIELDS, _aligner, _prefetch, load
 
 TEMPERATURE = 0.07
 E4M3 = "e4m3"
+
+# one hit of `search_moments`: the video, the moment's first / last second (inclusive), the best second, and its score
+Moment = namedtuple("Moment", ("vid", "start", "end", "second", "score"))
 
 
 def _is_e4m3(dtype):
@@ -88,6 +96,14 @@ class VideoIndex:
     def __init__(self, feat, v_off, vids, scale=None):
         self.feat, self.v_off, self.vids, self.scale = feat, np.asarray(v_off, dtype=np.int64), list(vids), scale
         assert (scale is not None) == (feat.dtype == torch.uint8)
+        self._v_off_dev = None
+
+    @property
+    def v_off_device(self):
+        """v_off as int32 on feat's device, made on first use and kept (it is not part of the file format)."""
+        if self._v_off_dev is None:
+            self._v_off_dev = torch.from_numpy(self.v_off.astype(np.int32)).to(self.feat.device)
+        return self._v_off_dev
 
     @property
     def e4m3(self):
@@ -198,7 +214,35 @@ def search(index, model, embed_text, queries, k=10, splits=0):
     return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
 
 
-def main(argv=None):
+@torch.no_grad()
+def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, splits=0):
+    """Per query the k best DISTINCT videos of the corpus, [[Moment(vid, start, end, second, score)] * k] * len(queries), by
+    descending score (equal scores by index row).  `second` is where the sentence fits the video best and `score` its score, as
+    `search` defines it; [start, end] (seconds of the video, inclusive) is the contiguous run around `second` whose scores stay
+    >= score - width.  k is clamped to the number of videos and must lie in [1, 32].
+    The default width = 0.07 is one unit of the evaluation's logit score / 0.07: the seconds whose softmax-over-time weight is at
+    least e^-1 of the peak's.  That is a definition chosen here, not a measurement of where moments end."""
+    queries = list(queries)
+    if not queries:
+        return []
+    k = min(int(k), len(index.vids))
+    if not 1 <= k <= 32:
+        raise ValueError("search_moments: k must lie in [1, 32]")
+    if not width >= 0:
+        raise ValueError("search_moments: width must be >= 0")
+    tq = query_features(index, model, embed_text, queries)
+    tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
+    v_off = index.v_off_device
+    score, row, video = ops.rank_topk_video(tq, index.feat, v_off, k, splits=splits, **scales)
+    start, end = ops.moment_extent(tq, index.feat, v_off, score, row, video, width, **scales)
+    score = score.cpu().numpy()                                    # the one read-back: the int32 results travel together
+    row, video, start, end = torch.stack((row, video, start, end)).cpu().numpy()
+    first = index.v_off[video]
+    return [[Moment(index.vids[video[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
+                    int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
+
+
+def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name in ("index", "query"):
@@ -219,14 +263,32 @@ def main(argv=None):
     p = sub.choices["query"]
     p.add_argument("--index", required=True)
     p.add_argument("-k", type=int, default=10)
+    p.add_argument("--moments", action="store_true",
+                   help="the k best distinct videos, each as `sentence vid start end second score` (seconds of the video)")
+    p.add_argument("--width", type=float, default=None,
+                   help=f"with --moments: a moment extends while the score stays within this of its peak (default {TEMPERATURE})")
     p.add_argument("sentences", nargs="+")
+    return ap
+
+
+def parse_args(argv=None):
+    ap = _parser()
     a = ap.parse_args(argv)
+    if a.cmd == "query" and a.width is not None and not a.moments:
+        ap.error("--width needs --moments")
+    if a.cmd == "query" and a.width is not None and not a.width >= 0:
+        ap.error("--width must be >= 0")
+    if a.cmd == "index" and not 0 <= a.worker_id < a.num_workers:
+        ap.error("--worker-id must lie in [0, --num-workers)")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     from .infer_align import build_aligner, make_embed_text, read_corpus
     vocab = np.load(a.vocab)
     model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
     if a.cmd == "index":
-        if not 0 <= a.worker_id < a.num_workers:
-            ap.error("--worker-id must lie in [0, --num-workers)")
         corpus = read_corpus(a.feature_dir, a.asr_json, a.vlen_csv, a.worker_id, a.num_workers)
         idx = build_index(model, corpus, dtype={"bf16": torch.bfloat16, "fp32": torch.float32, "e4m3": E4M3}[a.index_dtype or a.dtype])
         idx.save(a.out)
@@ -235,6 +297,12 @@ def main(argv=None):
     from .word2vec_model import Word2VecTokenizer
     embed = make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab))
     idx = VideoIndex.load(a.index)
+    if a.moments:
+        width = TEMPERATURE if a.width is None else a.width
+        for sentence, hits in zip(a.sentences, search_moments(idx, model, embed, a.sentences, a.k, width)):
+            for m in hits:
+                print(f"{sentence}\t{m.vid}\t{m.start}\t{m.end}\t{m.second}\t{m.score:.6f}")
+        return 0
     for sentence, hits in zip(a.sentences, search(idx, model, embed, a.sentences, a.k)):
         for vid, sec, score in hits:
             print(f"{sentence}\t{vid}\t{sec}\t{score:.6f}")

@@ -1,12 +1,17 @@
 """Corpus sweep time: `ops.rank_topk` over a bf16 index against `ops.rank_topk_e4m3` over the e4m3 index of the same rows, one
 process, device events around each call, caller-owned outputs and scratch.  Prints one JSON line; `--out` also writes the table.
 
-    python tools/search_bench.py [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE] [--moments]
 
 Rows: seeded random unit rows, made in slices.  4 Mi rows are 4 GiB of bf16 and 2 GiB + 16 MiB of e4m3 codes and scales: both far
 beyond the 256 MB last-level cache, so every sweep streams its index from HBM.  Bytes per second count the index once per sweep
 (at Q <= 128, one query tile, that is all a sweep reads); `of_stream` relates them to the 6.29 TB/s streaming read the project has
-measured on this part.  The yardstick is the bf16 sweep of the same run."""
+measured on this part.  The yardstick is the bf16 sweep of the same run.
+
+--moments adds `ops.rank_topk_video` and `ops.moment_extent` (width 0.07) on the same rows and queries, for two `v_off` layouts:
+"corpus" (seeded video lengths 60..1200 seconds) and "one" (a single video of all rows, k = 1: every tile refills the candidate
+buffers of a video that is already listed).  `*_video_over_rows` is the video sweep's time over `rank_topk`'s in the same run -- the
+same loads and MFMA loop, so the ratio is what the video epilogue and the row -> video map cost."""
 import argparse
 import json
 import os
@@ -42,6 +47,34 @@ def timed(fn, warmup, reps):
     return float(np.median(ms)), float(min(ms))
 
 
+def video_layouts(N):
+    lens = np.random.default_rng(0).integers(60, 1201, size=N // 60 + 1)
+    cuts = np.concatenate([[0], np.cumsum(lens)])
+    corpus = np.concatenate([cuts[cuts < N], [N]])
+    return {"corpus": torch.from_numpy(corpus.astype(np.int32)).cuda(), "one": torch.tensor([0, N], dtype=torch.int32, device="cuda")}
+
+
+def moments_row(Q, N, k, idx, t_rows, a):
+    """idx: format -> (tq, vn, scale keywords); t_rows: format -> rank_topk's median ms in this run"""
+    row = {}
+    for name, v_off in video_layouts(N).items():
+        nv = v_off.numel() - 1
+        kk = min(k, nv)
+        ws = torch.empty(ops.rank_topk_video_ws_bytes(Q, N, nv, kk), dtype=torch.uint8, device="cuda")
+        out = (torch.empty(Q, kk, device="cuda"), torch.empty(Q, kk, dtype=torch.int32, device="cuda"),
+               torch.empty(Q, kk, dtype=torch.int32, device="cuda"))
+        ext = (torch.empty(Q, kk, dtype=torch.int32, device="cuda"), torch.empty(Q, kk, dtype=torch.int32, device="cuda"))
+        row[f"{name}_videos"], row[f"{name}_k"] = nv, kk
+        for fmt, (tq, vn, kw) in idx.items():
+            tv, _ = timed(lambda: ops.rank_topk_video(tq, vn, v_off, kk, out=out, ws=ws, **kw), a.warmup, a.reps)
+            te, _ = timed(lambda: ops.moment_extent(tq, vn, v_off, *out, 0.07, out=ext, **kw), a.warmup, a.reps)
+            row[f"{name}_{fmt}_video_ms"] = round(tv, 4)
+            row[f"{name}_{fmt}_video_over_rows"] = round(tv / t_rows[fmt], 3)
+            row[f"{name}_{fmt}_extent_ms"] = round(te, 4)
+            row[f"{name}_{fmt}_moment_rows"] = round(float((ext[1] - ext[0] + 1).float().mean()), 1)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4 * 2 ** 20)
@@ -50,6 +83,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--moments", action="store_true", help="also time rank_topk_video and moment_extent (see the module docstring)")
     a = ap.parse_args()
     N, k = a.rows, a.k
     v16 = torch.empty(N, 512, dtype=torch.bfloat16, device="cuda")
@@ -78,6 +112,9 @@ def main():
                      "bf16_of_stream": round(by16 / t16 * 1e-9 / STREAM_TBS, 3), "e4m3_of_stream": round(by8 / t8 * 1e-9 / STREAM_TBS, 3),
                      "bf16_TFLOPs": round(2.0 * Q * N * 512 / t16 * 1e-9, 1), "e4m3_TFLOPs": round(2.0 * Q * N * 512 / t8 * 1e-9, 1),
                      "top1_agree": round(agree, 4)})
+        if a.moments:
+            idx = {"bf16": (q16, v16, {}), "e4m3": (q8, v8, dict(q_scale=qs8, v_scale=s8))}
+            rows[-1].update(moments_row(Q, N, k, idx, {"bf16": t16, "e4m3": t8}, a))
     res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "stream_TBps": STREAM_TBS,
            "table": rows}
     if a.out:
@@ -85,10 +122,20 @@ def main():
         with open(a.out, "w") as fh:
             fh.write(f"# tools/search_bench.py --rows {N} -k {k}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
             fh.write(f"# index bytes per sweep: bf16 {N * 1024}, e4m3 {N * 516}; of_stream = bytes/s over {STREAM_TBS} TB/s\n")
-            cols = list(rows[0])
+            cols = [c for c in rows[0] if not c.startswith(("corpus_", "one_"))]
             fh.write(" ".join(f"{c:>15}" for c in cols) + "\n")
             for r in rows:
                 fh.write(" ".join(f"{r[c]:>15}" for c in cols) + "\n")
+            if a.moments:
+                fh.write("# --moments: rank_topk_video / moment_extent (width 0.07) per v_off layout; video_over_rows = video sweep ms over "
+                         "rank_topk ms above\n")
+                cols = ["layout", "fmt", "Q", "videos", "k", "video_ms", "video_over_rows", "extent_ms", "moment_rows"]
+                fh.write(" ".join(f"{c:>15}" for c in cols) + "\n")
+                for name in ("corpus", "one"):
+                    for fmt in ("bf16", "e4m3"):
+                        for r in rows:
+                            vals = [name, fmt, r["Q"], r[f"{name}_videos"], r[f"{name}_k"]] + [r[f"{name}_{fmt}_{c}"] for c in cols[5:]]
+                            fh.write(" ".join(f"{v:>15}" for v in vals) + "\n")
     print(json.dumps(res))
 
 

@@ -817,6 +817,47 @@ int tan_moment_extent(const void* Tq, const void* Vn, int dtype, long Q, long N,
 int tan_moment_extent_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
                            const int* v_off, long n_videos, int k, const float* top_score, const int* top_row,
                            const int* top_video, float width, int* start, int* end, void* stream);
+/* ---- ordered-sequence search: the k videos that show a list of steps in order, by their best order-preserving path ----
+ * A SEQUENCE is 1 to 32 consecutive rows of Tq [Qt, C] (its steps, in order): s_off [n_seq + 1] int32 on the device, s_off[0] == 0,
+ * s_off[n_seq] == Qt, strictly increasing, every difference in [1, 32].  A VIDEO v is the index rows [v_off[v], v_off[v + 1]) -- the
+ * v_off contract of tan_rank_topk_video.  For sequence p with steps q_0 .. q_{m-1} and video v with V rows, let
+ * x_i[t] = score(q_i, v_off[v] + t).  Then
+ *     D_0[t] = x_0[t];   D_i[t] = x_i[t] + M_{i-1}[t]   -- one f32 add, round to nearest, never contracted
+ *     M_i[t] = max_{t' <= t} D_i[t'];   path(p, v) = M_{m-1}[V - 1]
+ * -- tan_monotonic_decode's recurrence, word for word: non-decreasing seconds, equal seconds allowed, any V >= 1, also V < m.  The
+ * maximum is exact and each cell is one rounded add, so given the bits of x the bits of path do not depend on scan order, tiling or
+ * splits.  score(q, n) is the row sweep's: the MFMA chain of tan_rank_topk in the same K order (e4m3: (acc * v_scale[n]) *
+ * q_scale[q]); an MFMA element does not depend on where its row sits in a tile, so a video is tiled from its own first row.
+ * tan_sequence_topk (Tq, Vn, dtype, C == 512, alignment as tan_rank_topk):
+ *   top_score / top_video [n_seq, k], 1 <= k <= min(32, n_videos): per sequence the k videos with the largest path(p, v), by
+ *     descending path, equal paths by ascending video.  top_score (f32) is the path, top_video (int32) is v.
+ *   splits: how many workgroups share the index per four sequences; 0 = chosen from n_seq and N, at most 256.  A split takes WHOLE
+ *     videos (those whose first row falls into its row range).  Results are bit-identical from run to run and for every `splits`;
+ *     no float atomics.  Nothing of size Qt x N, n_seq x N or n_seq x n_videos is stored.
+ *   ws: tan_sequence_topk_ws_bytes(n_seq, N, k) bytes of scratch, 16-byte aligned: the splits' lists (at most 256 * n_seq * k * 8
+ *     bytes; the splits' video ranges are searched in v_off by the kernel); it does not depend on `splits`; -1 for invalid sizes.
+ * Another width, k outside [1, min(32, n_videos)], an unknown dtype, a NULL pointer, misalignment, negative splits, n_seq < 1, Qt
+ * outside [n_seq, 32 * n_seq], n_videos outside [1, N], N outside [1, 2^31): TAN_ERR_BAD_ARG, nothing launched.
+ * An s_off or v_off that breaks its contract is the CALLER's error: every lookup is clamped, nothing is read or written out of
+ * bounds, and the lists are unspecified (a slot may then hold score -inf, video 0x7fffffff).  The Python wrapper checks on request.
+ * tan_sequence_scores: for P hits, hits [P, 2] int32 = (sequence, video) on the device, x + x_off[h] <- x_i[t], i < m, t < V,
+ * row-major [m, V] f32 (x_off [P]: `long` element offsets on the device, x holds n_x elements) -- the scores with the bits
+ * tan_sequence_topk used (the same tile routine, the same K order).  A hit whose sequence or video lies outside the tables, or whose
+ * block would leave [0, n_x), is skipped.  One workgroup per hit, no atomics.  tan_monotonic_decode over such a block (one "video" of
+ * its tables per hit, the hit's m rows in step order) returns the path's seconds, and its `path` equals top_score bit for bit.
+ * The _e4m3 variants take the codes and scales of tan_rank_topk_e4m3.                                                              */
+long tan_sequence_topk_ws_bytes(long n_seq, long N, int k);
+int tan_sequence_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* s_off, long n_seq,
+                      const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_video, void* ws, void* stream);
+int tan_sequence_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                           const int* s_off, long n_seq, const int* v_off, long n_videos, int k, int splits, float* top_score,
+                           int* top_video, void* ws, void* stream);
+int tan_sequence_scores(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* s_off, long n_seq,
+                        const int* v_off, long n_videos, const int* hits, const long* x_off, long P, float* x, long n_x,
+                        void* stream);
+int tan_sequence_scores_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                             const int* s_off, long n_seq, const int* v_off, long n_videos, const int* hits, const long* x_off,
+                             long P, float* x, long n_x, void* stream);
 /* Clip pooling of test_retrieval_yc2 (:197-214).  stage: one stage of the video stack's output, window w's frame f at
  * stage + w * win_stride + f * 512 elements of `dtype` (win_stride >= T * 512, a multiple of 8); table [W, 3] int32 = (clip,
  * first_frame, n_frames) per window.  normalize != 0: every selected frame is L2-normalised (sim = 'cos').  sum [n_clips, 512] /

@@ -22,6 +22,9 @@
 // tan_rank_topk_video ranks VIDEOS (contiguous row ranges, v_off) by their best row with the same sweep (rank_kernel's VIDEO mode):
 // a candidate slot also holds its video, compaction keeps one entry per video (distinct64), and the merge folds the splits' lists the
 // same way.  tan_moment_extent then walks outward from each hit's best row while the score stays within `width` of the peak.
+// tan_sequence_topk ranks videos by the best ORDER-PRESERVING path of a sequence of up to 32 query rows (tan_decode.hip's recurrence
+// fused into the sweep: seq_kernel, which shares the load / MFMA routine tile_scores with rank_kernel), and tan_sequence_scores
+// writes the winners' step x second scores, with the sweep's bits, for tan_monotonic_decode to backtrack.
 //
 // tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
 // of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
@@ -148,6 +151,57 @@ __device__ __forceinline__ void stage_store(T* tile, int tid, const uint4 (&pre)
     }
 }
 
+// One 64-row index tile against a wave's 32 resident query columns: the load / MFMA loop every sweep of this file shares.  `pre` (and,
+// e4m3, `psc`) hold the tile's first K chunk on entry; the chunks stream through the two LDS buffers (one barrier per chunk), and
+// after each barrier next(kc) issues the loads that follow chunk kc -- this tile's next chunk or the next tile's first.  On return
+// acc[rt][r] is score(column lane & 31, tile row 32 rt + acc_row(r, lane)), for e4m3 already (acc * v_scale[n]) * q_scale[q].  An
+// element's MFMA chain and K order do not depend on the tile or on where its row sits in it.  All 256 threads must call it.
+template <typename T, typename Next>
+__device__ __forceinline__ void tile_scores(T* tile, float* sc, int tid, int lane, const uint4 (&pre)[4], const float& psc,
+                                            const typename Mma<T>::frag_t (&qf)[RC / Mma<T>::KS], float qs, f32x16 (&acc)[2],
+                                            Next&& next) {
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, KS = M::KS, NCH = RC / KC, SPC = KC / KS;
+    constexpr int TS = BN * LD;                                    // elements per tile buffer
+    constexpr bool F8 = sizeof(T) == 1;
+    acc_zero(acc[0]);
+    acc_zero(acc[1]);
+#pragma unroll
+    for (int kc = 0; kc < NCH; ++kc) {
+        T* cur = tile + (kc & 1) * TS;                             // NCH is even: the buffer alternates across tiles too
+        stage_store<T>(cur, tid, pre);
+        if constexpr (F8) {
+            // written before the last chunk's barrier, read after it; the next write comes after the next tile's first barrier,
+            // which no wave passes before every wave has left this tile's epilogue: one buffer is enough
+            if (kc == NCH - 1 && tid < BN) sc[tid] = psc;
+        }
+        __syncthreads();
+        next(kc);
+#pragma unroll
+        for (int ks = 0; ks < SPC; ++ks) {
+            const frag_t a0 = M::template load<true>(cur, LD, 0, ks * KS, lane);
+            const frag_t a1 = M::template load<true>(cur, LD, 32, ks * KS, lane);
+            M::mma(acc[0], a0, qf[kc * SPC + ks]);
+            M::mma(acc[1], a1, qf[kc * SPC + ks]);
+        }
+    }
+    if constexpr (F8) {
+        // a lane's 16 rows of a 32-row half are four runs of four: 8 g + 4 (lane >> 5) + 0..3.  Two f32 multiplies in this order
+        // (powers of two: exact), the same in the pair launch and the sweep.
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 s4 = *reinterpret_cast<const float4*>(sc + rt * 32 + 8 * g + 4 * (lane >> 5));
+                acc[rt][4 * g + 0] = (acc[rt][4 * g + 0] * s4.x) * qs;
+                acc[rt][4 * g + 1] = (acc[rt][4 * g + 1] * s4.y) * qs;
+                acc[rt][4 * g + 2] = (acc[rt][4 * g + 2] * s4.z) * qs;
+                acc[rt][4 * g + 3] = (acc[rt][4 * g + 3] * s4.w) * qs;
+            }
+    }
+}
+
 // PAIR = true : launch 1 (grid = query tiles); tile t of 2 holds the paired rows of the block's queries 64 t .. 64 t + 63
 // PAIR = false: launch 2 (grid = query tiles x splits)
 // q_scale / v_scale: the rows' scales, e4m3 only (the other instantiations do not read them)
@@ -169,7 +223,7 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
                                                    int* __restrict__ part_v) {
     typedef Mma<T> M;
     typedef typename M::frag_t frag_t;
-    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, KS = M::KS, NCH = RC / KC, SPC = KC / KS, NFR = RC / KS;
+    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, KS = M::KS, NCH = RC / KC, NFR = RC / KS;
     constexpr int TS = BN * LD;                                    // elements per tile buffer
     constexpr long ROWB = (long)RC * sizeof(T);
     constexpr bool F8 = sizeof(T) == 1;
@@ -279,42 +333,10 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
             }
         }
         f32x16 acc[2];
-        acc_zero(acc[0]);
-        acc_zero(acc[1]);
-#pragma unroll
-        for (int kc = 0; kc < NCH; ++kc) {
-            T* cur = tile + (kc & 1) * TS;                         // NCH is even: the buffer alternates across tiles too
-            stage_store<T>(cur, tid, pre);
-            if constexpr (F8) {
-                // written before the last chunk's barrier, read after it; the next write comes after the next tile's first barrier,
-                // which no wave passes before every wave has left this tile's epilogue: one buffer is enough
-                if (kc == NCH - 1 && tid < BN) sc[tid] = psc;
-            }
-            __syncthreads();
+        tile_scores<T>(tile, sc, tid, lane, pre, psc, qf, qs, acc, [&](int kc) {
             if (kc + 1 < NCH) issue(t, kc + 1);
             else if (t + 1 < t1) issue(t + 1, 0);
-#pragma unroll
-            for (int ks = 0; ks < SPC; ++ks) {
-                const frag_t a0 = M::template load<true>(cur, LD, 0, ks * KS, lane);
-                const frag_t a1 = M::template load<true>(cur, LD, 32, ks * KS, lane);
-                M::mma(acc[0], a0, qf[kc * SPC + ks]);
-                M::mma(acc[1], a1, qf[kc * SPC + ks]);
-            }
-        }
-        if constexpr (F8) {
-            // a lane's 16 rows of a 32-row half are four runs of four: 8 g + 4 (lane >> 5) + 0..3.  Two f32 multiplies in this order
-            // (powers of two: exact), the same in the pair launch and the sweep.
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 s4 = *reinterpret_cast<const float4*>(sc + rt * 32 + 8 * g + 4 * (lane >> 5));
-                    acc[rt][4 * g + 0] = (acc[rt][4 * g + 0] * s4.x) * qs;
-                    acc[rt][4 * g + 1] = (acc[rt][4 * g + 1] * s4.y) * qs;
-                    acc[rt][4 * g + 2] = (acc[rt][4 * g + 2] * s4.z) * qs;
-                    acc[rt][4 * g + 3] = (acc[rt][4 * g + 3] * s4.w) * qs;
-                }
-        }
+        });
         if (PAIR) {
             if (t == (wave >> 1)) {
                 const f32x16 a = (wave & 1) ? acc[1] : acc[0];
@@ -475,6 +497,183 @@ __global__ void __launch_bounds__(256) tile_video_kernel(const int* __restrict__
         found[e] = video_search(v_off, n, 0, n_videos - 1);
     }
     tvid[t] = make_int2(found[0], found[1]);
+}
+
+// ---- ordered-sequence search: videos ranked by the best order-preserving path of a sequence of steps (include/tan_hip.h) ----
+// A wave owns ONE sequence: its up to 32 steps are the wave's 32 resident query columns (padded columns are computed and ignored), a
+// workgroup of four waves owns four sequences.  A split is a contiguous range of WHOLE videos -- a path needs all of its video: the
+// index is cut into equal row ranges and a video goes to the split its first row falls in.  Every video is tiled from its own first
+// row by tile_scores, the loop rank_kernel runs; the tail rows of its last tile are masked to -inf.  A lane's 16 accumulators belong
+// to one step, so the wave writes its [32 steps][64 seconds] tile to LDS (pitch 65: both directions conflict-free up to the two
+// half-waves) and runs tan_monotonic_decode's recurrence with lanes over seconds: per step one LDS read, one add, a 6-round inclusive
+// max-scan, a max with the step's carry from the video's previous tile (lane i of `carry` holds step i's) and a readlane for the new
+// carry.  The maximum is exact and each cell is one rounded add, so the path's bits do not depend on the tiling.  A finished video
+// gives ONE candidate (path, video); the 64 candidates of a sequence live one per lane in registers, sort64 keeps the k best when they
+// are full and raises the threshold.  The splits' lists are folded by rank_merge_kernel (row = video: the order is total).
+// SCORES = true: tan_sequence_scores -- one workgroup per hit (sequence, video), all four waves hold the hit's sequence, and instead
+// of the scan wave w writes the steps i = w mod 4 of the tile to x (lanes over seconds: coalesced).  Same routine, same bits.
+constexpr int XS_LD = BN + 1;
+constexpr int XS_WAVE = 32 * XS_LD;
+template <typename T> constexpr int seq_lds() { return (tile_bytes<T>() + 15) / 16 * 16 + 4 * XS_WAVE * 4; }
+
+// the number of videos whose first row lies below row r (r >= 1): whatever v_off holds, a value in [1, n_videos]
+__device__ __forceinline__ int videos_below(const int* __restrict__ v_off, long r, int n_videos) {
+    return video_search(v_off, r - 1, 0, n_videos - 1) + 1;
+}
+
+template <typename T, bool SCORES>
+__global__ void __launch_bounds__(256) seq_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Qt, long N,
+                                                  const int* __restrict__ s_off, int n_seq, const int* __restrict__ v_off,
+                                                  int n_videos, int k, long rows_per_split, const float* __restrict__ q_scale,
+                                                  const float* __restrict__ v_scale, float* __restrict__ part_s,
+                                                  int* __restrict__ part_n, const int* __restrict__ hits, int n_hits,
+                                                  const long* __restrict__ x_off, float* __restrict__ x, long n_x) {
+#pragma clang fp contract(off)
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, NCH = RC / KC, NFR = RC / M::KS;
+    constexpr long ROWB = (long)RC * sizeof(T);
+    constexpr bool F8 = sizeof(T) == 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* tile = reinterpret_cast<T*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + 2 * BN * LD * sizeof(T));
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
+    float* xw = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16) + wave * XS_WAVE;
+
+    // the wave's sequence and the workgroup's videos [va, vb); every lookup is clamped
+    int p, va, vb;
+    if constexpr (SCORES) {
+        const int h = blockIdx.x;
+        p = hits[2 * h];
+        va = hits[2 * h + 1];
+        va = va < 0 ? 0 : (va >= n_videos ? n_videos - 1 : va);
+        vb = va + 1;
+    } else {
+        p = blockIdx.x * 4 + wave;
+        const long r0 = (long)blockIdx.y * rows_per_split, r1 = r0 + rows_per_split;
+        va = r0 <= 0 ? 0 : videos_below(v_off, r0, n_videos);
+        vb = r1 >= N ? n_videos : videos_below(v_off, r1, n_videos);
+    }
+    const bool pok = p >= 0 && p < n_seq;
+    p = p < 0 ? 0 : (p >= n_seq ? n_seq - 1 : p);
+    long q0 = s_off[p];
+    q0 = q0 < 0 ? 0 : (q0 >= Qt ? Qt - 1 : q0);
+    long m_l = (long)s_off[p + 1] - q0;
+    m_l = m_l > Qt - q0 ? Qt - q0 : m_l;
+    const int m = m_l < 1 ? 1 : (m_l > 32 ? 32 : (int)m_l);        // wave-uniform
+
+    frag_t qf[NFR];                                                // the sequence's steps, resident; columns >= m repeat the last step
+    const long qme = q0 + (col < m ? col : m - 1);
+    {
+        const T* qrow = Tq + qme * RC;
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(qrow, j, lane);
+    }
+    float qs = 1.0f, psc = 0.0f;
+    if constexpr (F8) qs = q_scale[qme];
+
+    long xo = 0;
+    if constexpr (SCORES) {
+        xo = x_off[blockIdx.x];
+        long lo = v_off[va], hi = v_off[va + 1];
+        lo = lo < 0 ? 0 : (lo > N ? N : lo);
+        hi = hi < lo ? lo : (hi > N ? N : hi);
+        if (!pok || xo < 0 || xo + (long)m * (hi - lo) > n_x) return;   // block-uniform: nothing is written outside x
+    }
+
+    // the tile under the MFMAs: video v, its rows [lo, hi) cut to the index, tile t of it
+    struct Cur { int v; long lo, hi, t; };
+    auto open = [&](int v) {
+        Cur c{v, 0, 0, 0};
+        if (v < vb) {
+            c.lo = v_off[v];
+            c.hi = v_off[v + 1];
+            c.lo = c.lo < 0 ? 0 : (c.lo > N ? N : c.lo);
+            c.hi = c.hi < c.lo ? c.lo : (c.hi > N ? N : c.hi);
+        }
+        return c;
+    };
+    uint4 pre[4];
+    auto issue = [&](const Cur& c, int kc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
+            const long n = c.lo + c.t * BN + row;
+            pre[i] = n < c.hi ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Vn) + n * ROWB + kc * 256 + c16 * 16)
+                              : make_uint4(0, 0, 0, 0);
+        }
+        if constexpr (F8) {
+            if (kc == NCH - 1 && tid < BN) {
+                const long n = c.lo + c.t * BN + tid;
+                psc = n < c.hi ? v_scale[n] : 0.0f;
+            }
+        }
+    };
+
+    float cs = -INFINITY, thr = -INFINITY, carry = -INFINITY;
+    int cn = SENT_ROW, fill = 0;                                   // fill, thr: wave-uniform
+
+    Cur cur = open(va);
+    if (cur.v < vb) issue(cur, 0);
+    while (cur.v < vb) {                                           // block-uniform
+        Cur nxt = cur;
+        if ((cur.t + 1) * BN < cur.hi - cur.lo) ++nxt.t; else nxt = open(cur.v + 1);
+        f32x16 acc[2];
+        tile_scores<T>(tile, sc, tid, lane, pre, psc, qf, qs, acc, [&](int kc) {
+            if (kc + 1 < NCH) issue(cur, kc + 1);
+            else if (nxt.v < vb) issue(nxt, 0);
+        });
+        // the wave's tile -> LDS as [step][second]; only this wave reads it back
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xw[col * XS_LD + rt * 32 + acc_row(r, lane)] = acc[rt][r];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        const long V = cur.hi - cur.lo, left = V - cur.t * BN;     // the tile's seconds [0, left) are the video's
+        if constexpr (SCORES) {
+            if (lane < left)
+                for (int i = wave; i < m; i += 4) x[xo + (long)i * V + cur.t * BN + lane] = xw[i * XS_LD + lane];
+        } else {
+            float mprev = 0.0f;
+            for (int i = 0; i < m; ++i) {
+                const float xi = lane < left ? xw[i * XS_LD + lane] : -INFINITY;
+                float d = i ? xi + mprev : xi;                     // D_i[t]: one add, not contracted
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {                 // inclusive max-scan over the tile's seconds
+                    const float l = __shfl_up(d, o, 64);
+                    if (lane >= o && l > d) d = l;
+                }
+                const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(carry), i));
+                d = c > d ? c : d;                                 // M_i[t]
+                mprev = d;
+                const float nc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), 63));
+                if (lane == i) carry = nc;
+            }
+            if (nxt.v != cur.v) {                                  // the video is finished: one candidate
+                const float path = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(carry), m - 1));
+                carry = -INFINITY;
+                if (V > 0 && path >= thr) {                        // wave-uniform
+                    if (lane == fill) { cs = path; cn = cur.v; }
+                    if (++fill == CAP) {
+                        sort64(cs, cn, lane);
+                        thr = __shfl(cs, k - 1, 64);
+                        if (lane >= k) { cs = -INFINITY; cn = SENT_ROW; }
+                        fill = k;
+                    }
+                }
+            }
+        }
+        cur = nxt;
+    }
+    if constexpr (!SCORES) {
+        sort64(cs, cn, lane);
+        if (pok && lane < k) {
+            const long o = ((long)blockIdx.y * n_seq + p) * k + lane;
+            part_s[o] = cs;
+            part_n[o] = cn;
+        }
+    }
 }
 
 // ---- one wave per frame row: 64 lanes x 8 channels
@@ -792,6 +991,55 @@ inline bool video_sizes_ok(long Q, long N, int C, long n_videos, int k) {
            k <= n_videos;
 }
 
+// how many splits the sequence sweep launches and the index rows each one covers (a video goes to the split of its first row)
+inline int n_seq_splits(long n_seq, long N, int splits, long* rows_per_split) {
+    const long blocks = (n_seq + 3) / 4;
+    long want = splits > 0 ? splits : (512 + blocks - 1) / blocks;
+    want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
+    want = want > n_index_tiles(N) ? n_index_tiles(N) : want;
+    *rows_per_split = (N + want - 1) / want;
+    return (int)((N + *rows_per_split - 1) / *rows_per_split);
+}
+
+inline bool seq_sizes_ok(long Qt, long N, int C, long n_seq, long n_videos) {
+    return C == RC && N >= 1 && N < (1L << 31) && n_seq >= 1 && n_seq < (1L << 29) && Qt >= n_seq && Qt <= 32 * n_seq && n_videos >= 1 &&
+           n_videos <= N;
+}
+
+// ws: the splits' lists (score, video)
+template <typename T>
+int seq_topk_launch(const void* Tq, const void* Vn, long Qt, long N, const int* s_off, long n_seq, const int* v_off, int n_videos, int k,
+                    int splits, float* top_s, int* top_v, void* ws, hipStream_t st, const float* q_scale = nullptr,
+                    const float* v_scale = nullptr) {
+    long rps;
+    const int ns = n_seq_splits(n_seq, N, splits, &rps);
+    float* part_s = (float*)ws;
+    int* part_n = (int*)(part_s + (long)ns * n_seq * k);
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)seq_kernel<T, false>, seq_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((seq_kernel<T, false>), dim3(cdiv(n_seq, 4), (unsigned)ns), dim3(256), seq_lds<T>(), st, (const T*)Tq,
+                       (const T*)Vn, Qt, N, s_off, (int)n_seq, v_off, n_videos, k, rps, q_scale, v_scale, part_s, part_n,
+                       (const int*)nullptr, 0, (const long*)nullptr, (float*)nullptr, 0L);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, st, part_s, part_n, n_seq, k, ns, top_s, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int seq_scores_launch(const void* Tq, const void* Vn, long Qt, long N, const int* s_off, long n_seq, const int* v_off, int n_videos,
+                      const int* hits, const long* x_off, long P, float* x, long n_x, hipStream_t st, const float* q_scale = nullptr,
+                      const float* v_scale = nullptr) {
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)seq_kernel<T, true>, seq_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((seq_kernel<T, true>), dim3((unsigned)P), dim3(256), seq_lds<T>(), st, (const T*)Tq, (const T*)Vn, Qt, N, s_off,
+                       (int)n_seq, v_off, n_videos, 0, 0L, q_scale, v_scale, (float*)nullptr, (int*)nullptr, hits, (int)P, x_off, x, n_x);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 }  // namespace tal
 
@@ -876,6 +1124,55 @@ extern "C" int tan_moment_extent_e4m3(const void* Tq, const float* q_scale, cons
     TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0);
     return extent_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end,
                                  (hipStream_t)stream, q_scale, v_scale);
+}
+
+extern "C" long tan_sequence_topk_ws_bytes(long n_seq, long N, int k) {
+    if (n_seq < 1 || n_seq >= (1L << 29) || N < 1 || N >= (1L << 31) || k < 1 || k > KMAX) return TAN_ERR_BAD_ARG;
+    const long ns = n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS;
+    return ns * n_seq * k * 8;
+}
+
+extern "C" int tan_sequence_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* s_off, long n_seq,
+                                 const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_video, void* ws,
+                                 void* stream) {
+    TAN_REQUIRE(Tq && Vn && s_off && v_off && top_score && top_video && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16
+               ? seq_topk_launch<bf16_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score, top_video, ws, st)
+               : seq_topk_launch<float>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score, top_video, ws, st);
+}
+
+extern "C" int tan_sequence_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                                      const int* s_off, long n_seq, const int* v_off, long n_videos, int k, int splits,
+                                      float* top_score, int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && s_off && v_off && top_score && top_video && ws);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
+    return seq_topk_launch<e4m3_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score, top_video, ws,
+                                   (hipStream_t)stream, q_scale, v_scale);
+}
+
+extern "C" int tan_sequence_scores(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* s_off, long n_seq,
+                                   const int* v_off, long n_videos, const int* hits, const long* x_off, long P, float* x, long n_x,
+                                   void* stream) {
+    TAN_REQUIRE(Tq && Vn && s_off && v_off && hits && x_off && x && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && P >= 1 && P < (1L << 31) && n_x >= 1);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)x_off % 8 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16 ? seq_scores_launch<bf16_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, st)
+                             : seq_scores_launch<float>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, st);
+}
+
+extern "C" int tan_sequence_scores_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N,
+                                        int C, const int* s_off, long n_seq, const int* v_off, long n_videos, const int* hits,
+                                        const long* x_off, long P, float* x, long n_x, void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && s_off && v_off && hits && x_off && x);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && P >= 1 && P < (1L << 31) && n_x >= 1);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)x_off % 8 == 0);
+    return seq_scores_launch<e4m3_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, (hipStream_t)stream,
+                                     q_scale, v_scale);
 }
 
 extern "C" int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* codes, float* scale, void* stream) {

@@ -452,6 +452,75 @@ def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scal
     return start, end
 
 
+def sequence_topk_ws_bytes(n_seq, N, k):
+    n = _lib.lib().tan_sequence_topk_ws_bytes(n_seq, N, k)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_sequence_topk_ws_bytes({n_seq}, {N}, {k}): bad argument")
+    return n
+
+
+def _sequence_args(what, tq, vn, s_off, v_off, q_scale, v_scale, check_offsets):
+    e4m3 = _video_args(what, tq, vn, v_off, q_scale, v_scale)
+    assert s_off.dtype == torch.int32 and s_off.dim() == 1 and s_off.numel() >= 2 and s_off.is_contiguous()
+    if check_offsets:
+        s, v = s_off.cpu(), v_off.cpu()
+        if int(s[0]) != 0 or int(s[-1]) != tq.shape[0] or not bool(((s[1:] - s[:-1] >= 1) & (s[1:] - s[:-1] <= 32)).all()):
+            raise ValueError(f"{what}: s_off must start at 0, end at Qt and grow by 1 to 32 per sequence")
+        if int(v[0]) != 0 or int(v[-1]) != vn.shape[0] or not bool((v[1:] > v[:-1]).all()):
+            raise ValueError(f"{what}: v_off must start at 0, end at N and strictly increase")
+    return e4m3
+
+
+def sequence_topk(tq, vn, s_off, v_off, k, *, q_scale=None, v_scale=None, splits=0, check_offsets=False, out=None, ws=None):
+    """The k videos that show each SEQUENCE of steps best in order (tan_sequence_topk / _e4m3; the path is defined in
+    include/tan_hip.h): tq [Qt, 512] holds the sequences' steps one after the other, s_off [n_seq + 1] int32 (device) each sequence's
+    first row, then Qt (1 to 32 steps each); vn / v_off / q_scale / v_scale as for `rank_topk_video`.
+    Returns (top_score [n_seq, k] f32: the path score, top_video [n_seq, k] int32), by descending path, equal paths by ascending
+    video.  splits: 0 = automatic; the result does not depend on it.  check_offsets: verify s_off and v_off on the host (one
+    synchronisation); otherwise they are the caller's contract.  out / ws: caller-owned outputs (the same 2-tuple) and scratch
+    (uint8, >= sequence_topk_ws_bytes) instead of fresh ones."""
+    e4m3 = _sequence_args("sequence_topk", tq, vn, s_off, v_off, q_scale, v_scale, check_offsets)
+    Qt, N, ns, nv, dev = tq.shape[0], vn.shape[0], s_off.numel() - 1, v_off.numel() - 1, tq.device
+    if out is None:
+        out = (torch.empty(ns, k, dtype=torch.float32, device=dev), torch.empty(ns, k, dtype=torch.int32, device=dev))
+    top_s, top_v = out
+    L = _lib.lib()
+    need = L.tan_sequence_topk_ws_bytes(ns, N, k)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    if e4m3:
+        _lib.check(L.tan_sequence_topk_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Qt, N, tq.shape[1], _ptr(s_off), ns,
+                                            _ptr(v_off), nv, k, splits, _f32(top_s), _ptr(top_v), _ptr(ws), _stream()),
+                   "tan_sequence_topk_e4m3")
+    else:
+        _lib.check(L.tan_sequence_topk(_ptr(tq), _ptr(vn), _dt(tq), Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, k, splits,
+                                       _f32(top_s), _ptr(top_v), _ptr(ws), _stream()), "tan_sequence_topk")
+    return top_s, top_v
+
+
+def sequence_scores(tq, vn, s_off, v_off, hits, x_off, x, *, q_scale=None, v_scale=None, check_offsets=False):
+    """x [n_x] f32 (caller-owned, returned): for every hit h of hits [P, 2] int32 = (sequence, video), the [m, V] block of step x
+    second scores at x[x_off[h]:], x_off [P] int64 -- the scores `sequence_topk` ranked by, bit for bit (tan_sequence_scores /
+    _e4m3).  Everything else as `sequence_topk`."""
+    e4m3 = _sequence_args("sequence_scores", tq, vn, s_off, v_off, q_scale, v_scale, check_offsets)
+    Qt, N, ns, nv = tq.shape[0], vn.shape[0], s_off.numel() - 1, v_off.numel() - 1
+    P = hits.shape[0]
+    assert hits.dtype == torch.int32 and hits.shape == (P, 2) and hits.is_contiguous()
+    assert x_off.dtype == torch.int64 and x_off.shape == (P,) and x_off.is_contiguous()
+    assert x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()
+    L = _lib.lib()
+    if e4m3:
+        _lib.check(L.tan_sequence_scores_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Qt, N, tq.shape[1], _ptr(s_off), ns,
+                                              _ptr(v_off), nv, _ptr(hits), _ptr(x_off), P, _f32(x), x.numel(), _stream()),
+                   "tan_sequence_scores_e4m3")
+    else:
+        _lib.check(L.tan_sequence_scores(_ptr(tq), _ptr(vn), _dt(tq), Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, _ptr(hits),
+                                         _ptr(x_off), P, _f32(x), x.numel(), _stream()), "tan_sequence_scores")
+    return x
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

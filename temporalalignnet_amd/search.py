@@ -17,10 +17,15 @@ sentence is ranked against all of it:
   * `search_moments`: neighbouring seconds of a video score almost alike, so the k best ROWS are a few videos' adjacent seconds.
     `tan_rank_topk_video` ranks VIDEOS by their best second in the same matrix-free sweep, and `tan_moment_extent` measures how
     far the matching moment extends around that second (`query --moments`).
+  * `search_sequences`: "which videos show these steps, in this order, and when?"  `tan_sequence_topk` scores every video of the
+    index by the best non-decreasing assignment of seconds to an ordered list of sentences -- `tan_monotonic_decode`'s path, fused
+    into the same matrix-free sweep -- and keeps the k best videos; `tan_sequence_scores` and the decode itself then give the
+    winners' seconds (`query --sequence`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --moments [--width 0.07] "crack two eggs" ...
+    python -m temporalalignnet_amd.search query ... --sequence "crack two eggs" "whisk them" "pour into the pan"
 """
 from __future__ import annotations
 
@@ -39,6 +44,9 @@ E4M3 = "e4m3"
 
 # one hit of `search_moments`: the video, the moment's first / last second (inclusive), the best second, and its score
 Moment = namedtuple("Moment", ("vid", "start", "end", "second", "score"))
+
+# one hit of `search_sequences`: the video, the second of every step (non-decreasing), and the path score
+SequenceHit = namedtuple("SequenceHit", ("vid", "seconds", "score"))
 
 
 def _is_e4m3(dtype):
@@ -242,6 +250,56 @@ def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, s
                     int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
 
 
+@torch.no_grad()
+def search_sequences(index, model, embed_text, sequences, k=10, splits=0):
+    """Per SEQUENCE (an ordered list of 1 to 32 sentences) the k videos of the corpus that show its steps best IN ORDER:
+    [[SequenceHit(vid, seconds, score)] * k] * len(sequences), by descending score (equal scores by video number).  `seconds` holds
+    one second of the video per step, non-decreasing (equal seconds allowed): the assignment with the largest summed score, ties to
+    the smallest last second, then the smallest second to last, as `align_corpus(decode="monotonic")` breaks them.  `score` is that
+    sum of the steps' stitched dual cosines (`search`'s score); / 0.07 gives the summed logit.  k is clamped to the number of
+    videos and must lie in [1, 32].  Two read-backs: the winning videos (to size the score blocks), then seconds and scores."""
+    sequences = [list(seq) for seq in sequences]
+    if not sequences:
+        return []
+    if any(not 1 <= len(seq) <= 32 for seq in sequences):
+        raise ValueError("search_sequences: a sequence holds 1 to 32 sentences")
+    k = min(int(k), len(index.vids))
+    if not 1 <= k <= 32:
+        raise ValueError("search_sequences: k must lie in [1, 32]")
+    dev = index.feat.device
+    m = np.array([len(seq) for seq in sequences], dtype=np.int64)
+    s_off = torch.from_numpy(np.concatenate([[0], np.cumsum(m)]).astype(np.int32)).to(dev)
+    tq = query_features(index, model, embed_text, [sentence for seq in sequences for sentence in seq])
+    tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
+    v_off = index.v_off_device
+    top_s, top_v = ops.sequence_topk(tq, index.feat, s_off, v_off, k, splits=splits, **scales)
+    video = top_v.cpu().numpy().astype(np.int64)                   # read-back 1: [n_seq, k] winners
+    # one [m, V] block of scores per hit, and the decode's tables: one "video" per hit, its m rows in step order
+    n_seq = len(sequences)
+    hm = np.repeat(m, k)
+    hv = (index.v_off[video + 1] - index.v_off[video]).reshape(-1)
+    x_off = np.concatenate([[0], np.cumsum(hm * hv)])
+    if x_off[-1] >= 2 ** 31:
+        raise ValueError("search_sequences: the winners' score blocks exceed the int32 decode tables; lower k or split the call")
+    first = np.concatenate([[0], np.cumsum(hm)])
+    hit_of_row = np.repeat(np.arange(n_seq * k), hm)
+    step = np.arange(first[-1]) - first[hit_of_row]
+    rows = np.stack((x_off[hit_of_row] + step * hv[hit_of_row], hv[hit_of_row]), 1)
+    vtab = np.stack((first[:-1], hm, np.concatenate([[0], np.cumsum(hv)])[:-1]), 1)
+    hits = np.stack((np.repeat(np.arange(n_seq), k), video.reshape(-1)), 1)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)          # noqa: E731
+    x = torch.empty(int(x_off[-1]), dtype=torch.float32, device=dev)
+    ops.sequence_scores(tq, index.feat, s_off, v_off, i32(hits), torch.from_numpy(x_off[:-1].copy()).to(dev), x, **scales)
+    ts = torch.empty(int(first[-1]), dtype=torch.int32, device=dev)
+    path = torch.empty(n_seq * k, dtype=torch.float32, device=dev)
+    ops.monotonic_decode(x, i32(rows), torch.arange(int(first[-1]), dtype=torch.int32, device=dev), i32(vtab), None,
+                         torch.empty(x.numel(), dtype=torch.int32, device=dev), torch.empty(int(hv.sum()), device=dev), ts, path)
+    back = torch.cat((top_s.reshape(-1).view(torch.int32), ts)).cpu().numpy()                  # read-back 2: scores and seconds
+    score, ts = back[:n_seq * k].view(np.float32), back[n_seq * k:]
+    return [[SequenceHit(index.vids[video[p, i]], tuple(int(t) for t in ts[first[p * k + i]:first[p * k + i + 1]]),
+                         float(score[p * k + i])) for i in range(k)] for p in range(n_seq)]
+
+
 def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -267,6 +325,9 @@ def _parser():
                    help="the k best distinct videos, each as `sentence vid start end second score` (seconds of the video)")
     p.add_argument("--width", type=float, default=None,
                    help=f"with --moments: a moment extends while the score stays within this of its peak (default {TEMPERATURE})")
+    p.add_argument("--sequence", action="store_true",
+                   help="the sentences are ONE ordered list of steps: the k videos that show them in order, each as "
+                        "`vid score t_0 ... t_{m-1}` (seconds of the video, non-decreasing)")
     p.add_argument("sentences", nargs="+")
     return ap
 
@@ -274,6 +335,10 @@ def _parser():
 def parse_args(argv=None):
     ap = _parser()
     a = ap.parse_args(argv)
+    if a.cmd == "query" and a.sequence and (a.moments or a.width is not None):
+        ap.error("--sequence does not go with --moments / --width")
+    if a.cmd == "query" and a.sequence and len(a.sentences) > 32:
+        ap.error("--sequence takes at most 32 sentences")
     if a.cmd == "query" and a.width is not None and not a.moments:
         ap.error("--width needs --moments")
     if a.cmd == "query" and a.width is not None and not a.width >= 0:
@@ -297,6 +362,10 @@ def main(argv=None):
     from .word2vec_model import Word2VecTokenizer
     embed = make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab))
     idx = VideoIndex.load(a.index)
+    if a.sequence:
+        for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
+            print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))
+        return 0
     if a.moments:
         width = TEMPERATURE if a.width is None else a.width
         for sentence, hits in zip(a.sentences, search_moments(idx, model, embed, a.sentences, a.k, width)):

@@ -15,7 +15,8 @@ for src in sorted(glob.glob(os.path.join(ROOT, "temporalalignnet_amd", "csrc", "
         lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1))
         get = lambda what: int((re.search(r"\.set " + re.escape(k) + r"\." + what + r", (\d+)", s) or [0, 0])[1])
         v, a, scratch = get("num_vgpr"), get("num_agpr"), get("private_seg_size")
-        name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().split("(")[0]
+        name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
+        name = name[:name.index(">(") + 1] if ">(" in name else name.split("(")[0]            # keep a template's arguments
         if flt and flt not in name:
             continue
         tot = max(v + a, 1)

@@ -2,6 +2,7 @@
 process, device events around each call, caller-owned outputs and scratch.  Prints one JSON line; `--out` also writes the table.
 
     python tools/search_bench.py [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE] [--moments]
+    python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
 
 Rows: seeded random unit rows, made in slices.  4 Mi rows are 4 GiB of bf16 and 2 GiB + 16 MiB of e4m3 codes and scales: both far
 beyond the 256 MB last-level cache, so every sweep streams its index from HBM.  Bytes per second count the index once per sweep
@@ -11,7 +12,12 @@ measured on this part.  The yardstick is the bf16 sweep of the same run.
 --moments adds `ops.rank_topk_video` and `ops.moment_extent` (width 0.07) on the same rows and queries, for two `v_off` layouts:
 "corpus" (seeded video lengths 60..1200 seconds) and "one" (a single video of all rows, k = 1: every tile refills the candidate
 buffers of a video that is already listed).  `*_video_over_rows` is the video sweep's time over `rank_topk`'s in the same run -- the
-same loads and MFMA loop, so the ratio is what the video epilogue and the row -> video map cost."""
+same loads and MFMA loop, so the ratio is what the video epilogue and the row -> video map cost.
+
+--sequences times `ops.sequence_topk` INSTEAD of the tables above, on the "corpus" layout, for n_seq x m in 1 x 8, 1 x 32, 8 x 32 and
+32 x 32 (random unit steps), bf16 and e4m3.  The yardsticks, in the same run on the same rows with Q = n_seq * m queries, are
+`ops.rank_topk_video` (the video sweep) and `ops.rank_topk` (the row sweep).  `finish_ms` is `ops.sequence_scores` plus
+`ops.monotonic_decode` for the n_seq * k winners (tables made once, outside the timing)."""
 import argparse
 import json
 import os
@@ -75,6 +81,61 @@ def moments_row(Q, N, k, idx, t_rows, a):
     return row
 
 
+SEQ_CASES = ((1, 8), (1, 32), (8, 32), (32, 32))
+
+
+def sequences_table(N, k, idx_of, a):
+    """idx_of(q f32 [Q, 512]) -> {format: (tq, vn, scale keywords)}"""
+    v_off = video_layouts(N)["corpus"]
+    v_host = v_off.cpu().numpy().astype(np.int64)
+    nv = v_off.numel() - 1
+    kk = min(k, nv)
+    i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).cuda()          # noqa: E731
+    rows = []
+    for n_seq, m in SEQ_CASES:
+        Q = n_seq * m
+        s_off = torch.arange(0, Q + 1, m, dtype=torch.int32, device="cuda")
+        for fmt, (tq, vn, kw) in idx_of(unit_rows(Q, (1 << 30) + Q)).items():
+            out = (torch.empty(n_seq, kk, device="cuda"), torch.empty(n_seq, kk, dtype=torch.int32, device="cuda"))
+            ws = torch.empty(ops.sequence_topk_ws_bytes(n_seq, N, kk), dtype=torch.uint8, device="cuda")
+            ts, _ = timed(lambda: ops.sequence_topk(tq, vn, s_off, v_off, kk, out=out, ws=ws, **kw), a.warmup, a.reps)
+            vout = (torch.empty(Q, kk, device="cuda"), torch.empty(Q, kk, dtype=torch.int32, device="cuda"),
+                    torch.empty(Q, kk, dtype=torch.int32, device="cuda"))
+            vws = torch.empty(ops.rank_topk_video_ws_bytes(Q, N, nv, kk), dtype=torch.uint8, device="cuda")
+            tv, _ = timed(lambda: ops.rank_topk_video(tq, vn, v_off, kk, out=vout, ws=vws, **kw), a.warmup, a.reps)
+            rout = (None, None, vout[0], vout[1])
+            rws = torch.empty(ops.rank_topk_ws_bytes(Q, N, kk), dtype=torch.uint8, device="cuda")
+            if kw:
+                tr, _ = timed(lambda: ops.rank_topk_e4m3(tq, kw["q_scale"], vn, kw["v_scale"], None, kk, out=rout, ws=rws), a.warmup, a.reps)
+            else:
+                tr, _ = timed(lambda: ops.rank_topk(tq, vn, None, kk, out=rout, ws=rws), a.warmup, a.reps)
+            # the winners' seconds: one [m, V] block per hit, then the decode over them
+            video = out[1].cpu().numpy().astype(np.int64).reshape(-1)
+            P = n_seq * kk
+            hv = v_host[video + 1] - v_host[video]
+            x_off = np.concatenate([[0], np.cumsum(m * hv)])
+            first = np.arange(P + 1) * m
+            hit_of_row = np.repeat(np.arange(P), m)
+            rows_t = i32(np.stack((x_off[hit_of_row] + (np.arange(P * m) - first[hit_of_row]) * hv[hit_of_row], hv[hit_of_row]), 1))
+            vtab = i32(np.stack((first[:-1], np.full(P, m), np.concatenate([[0], np.cumsum(hv)])[:-1]), 1))
+            hits = i32(np.stack((np.repeat(np.arange(n_seq), kk), video), 1))
+            xo = torch.from_numpy(x_off[:-1].copy()).cuda()
+            x = torch.empty(int(x_off[-1]), device="cuda")
+            order = torch.arange(P * m, dtype=torch.int32, device="cuda")
+            bp, run = torch.empty(x.numel(), dtype=torch.int32, device="cuda"), torch.empty(int(hv.sum()), device="cuda")
+            sec, path = torch.empty(P * m, dtype=torch.int32, device="cuda"), torch.empty(P, device="cuda")
+
+            def finish():
+                ops.sequence_scores(tq, vn, s_off, v_off, hits, xo, x, **kw)
+                ops.monotonic_decode(x, rows_t, order, vtab, None, bp, run, sec, path)
+            tf, _ = timed(finish, a.warmup, a.reps)
+            rows.append({"n_seq": n_seq, "m": m, "fmt": fmt, "Q": Q, "videos": nv, "k": kk, "sequence_ms": round(ts, 4),
+                         "video_sweep_ms": round(tv, 4), "row_sweep_ms": round(tr, 4), "seq_over_video": round(ts / tv, 3),
+                         "seq_over_rows": round(ts / tr, 3), "finish_ms": round(tf, 4), "hit_rows": int(hv.sum()),
+                         "path_equals_decode": bool(torch.equal(path.view(n_seq, kk), out[0]))})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4 * 2 ** 20)
@@ -84,6 +145,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--moments", action="store_true", help="also time rank_topk_video and moment_extent (see the module docstring)")
+    ap.add_argument("--sequences", action="store_true", help="time sequence_topk against the video and row sweeps instead (see the module docstring)")
     a = ap.parse_args()
     N, k = a.rows, a.k
     v16 = torch.empty(N, 512, dtype=torch.bfloat16, device="cuda")
@@ -94,6 +156,24 @@ def main():
         v16[r:r + SLICE] = x.to(torch.bfloat16)
         ops.quantize_rows_e4m3(x, v8[r:r + SLICE], s8[r:r + SLICE])
     del x
+    if a.sequences:
+        def idx_of(q):
+            q8, qs8 = ops.quantize_rows_e4m3(q)
+            return {"bf16": (q.to(torch.bfloat16), v16, {}), "e4m3": (q8, v8, dict(q_scale=qs8, v_scale=s8))}
+        rows = sequences_table(N, k, idx_of, a)
+        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "sequences": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --sequences --rows {N} -k {k}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
+                fh.write("# sequence_topk against rank_topk_video and rank_topk with Q = n_seq * m queries, same run, same rows; finish_ms = "
+                         "sequence_scores + monotonic_decode for the n_seq * k winners\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>18}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>18}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
     rows = []
     for Q in a.queries:
         q = unit_rows(Q, 1 << 30)

@@ -878,6 +878,36 @@ int tan_window_feat_acc(const void* feat, int dtype, long win_stride, const int*
                         long n_rows, void* stream);
 int tan_window_feat_final(const float* acc, const float* cnt, long n_rows, void* out, int out_dtype, void* stream);
 
+/* ---- two-stage search: the dual sweep's candidates rescored by the joint stack (`search.search_rerank`) ----
+ * tan_rerank_tail: one (score, second, confidence, alignability) per window from a pass of joint-stack outputs.
+ *   stage_last: the last joint stage after ln_joint_post_enc, [W, L, 512] of `dtype` (TAN_F32 or TAN_BF16), 16-byte aligned; window
+ *     w's frame f is row w * L + f, f < T, and its query is the text row w * L + T (the first text slot; L > T, 1 <= T <= 1024).
+ *   stage_head: joint stage index 2 in the same layout (what eval_zeroshot_align.py:186 reads; it may be stage_last itself), or NULL.
+ *   table: the pass's TAN_WIN_FIELDS rows, of which t and s0 are read; t is clamped to [0, T].
+ *   Per window, in f32, a lane of the wave owning channels 8 lane .. 8 lane + 7:
+ *     dot(a, b) = wave_sum(the lane's 8 products added in channel order)   -- wave_sum: tan_common.h's fixed 64-lane tree
+ *     cos[f] = dot(v_f, q) / (sqrtf(dot(v_f, v_f)) * sqrtf(dot(q, q)))     for f < t; no epsilon, as tan_model.py:116-117,136-137
+ *     out[4 w + 0] = max_f cos[f]                        (NaN cosines are passed over)
+ *     out[4 w + 1] = s0 + the FIRST f attaining it, an int32 stored as its bit pattern in the f32 slot
+ *     out[4 w + 2] = 1 / sum_f expf(cos[f] / 0.07f - max / 0.07f)          -- the maximum of the softmax over the t valid frames of
+ *                    cos / 0.07 (align_corpus's `confidence`); a lane adds its frames f = lane, lane + 64, .. in order, then wave_sum
+ *     out[4 w + 3] = dot(head_w, text row of stage_head) + head_b[0]       (tan_model.py:148), 0 when stage_head is NULL
+ *   t >= 1 is the caller's contract; t <= 0 gives (-inf, s0, 0, .).  sim [W, T] f32 or NULL: cos[f], -inf for f >= t.
+ *   Error against the exact cosine of the same stored rows: each of the three dots is a 512-term f32 accumulation, error at most
+ *   512 * 2^-23 * sum_i |a_i b_i| (bound (a) of DESIGN 3.12); the two square roots halve the norms' relative error and add 2^-24
+ *   each, the product and the division 2^-24 each.  With A = sum_i |v_i q_i| / (|v| |q|) <= 1:
+ *       |cos - exact| <= 2^-23 * (512 A + 516 |cos|)  <=  1028 * 2^-23 = 1.23e-4.
+ *   One workgroup per window; every stage row is read once, by one wave, with 16-byte loads; the four outputs leave in one 16-byte
+ *   store.  No atomics, no scratch: a window's bits depend on its rows alone, not on W or on the windows around it.
+ *   NULL stage_last / table / out, stage_head without head_w / head_b, misalignment, sizes outside the above: TAN_ERR_BAD_ARG.
+ * tan_rerank_select: score(q, i) = score[(q * P + i) * stride] (f32; stride = 4 reads tan_rerank_tail's out), 1 <= P <= 32,
+ *   1 <= k <= P, Q >= 1: out_idx [Q, k] int32 <- the k candidates i of query q with the largest score, by descending score, equal
+ *   scores by ascending i (candidates arrive in dual rank order, so ties keep it); a NaN score counts as -inf.  One wave per query
+ *   through the rank sweeps' sort64.  Bad sizes or NULL pointers: TAN_ERR_BAD_ARG.                                                  */
+int tan_rerank_tail(const void* stage_last, const void* stage_head, int dtype, int L, int T, const int* table, int W,
+                    const float* head_w, const float* head_b, float* out, float* sim, void* stream);
+int tan_rerank_select(const float* score, long Q, int P, long stride, int k, int* out_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "tan_mma.h"
+#include "tan_sort.h"
 
 namespace tal {
 namespace {
@@ -57,24 +58,6 @@ constexpr int BUF_BYTES = 4 * 32 * CAP * 8;
 constexpr int VID_BYTES = 4 * 32 * CAP * 4 + 2 * BN * 4;          // the video sweep: a video per candidate slot, and per row of two tiles
 template <typename T, bool VIDEO = false> constexpr int sweep_lds() {
     return (tile_bytes<T>() + 15) / 16 * 16 + BUF_BYTES + (VIDEO ? VID_BYTES : 0);
-}
-
-__device__ __forceinline__ bool better(float s, int n, float os, int on) { return s > os || (s == os && n < on); }
-
-// 64 (score, row) pairs, one per lane -> lane j holds rank j (score descending, equal scores by ascending row)
-__device__ __forceinline__ void sort64(float& s, int& n, int lane) {
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const float os = __shfl_xor(s, stride, 64);
-            const int on = __shfl_xor(n, stride, 64);
-            const bool lower = (lane & stride) == 0, desc = (lane & size) == 0;
-            const bool mine = better(s, n, os, on);
-            const bool keep = (lower == desc) ? mine : !mine;
-            if (!keep) { s = os; n = on; }
-        }
-    }
 }
 
 // sort64 with a payload: the entry's video

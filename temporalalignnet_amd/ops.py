@@ -557,6 +557,34 @@ def window_feat_final(acc, cnt, out):
     return out
 
 
+def rerank_tail(stage_last, stage_head, table, T, head_w, head_b, out, sim=None):
+    """out [W, 4] f32 <- per window of a joint pass (max cosine, window start + first arg-max as int32 bits, softmax maximum of
+    cos / 0.07, alignability logit) (tan_rerank_tail; the arithmetic is in include/tan_hip.h).  stage_last / stage_head [W * L, 512]
+    (f32 / bf16): the last joint stage and stage index 2 (or None, with head_w / head_b None: out[:, 3] = 0); table [W, 8] int32 the
+    pass's window table; sim [W, T] f32 or None <- every frame's cosine, -inf beyond the window's t."""
+    W = table.shape[0]
+    L = stage_last.shape[0] // W
+    assert stage_last.shape == (W * L, 512) and stage_last.is_contiguous() and table.dtype == torch.int32 and table.shape == (W, 8)
+    assert table.is_contiguous() and out.dtype == torch.float32 and out.shape == (W, 4) and out.is_contiguous()
+    assert stage_head is None or (stage_head.shape == stage_last.shape and stage_head.dtype == stage_last.dtype and stage_head.is_contiguous())
+    assert sim is None or (sim.dtype == torch.float32 and sim.shape == (W, T) and sim.is_contiguous())
+    _lib.check(_lib.lib().tan_rerank_tail(_ptr(stage_last), _ptr(stage_head), _dt(stage_last), L, T, _ptr(table), W, _f32(head_w),
+                                          _f32(head_b), _f32(out), _f32(sim), _stream()), "tan_rerank_tail")
+    return out
+
+
+def rerank_select(score, k, stride=1, out=None):
+    """out [Q, k] int32 <- per query the k of its P <= 32 candidates with the largest score, descending, equal scores by ascending
+    candidate (tan_rerank_select).  score [Q, P] f32, or [Q, P, stride] with the score in element 0 (rerank_tail's out: stride 4)."""
+    Q, P = score.shape[:2]
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == Q * P * stride
+    if out is None:
+        out = torch.empty(Q, k, dtype=torch.int32, device=score.device)
+    assert out.dtype == torch.int32 and out.shape == (Q, k) and out.is_contiguous()
+    _lib.check(_lib.lib().tan_rerank_select(_f32(score), Q, P, stride, k, _ptr(out), _stream()), "tan_rerank_select")
+    return out
+
+
 def clip_chunk():
     """elements per chunk of the gradient-clipping tables (tan_clip_chunk)"""
     return int(_lib.lib().tan_clip_chunk())

@@ -21,11 +21,17 @@ sentence is ranked against all of it:
     index by the best non-decreasing assignment of seconds to an ordered list of sentences -- `tan_monotonic_decode`'s path, fused
     into the same matrix-free sweep -- and keeps the k best videos; `tan_sequence_scores` and the decode itself then give the
     winners' seconds (`query --sequence`).
+  * `search_rerank`: two stages.  The dual sweep (`tan_rank_topk_video`) proposes `pool` videos per sentence; one 64-second window
+    around each candidate's best second is cut out of the index's STEM store (`build_index(keep_stem=True)`: video_pre_proj of
+    every second, the part of the video input that depends on neither window nor text), run through the joint stack
+    (`TemporalAligner.joint_from_stem`) and reduced by `tan_rerank_tail` to the joint cosine, the second the joint encoder picks,
+    its softmax confidence and the alignability logit; `tan_rerank_select` orders the candidates (`query --rerank`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --moments [--width 0.07] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --sequence "crack two eggs" "whisk them" "pour into the pan"
+    python -m temporalalignnet_amd.search index ... --keep-stem;  ... query ... --rerank [--pool 32] "crack two eggs" ...
 """
 from __future__ import annotations
 
@@ -37,7 +43,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .infer_align import PASSES_PER_CHUNK, WIN_FIELDS, _aligner, _prefetch, load_packed
+from .infer_align import JOINT_MAX_LEN, PASSES_PER_CHUNK, WIN_FIELDS, _aligner, _prefetch, load_packed
 
 TEMPERATURE = 0.07
 E4M3 = "e4m3"
@@ -47,6 +53,11 @@ Moment = namedtuple("Moment", ("vid", "start", "end", "second", "score"))
 
 # one hit of `search_sequences`: the video, the second of every step (non-decreasing), and the path score
 SequenceHit = namedtuple("SequenceHit", ("vid", "seconds", "score"))
+
+# one hit of `search_rerank`: the video, the second / cosine / softmax confidence / alignability logit (None without the head) of the
+# joint encoder on the window around the dual encoder's best second, and that second and its dual score
+Reranked = namedtuple("Reranked", ("vid", "second", "score", "confidence", "alignability", "dual_second", "dual_score"))
+RERANK_TEXT_SLOTS = 8           # a rerank window holds one sentence; `align_corpus` pads the text side to multiples of 8
 
 
 def _is_e4m3(dtype):
@@ -99,11 +110,16 @@ def _index_chunks(videos, seq_len, windows_per_pass):
 
 class VideoIndex:
     """feat [sum vlen, 512] (device, bf16 or f32): one row per second; v_off [n_videos + 1]: each video's first row; vids.
-    An e4m3 index holds feat as uint8 codes and scale [sum vlen] f32, one power of two per row; scale is None otherwise."""
+    An e4m3 index holds feat as uint8 codes and scale [sum vlen] f32, one power of two per row; scale is None otherwise.
+    stem [sum vlen, 512] (bf16 or f32, the model's compute dtype) or None: `TemporalAligner.video_stem` of every second, what
+    `search_rerank` cuts its windows from.  A bf16 stem adds 1 KiB per second: an e4m3 index with a stem is 516 + 1024 bytes per
+    second, a bf16 one 2 KiB."""
 
-    def __init__(self, feat, v_off, vids, scale=None):
+    def __init__(self, feat, v_off, vids, scale=None, stem=None):
         self.feat, self.v_off, self.vids, self.scale = feat, np.asarray(v_off, dtype=np.int64), list(vids), scale
+        self.stem = stem
         assert (scale is not None) == (feat.dtype == torch.uint8)
+        assert stem is None or (stem.shape == (feat.shape[0], 512) and stem.dtype in (torch.bfloat16, torch.float32))
         self._v_off_dev = None
 
     @property
@@ -118,11 +134,11 @@ class VideoIndex:
         return self.scale is not None
 
     def quantize(self):
-        """The e4m3 index of this bf16 / f32 one (tan_quantize_rows_e4m3); an e4m3 index is returned as it is."""
+        """The e4m3 index of this bf16 / f32 one (tan_quantize_rows_e4m3), with the same stem; an e4m3 index is returned as it is."""
         if self.e4m3:
             return self
         codes, scale = ops.quantize_rows_e4m3(self.feat.contiguous())
-        return VideoIndex(codes, self.v_off, self.vids, scale)
+        return VideoIndex(codes, self.v_off, self.vids, scale, self.stem)
 
     def __len__(self):
         return int(self.feat.shape[0])
@@ -134,10 +150,14 @@ class VideoIndex:
         return v, rows - self.v_off[v]
 
     def save(self, path):
-        """One .npz of plain arrays (bf16 rows as their uint16 bit patterns; e4m3 rows as uint8 codes plus `scale`)."""
+        """One .npz of plain arrays (bf16 rows as their uint16 bit patterns; e4m3 rows as uint8 codes plus `scale`; `stem`, bf16 as
+        uint16 bits too, only when the index has one: without it the file is what it was before stems existed)."""
         f = self.feat.cpu()
         bf16 = f.dtype == torch.bfloat16
         more = dict(scale=self.scale.cpu().numpy()) if self.e4m3 else {}
+        if self.stem is not None:
+            st = self.stem.cpu().contiguous()
+            more["stem"] = st.view(torch.int16).numpy().view(np.uint16) if st.dtype == torch.bfloat16 else st.numpy()
         with open(path, "wb") as fh:
             np.savez(fh, feat=(f.view(torch.int16).numpy().view(np.uint16) if bf16 else f.numpy()), bf16=np.array(bf16),
                      e4m3=np.array(self.e4m3), v_off=self.v_off, vids=np.array(self.vids, dtype=np.str_), **more)
@@ -148,25 +168,35 @@ class VideoIndex:
             f = torch.from_numpy(z["feat"].view(np.int16)).view(torch.bfloat16) if bool(z["bf16"]) else torch.from_numpy(z["feat"])
             e4m3 = "e4m3" in z.files and bool(z["e4m3"])                  # files written before the e4m3 format have no such key
             scale = torch.from_numpy(z["scale"]).to(device).contiguous() if e4m3 else None
-            return cls(f.to(device).contiguous(), z["v_off"], [str(v) for v in z["vids"]], scale)
+            stem = None
+            if "stem" in z.files:                                         # uint16: bf16 bit patterns
+                st = z["stem"]
+                stem = torch.from_numpy(st.view(np.int16)).view(torch.bfloat16) if st.dtype == np.uint16 else torch.from_numpy(st)
+                stem = stem.to(device).contiguous()
+            return cls(f.to(device).contiguous(), z["v_off"], [str(v) for v in z["vids"]], scale, stem)
 
 
 @torch.no_grad()
-def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfloat16):
+def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfloat16, keep_stem=False):
     """`videos`: iterable of {'vid', 'video' [vlen, Dv] (array / tensor) or a callable that reads it (then 'vlen' is required)} --
     `infer_align.read_corpus` items work as they are.  Every second of every video gets one row (see the module docstring); the rows
     do not depend on how the windows are cut into passes.  dtype: torch.bfloat16, torch.float32, or "e4m3" (torch.float8_e4m3fn):
-    each chunk's rows are finished in f32 and quantised at once; only codes and scales are kept."""
+    each chunk's rows are finished in f32 and quantised at once; only codes and scales are kept.
+    keep_stem: also keep `model.video_stem` of every second (`VideoIndex.stem`, in the model's compute dtype: 1 KiB per second in
+    bf16, so an e4m3 index with a stem is 516 + 1024 bytes per second) for `search_rerank`.  A second is projected once per chunk,
+    not once per covering window; feat, scale, v_off and vids are what they are without the option."""
     e4m3 = _is_e4m3(dtype)
     net = _aligner(model)
     device = torch.device("cuda", torch.cuda.current_device())
     T = seq_len
-    feats, scales, vlens, vids = [], [], [], []
+    feats, scales, stems, vlens, vids = [], [], [], [], []
     no_text = torch.zeros(1, 8, device=device)
     for ch in _prefetch(_index_chunks(videos, seq_len, windows_per_pass), device):
         n_rows = int(ch.v_off[-1])
         acc = torch.zeros(n_rows, 512, device=device)
         cnt = torch.zeros(n_rows, device=device)
+        if keep_stem:
+            stems.append(net.video_stem(ch.video))
         for p0, p1 in ch.passes:
             W, tab = p1 - p0, ch.table_d[p0:p1]
             vid = torch.empty(W, T, ch.video.shape[1], dtype=ch.video.dtype, device=device)
@@ -186,7 +216,8 @@ def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfl
         vids += [it.get("vid") for it in ch.items]
     if not feats:
         raise ValueError("build_index: no videos")
-    return VideoIndex(torch.cat(feats, 0), np.concatenate([[0], np.cumsum(vlens)]), vids, torch.cat(scales, 0) if e4m3 else None)
+    return VideoIndex(torch.cat(feats, 0), np.concatenate([[0], np.cumsum(vlens)]), vids, torch.cat(scales, 0) if e4m3 else None,
+                      torch.cat(stems, 0) if keep_stem else None)
 
 
 @torch.no_grad()
@@ -300,6 +331,114 @@ def search_sequences(index, model, embed_text, sequences, k=10, splits=0):
                          float(score[p * k + i])) for i in range(k)] for p in range(n_seq)]
 
 
+def rerank_window(sec, vlen, seq_len=64):
+    """(s0, t): the window `search_rerank` gives a candidate whose best dual second is `sec` in a video of `vlen` seconds -- seq_len
+    seconds centred on `sec` (sec - seq_len // 2 first), moved inside the video where it would stick out, the whole video when it is
+    shorter than a window."""
+    s0 = min(max(int(sec) - seq_len // 2, 0), max(int(vlen) - seq_len, 0))
+    return s0, min(seq_len, int(vlen) - s0)
+
+
+def _rerank_table(v_off, d_row, d_video, T):
+    """One window per (query, candidate) of `rank_topk_video`'s [Q, pool] lists, on the device: TAN_WIN_FIELDS rows (vrow, t, krow = q,
+    k = 1, s0, vlen, 0, 0) with `rerank_window`'s arithmetic."""
+    Q, pool = d_row.shape
+    v = d_video.reshape(-1).long()
+    first = v_off[v]
+    vlen = v_off[v + 1] - first
+    s0 = torch.minimum((d_row.reshape(-1) - first - T // 2).clamp(min=0), (vlen - T).clamp(min=0))
+    t = torch.clamp(vlen - s0, max=T)
+    qn = torch.arange(Q, dtype=torch.int32, device=d_row.device).repeat_interleave(pool)
+    zero = torch.zeros_like(qn)
+    return torch.stack((first + s0, t, qn, zero + 1, s0, vlen, zero, zero), 1).to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, windows_per_pass=256, splits=0, return_sim=False):
+    """Two-stage search.  Per query the `pool` best distinct videos of the dual sweep (`search_moments`' candidates: the same
+    `tan_rank_topk_video` call), each rescored by the joint encoder on ONE window of `seq_len` seconds around its best dual second
+    (`rerank_window`), and the k best of them: [[Reranked(vid, second, score, confidence, alignability, dual_second, dual_score)]
+    * k] * len(queries), by descending `score`, equal scores by dual rank.
+      score         the largest cosine between the sentence's joint output and a frame's, last joint stage (/ 0.07: the logit)
+      second        the first second of the video that attains it
+      confidence    the maximum of the softmax over the window's seconds of cosine / 0.07 (`align_corpus`'s confidence)
+      alignability  binary_head on the sentence's joint output of stage index 2 (tan_model.py:148, eval_zeroshot_align.py:186):
+                    the model's "is this sentence visible at all" logit; None for a model without the head
+      dual_second / dual_score   what `search_moments` reports as second / score
+    That the order key is the joint cosine ALONE is a definition chosen here; it is not the evaluation's mean of the dual and joint
+    similarities (eval_zeroshot_align.py:197-201).  The position offset of every window is 0 (`joint_from_stem`).
+    The index needs a stem (`build_index(keep_stem=True)`).  pool is clamped to the number of videos and must lie in [1, 32]; k is
+    clamped to the number of videos too, 1 <= k <= pool.  The Q * pool windows run in passes of `windows_per_pass`; one read-back.
+    return_sim: also return every window's cosines, (hits, sim [Q, pool, seq_len] f32, candidates in dual rank order, -inf beyond
+    a window's seconds), a second read-back."""
+    net = _aligner(model)
+    if index.stem is None:
+        raise ValueError("search_rerank: the index has no stem store (build_index(..., keep_stem=True) / index --keep-stem)")
+    head = bool(net.use_alignability_head)
+    if head and net.num_decoder_layers < 3:
+        raise ValueError("the alignability score reads joint stage index 2 (eval_zeroshot_align.py:186): >= 3 decoder layers")
+    queries = list(queries)
+    if not queries:
+        return ([], np.zeros((0, 0, seq_len), np.float32)) if return_sim else []
+    n_videos = len(index.vids)
+    pool, k = min(int(pool), n_videos), min(int(k), n_videos)
+    if not 1 <= pool <= 32:
+        raise ValueError("search_rerank: pool must lie in [1, 32]")
+    if not 1 <= k <= pool:
+        raise ValueError("search_rerank: k must lie in [1, pool]")
+    T, Kp = int(seq_len), RERANK_TEXT_SLOTS
+    if not 1 <= T <= JOINT_MAX_LEN[net.compute_dtype] - Kp:
+        raise ValueError(f"search_rerank: seq_len must lie in [1, {JOINT_MAX_LEN[net.compute_dtype] - Kp}]")
+    if windows_per_pass < 1:
+        raise ValueError("search_rerank: windows_per_pass must be >= 1")
+    dev, Q = index.feat.device, len(queries)
+    # stage 1: the dual sweep, exactly as search_moments runs it
+    tq = query_features(index, model, embed_text, queries)
+    tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
+    v_off = index.v_off_device
+    d_score, d_row, d_video = ops.rank_topk_video(tq, index.feat, v_off, pool, splits=splits, **scales)
+    table = _rerank_table(v_off, d_row, d_video, T)
+    # stage 2: the joint stack over the stem windows, reduced per pass
+    emb = embed_text(queries).to(dev).float().reshape(Q, -1).contiguous()
+    net._ensure_flat()
+    w_head, b_head = (net._f("binary_head.weight").view(-1), net._f("binary_head.bias")) if head else (None, None)
+    n_win, Sd = Q * pool, net.num_decoder_layers
+    out = torch.empty(n_win, 4, device=dev)
+    sim = torch.empty(n_win, T, device=dev) if return_sim else None
+    for p0 in range(0, n_win, windows_per_pass):
+        p1 = min(p0 + windows_per_pass, n_win)
+        W, tab = p1 - p0, table[p0:p1]
+        win = torch.empty(W, T, 512, dtype=index.stem.dtype, device=dev)
+        vm = torch.empty(W, T, dtype=torch.bool, device=dev)
+        txt = torch.empty(W, Kp, emb.shape[1], device=dev)
+        tm = torch.empty(W, Kp, dtype=torch.bool, device=dev)
+        ops.window_pack(index.stem, emb, tab, T, Kp, win, vm, txt, tm)
+        ej = net.joint_from_stem(win, vm, txt, tm)
+        ops.rerank_tail(ej.stage(Sd - 1), ej.stage(2) if head else None, tab, T, w_head, b_head, out[p0:p1],
+                        sim[p0:p1] if return_sim else None)
+        net._release_ws(ej)
+    order = ops.rerank_select(out.view(Q, pool, 4), k, stride=4)
+    # the one read-back: f32 results as their bit patterns next to the int32 ones
+    back = torch.cat((out.view(torch.int32).reshape(-1), order.reshape(-1), d_score.view(torch.int32).reshape(-1), d_row.reshape(-1),
+                      d_video.reshape(-1))).cpu().numpy()
+    cut = np.cumsum([0, n_win * 4, Q * k, n_win, n_win, n_win])
+    res, order, d_score, d_row, d_video = (back[a:b] for a, b in zip(cut[:-1], cut[1:]))
+    res, order = res.reshape(Q, pool, 4), order.reshape(Q, k)
+    d_score, d_row, d_video = d_score.view(np.float32).reshape(Q, pool), d_row.reshape(Q, pool), d_video.reshape(Q, pool)
+    resf = res.view(np.float32)
+    hits = []
+    for q in range(Q):
+        row = []
+        for i in order[q]:
+            vnum = int(d_video[q, i])
+            row.append(Reranked(index.vids[vnum], int(res[q, i, 1]), float(resf[q, i, 0]), float(resf[q, i, 2]),
+                                float(resf[q, i, 3]) if head else None, int(d_row[q, i] - index.v_off[vnum]), float(d_score[q, i])))
+        hits.append(row)
+    if return_sim:
+        return hits, sim.view(Q, pool, T).cpu().numpy()
+    return hits
+
+
 def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -316,6 +455,8 @@ def _parser():
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("--index-dtype", choices=("bf16", "fp32", "e4m3"), default=None,
                    help="row format of the index (default: --dtype); e4m3: 516 bytes per second instead of 1 KiB")
+    p.add_argument("--keep-stem", action="store_true",
+                   help="also keep video_pre_proj of every second (what `query --rerank` needs): + 1 KiB per second in bf16")
     p.add_argument("--worker-id", type=int, default=0)
     p.add_argument("--num-workers", type=int, default=1)
     p = sub.choices["query"]
@@ -328,6 +469,10 @@ def _parser():
     p.add_argument("--sequence", action="store_true",
                    help="the sentences are ONE ordered list of steps: the k videos that show them in order, each as "
                         "`vid score t_0 ... t_{m-1}` (seconds of the video, non-decreasing)")
+    p.add_argument("--rerank", action="store_true",
+                   help="two stages: the --pool best distinct videos of the dual sweep rescored by the joint encoder, the k best as "
+                        "`sentence vid second score confidence alignability dual_second dual_score` (needs index --keep-stem)")
+    p.add_argument("--pool", type=int, default=None, help="with --rerank: candidates per sentence, 1 to 32 (default 32)")
     p.add_argument("sentences", nargs="+")
     return ap
 
@@ -339,6 +484,12 @@ def parse_args(argv=None):
         ap.error("--sequence does not go with --moments / --width")
     if a.cmd == "query" and a.sequence and len(a.sentences) > 32:
         ap.error("--sequence takes at most 32 sentences")
+    if a.cmd == "query" and a.rerank and (a.sequence or a.moments):
+        ap.error("--rerank does not go with --sequence / --moments")
+    if a.cmd == "query" and a.pool is not None and not a.rerank:
+        ap.error("--pool needs --rerank")
+    if a.cmd == "query" and a.pool is not None and not 1 <= a.pool <= 32:
+        ap.error("--pool must lie in [1, 32]")
     if a.cmd == "query" and a.width is not None and not a.moments:
         ap.error("--width needs --moments")
     if a.cmd == "query" and a.width is not None and not a.width >= 0:
@@ -355,7 +506,8 @@ def main(argv=None):
     model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
     if a.cmd == "index":
         corpus = read_corpus(a.feature_dir, a.asr_json, a.vlen_csv, a.worker_id, a.num_workers)
-        idx = build_index(model, corpus, dtype={"bf16": torch.bfloat16, "fp32": torch.float32, "e4m3": E4M3}[a.index_dtype or a.dtype])
+        idx = build_index(model, corpus, dtype={"bf16": torch.bfloat16, "fp32": torch.float32, "e4m3": E4M3}[a.index_dtype or a.dtype],
+                          keep_stem=a.keep_stem)
         idx.save(a.out)
         print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos", file=sys.stderr)
         return 0
@@ -365,6 +517,13 @@ def main(argv=None):
     if a.sequence:
         for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
             print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))
+        return 0
+    if a.rerank:
+        pool = 32 if a.pool is None else a.pool
+        for sentence, hits in zip(a.sentences, search_rerank(idx, model, embed, a.sentences, min(a.k, pool), pool)):
+            for h in hits:
+                al = "" if h.alignability is None else f"{h.alignability:.6f}"
+                print(f"{sentence}\t{h.vid}\t{h.second}\t{h.score:.6f}\t{h.confidence:.6f}\t{al}\t{h.dual_second}\t{h.dual_score:.6f}")
         return 0
     if a.moments:
         width = TEMPERATURE if a.width is None else a.width

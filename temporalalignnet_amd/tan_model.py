@@ -486,6 +486,40 @@ class TemporalAligner(_AlignerEngine, nn.Module):
         out["dual-sim"] = self._within_sample_sim(vd, td, Se, B, T, N, False)
         return out
 
+    # ------------------------------------------------------------------ two-stage search (search.search_rerank)
+    @torch.no_grad()
+    def video_stem(self, video):
+        """video_pre_proj(video) (tan_model.py:187, the projection `_video_embed` starts with): [n, Dv] device features -> [n, 512]
+        in the compute dtype.  It depends on neither the window a second falls into nor the text, so a corpus index can keep it
+        (`search.build_index(keep_stem=True)`) and `joint_from_stem` starts the joint stack from windows cut out of it."""
+        self._ensure_flat()
+        n, Dv = video.shape
+        video_c = self._prep(video)
+        proj = torch.empty(n, WIDTH, dtype=self.compute_dtype, device=video_c.device)
+        ops.gemm(video_c, self._w("video_pre_proj.weight"), proj, M=n, N=WIDTH, K=Dv)
+        return proj
+
+    @torch.no_grad()
+    def joint_from_stem(self, stem_win, video_padding_mask, lang_embed, lang_padding_mask):
+        """The joint stack on (windows of `video_stem` rows [W, T, 512], sentences [W, Kp, Dt]) with the padding masks [W, T] /
+        [W, Kp] as attention keys: the launches `_eval_joint` makes after the projection (text embedding, ln_video_init + position
+        rows in one LayerNorm launch, the stack).  Returns the joint workspace; the caller releases it (`_release_ws`).
+        The position offset is always 0: a search must return the same list every time, so `random_pos_start` is ignored here
+        (the text rows too take offset 0 when `use_text_pos_enc` is set)."""
+        self._ensure_flat()
+        W, T, _ = stem_win.shape
+        Kp = lang_embed.shape[1]
+        cd, dev = self.compute_dtype, stem_win.device
+        rows = stem_win.detach().contiguous().view(W * T, WIDTH)
+        if rows.dtype != cd:
+            rows = ops.cast(rows, torch.empty(W * T, WIDTH, dtype=cd, device=dev))
+        lang_t, _ = self._text_embed(self._prep(lang_embed), bool(self.use_text_pos_enc), 0, None, False)
+        pos_c, _ = self._pos_ln("temporal_pos_embed", T, 0, None, cd, False)
+        x0 = torch.empty(W * T, WIDTH, dtype=cd, device=dev)
+        ops.layernorm_fwd(rows, self._f("ln_video_init.weight"), self._f("ln_video_init.bias"), x0, torch.empty(W * T, device=dev),
+                          torch.empty(W * T, device=dev), pos_c, T)
+        return self._run_joint_stack(x0, lang_t, self._mask_u8(video_padding_mask), self._mask_u8(lang_padding_mask), W, T, Kp)
+
     # checkpoint compatibility: the released checkpoint spells the language model `lang_model.` (train/main.py:467-469)
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         # (called before the children's: an optimizer launch a pipelined step left in flight must not overwrite what is copied in)

@@ -3,6 +3,7 @@ process, device events around each call, caller-owned outputs and scratch.  Prin
 
     python tools/search_bench.py [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE] [--moments]
     python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py --rerank [--rows 4194304] [--queries 1 64] [--pool 32] [--reps 10] [--warmup 3] [--out FILE]
 
 Rows: seeded random unit rows, made in slices.  4 Mi rows are 4 GiB of bf16 and 2 GiB + 16 MiB of e4m3 codes and scales: both far
 beyond the 256 MB last-level cache, so every sweep streams its index from HBM.  Bytes per second count the index once per sweep
@@ -17,7 +18,15 @@ same loads and MFMA loop, so the ratio is what the video epilogue and the row ->
 --sequences times `ops.sequence_topk` INSTEAD of the tables above, on the "corpus" layout, for n_seq x m in 1 x 8, 1 x 32, 8 x 32 and
 32 x 32 (random unit steps), bf16 and e4m3.  The yardsticks, in the same run on the same rows with Q = n_seq * m queries, are
 `ops.rank_topk_video` (the video sweep) and `ops.rank_topk` (the row sweep).  `finish_ms` is `ops.sequence_scores` plus
-`ops.monotonic_decode` for the n_seq * k winners (tables made once, outside the timing)."""
+`ops.monotonic_decode` for the n_seq * k winners (tables made once, outside the timing).
+
+--rerank times the stages of `search.search_rerank` INSTEAD, on the "corpus" layout over a bf16 index with a bf16 stem store (random
+rows) and a randomly initialised 6 + 6 layer model with the alignability head, bf16: `dual_ms` (`ops.rank_topk_video`, k = pool),
+`joint_ms` (per pass of 256 windows: `ops.window_pack` + `joint_from_stem`), `tail_select_ms` (`ops.rerank_tail` per pass +
+`ops.rerank_select`), and `end_to_end_ms` (`search_rerank` itself on the host clock: text features, the window table and the read-back
+included).  Beside them, same run: `moments_ms` (`rank_topk_video` + `moment_extent` at k = 10: the device work of `search_moments`)
+and `eval_windows_ms` (`model.eval_windows` over as many windows of raw 1024-d features: projection, BOTH stacks and the [S, W, T, K]
+similarities -- the joint half of it is what stem + tail replace)."""
 import argparse
 import json
 import os
@@ -136,6 +145,90 @@ def sequences_table(N, k, idx_of, a):
     return rows
 
 
+def rerank_table(N, v16, stem, a):
+    import time
+
+    from temporalalignnet_amd import search
+    from temporalalignnet_amd.tan_model import TemporalAligner
+    torch.manual_seed(0)
+    m = TemporalAligner(6, 6, use_alignability_head=1, random_pos_start=0, language_model=None, compute_dtype="bf16").cuda().eval()
+    v_off = video_layouts(N)["corpus"]
+    nv = v_off.numel() - 1
+    idx = search.VideoIndex(v16, v_off.cpu().numpy(), [f"v{i}" for i in range(nv)], stem=stem)
+    T, Kp, pool, wpp = 64, search.RERANK_TEXT_SLOTS, min(a.pool, nv), 256
+    m._ensure_flat()
+    hw, hb = m._f("binary_head.weight").view(-1), m._f("binary_head.bias")
+    rows = []
+    for Q in a.queries:
+        emb = torch.randn(Q, 512, generator=torch.Generator(device="cuda").manual_seed(Q), device="cuda")
+        tq = search.query_features(idx, m, lambda qs: emb, [""] * Q)
+        out = (torch.empty(Q, pool, device="cuda"), torch.empty(Q, pool, dtype=torch.int32, device="cuda"),
+               torch.empty(Q, pool, dtype=torch.int32, device="cuda"))
+        ws = torch.empty(ops.rank_topk_video_ws_bytes(Q, N, nv, pool), dtype=torch.uint8, device="cuda")
+        t_dual, _ = timed(lambda: ops.rank_topk_video(tq, v16, v_off, pool, out=out, ws=ws), a.warmup, a.reps)
+        km = min(10, nv)
+        mout = tuple(t[:, :km].contiguous() for t in out)
+        ext = (torch.empty(Q, km, dtype=torch.int32, device="cuda"), torch.empty(Q, km, dtype=torch.int32, device="cuda"))
+
+        def moments():
+            ops.rank_topk_video(tq, v16, v_off, km, out=mout, ws=ws)
+            ops.moment_extent(tq, v16, v_off, *mout, 0.07, out=ext)
+        t_mom, _ = timed(moments, a.warmup, a.reps)
+        ops.rank_topk_video(tq, v16, v_off, pool, out=out, ws=ws)
+        table = search._rerank_table(v_off, out[1], out[2], T)
+        n_win = Q * pool
+        passes = [(p0, min(p0 + wpp, n_win)) for p0 in range(0, n_win, wpp)]
+        W0 = passes[0][1]
+        win = torch.empty(W0, T, 512, dtype=stem.dtype, device="cuda")
+        vm, tm = torch.empty(W0, T, dtype=torch.bool, device="cuda"), torch.empty(W0, Kp, dtype=torch.bool, device="cuda")
+        txt = torch.empty(W0, Kp, 512, device="cuda")
+        res = torch.empty(n_win, 4, device="cuda")
+        order = torch.empty(Q, min(10, pool), dtype=torch.int32, device="cuda")
+
+        def joint():
+            for p0, p1 in passes:
+                W = p1 - p0
+                ops.window_pack(stem, emb, table[p0:p1], T, Kp, win[:W], vm[:W], txt[:W], tm[:W])
+                m._release_ws(m.joint_from_stem(win[:W], vm[:W], txt[:W], tm[:W]))
+        t_joint, _ = timed(joint, a.warmup, a.reps)
+        kept = {p1 - p0: None for p0, p1 in passes}
+        for W in kept:                                            # a finished pass of each size: the tail's input
+            ops.window_pack(stem, emb, table[:W], T, Kp, win[:W], vm[:W], txt[:W], tm[:W])
+            kept[W] = m.joint_from_stem(win[:W], vm[:W], txt[:W], tm[:W])
+
+        def tail():
+            for p0, p1 in passes:
+                ej = kept[p1 - p0]
+                ops.rerank_tail(ej.stage(5), ej.stage(2), table[p0:p1], T, hw, hb, res[p0:p1])
+            ops.rerank_select(res.view(Q, pool, 4), order.shape[1], stride=4, out=order)
+        t_tail, _ = timed(tail, a.warmup, a.reps)
+        for ej in kept.values():
+            m._release_ws(ej)
+
+        def end_to_end():
+            t0 = time.perf_counter()
+            search.search_rerank(idx, m, lambda qs: emb, [""] * Q, k=order.shape[1], pool=pool, windows_per_pass=wpp)
+            return (time.perf_counter() - t0) * 1e3
+        for _ in range(a.warmup):
+            end_to_end()
+        t_e2e = float(np.median([end_to_end() for _ in range(a.reps)]))
+        raw = torch.randn(W0, T, 1024, generator=torch.Generator(device="cuda").manual_seed(7), device="cuda").abs()
+        vm.zero_()
+        tm.fill_(True)
+        tm[:, 0] = False
+
+        def evalw():
+            for p0, p1 in passes:
+                W = p1 - p0
+                m.eval_windows(raw[:W], txt[:W], vm[:W], tm[:W])
+        t_eval, _ = timed(evalw, a.warmup, a.reps)
+        rows.append({"Q": Q, "pool": pool, "videos": nv, "windows": n_win, "passes": len(passes), "dual_ms": round(t_dual, 4),
+                     "joint_ms": round(t_joint, 4), "tail_select_ms": round(t_tail, 4),
+                     "stages_ms": round(t_dual + t_joint + t_tail, 4), "end_to_end_ms": round(t_e2e, 4),
+                     "moments_ms": round(t_mom, 4), "eval_windows_ms": round(t_eval, 4)})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=4 * 2 ** 20)
@@ -146,8 +239,33 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--moments", action="store_true", help="also time rank_topk_video and moment_extent (see the module docstring)")
     ap.add_argument("--sequences", action="store_true", help="time sequence_topk against the video and row sweeps instead (see the module docstring)")
+    ap.add_argument("--rerank", action="store_true", help="time the stages of search_rerank instead (see the module docstring)")
+    ap.add_argument("--pool", type=int, default=32)
     a = ap.parse_args()
     N, k = a.rows, a.k
+    if a.rerank:
+        if a.queries == [1, 64, 1024]:
+            a.queries = [1, 64]
+        v16 = torch.empty(N, 512, dtype=torch.bfloat16, device="cuda")
+        stem = torch.empty(N, 512, dtype=torch.bfloat16, device="cuda")
+        for r in range(0, N, SLICE):
+            v16[r:r + SLICE] = unit_rows(min(SLICE, N - r), r).to(torch.bfloat16)
+            stem[r:r + SLICE] = (unit_rows(min(SLICE, N - r), N + r) * 4).to(torch.bfloat16)
+        rows = rerank_table(N, v16, stem, a)
+        res = {"rows": N, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "rerank": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --rerank --rows {N} --pool {a.pool}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
+                fh.write("# bf16 index + bf16 stem, 6 + 6 layer bf16 model with the head, passes of 256 windows of 64 s; stages_ms = dual + joint + "
+                         "tail_select (device events); end_to_end_ms = search_rerank on the host clock; moments_ms = rank_topk_video + moment_extent "
+                         "at k = 10; eval_windows_ms = eval_windows over as many raw-feature windows (both stacks)\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>15}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>15}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
     v16 = torch.empty(N, 512, dtype=torch.bfloat16, device="cuda")
     v8 = torch.empty(N, 512, dtype=torch.uint8, device="cuda")
     s8 = torch.empty(N, device="cuda")

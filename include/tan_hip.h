@@ -908,6 +908,36 @@ int tan_rerank_tail(const void* stage_last, const void* stage_head, int dtype, i
                     const float* head_w, const float* head_b, float* out, float* sim, void* stream);
 int tan_rerank_select(const float* score, long Q, int P, long stride, int k, int* out_idx, void* stream);
 
+/* ---- sharded search: the device fold of per-shard top-k lists (`search.ShardedIndex`) ----
+ * An index cut into shards (whole videos each) is swept shard by shard; the sweeps above leave per-shard lists whose rows / videos
+ * count from the shard's own start.  Three of their contracts make the sharded answer exact: a score does not depend on where its
+ * row sits in a tile, a split or an index (tan_rank_topk); a path depends only on the bits of its video's scores
+ * (tan_sequence_topk); tan_moment_extent reads only its own video's rows.
+ * tan_topk_fold: run_score (f32) / run_shard / run_row (int32) [Q, k] and run_aux [n_aux, Q, k] int32 (NULL when n_aux == 0) hold a
+ * running list per query; in_score / in_row [Q, k_in] and in_aux0 .. in_aux2 [Q, k_in] int32 (the first n_aux non-NULL, the rest
+ * ignored) are the list of shard number `shard`.
+ *   Result: run_*[q, :] <- the k best of (old run list of q) U (incoming list of q, each entry with shard `shard`) under the TOTAL
+ *     order score descending, then shard ascending, then row ascending -- with row_base[shard] the rows before the shard, the
+ *     sweeps' order on the global row row_base[shard] + row (or on the global video number, where `row` carries a video).
+ *   Payload: the aux columns travel with their entry unchanged (moment search: the video and the extent's start and end).
+ *   reset != 0: the old content of run_* is not read; the run list counts as empty.
+ *   Empty slots: an empty run slot is (-inf, shard 0x7fffffff, row 0x7fffffff, aux -1); an incoming slot whose row is 0x7fffffff
+ *     (what the sweeps leave under a broken v_off) counts as empty whatever its score; empty slots sort last.  With fewer than k
+ *     entries in all, the tail of the run list is empty slots.
+ *   Order independence: the order is total on (shard, row) and taking the k best of a union is associative and commutative, so
+ *     the run list after folding every shard ONCE does not depend on the order of the folds.  Folding a shard twice is the caller's
+ *     error (its entries then appear twice).
+ *   1 <= Q < 2^31, 1 <= k <= 32, 1 <= k_in <= k, 0 <= n_aux <= 3, 0 <= shard < 2^31 - 1.  The incoming arrays must not overlap
+ *     the run arrays; the fold is in place on the run arrays.
+ *   One wave per query, four queries per 256-thread workgroup; lanes 0..31 hold the run list, lanes 32..63 the incoming one, one
+ *     64-lane sorting network under the three-part key, payload by one cross-lane move per column.  No atomics, no scratch, no LDS:
+ *     run-to-run identical.
+ *   A NULL run_score / run_shard / run_row / in_score / in_row, run_aux NULL with n_aux > 0, one of the first n_aux in_aux pointers
+ *     NULL, sizes outside the ranges: TAN_ERR_BAD_ARG, nothing launched.                                                          */
+int tan_topk_fold(float* run_score, int* run_shard, int* run_row, int* run_aux, long Q, int k, int n_aux, int reset,
+                  const float* in_score, const int* in_row, const int* in_aux0, const int* in_aux1, const int* in_aux2, int k_in,
+                  int shard, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -585,6 +585,28 @@ def rerank_select(score, k, stride=1, out=None):
     return out
 
 
+def topk_fold(run, incoming, shard, reset=False):
+    """Fold one shard's top-k lists into the running lists, in place (tan_topk_fold; the order and the empty slots are defined in
+    include/tan_hip.h).  run = (score [Q, k] f32, shard [Q, k] int32, row [Q, k] int32, aux [n_aux, Q, k] int32 or None), caller-owned
+    and returned; incoming = (score [Q, k_in] f32, row [Q, k_in] int32, then n_aux int32 [Q, k_in] payload columns), k_in <= k <= 32,
+    n_aux <= 3; `shard`: the number the incoming entries get.  reset: the run lists' old content is ignored (they may be
+    uninitialised).  The run lists end as the k best of both by (score descending, shard ascending, row ascending)."""
+    r_score, r_shard, r_row, r_aux = run
+    in_score, in_row, *in_aux = incoming
+    Q, k = r_score.shape
+    k_in, n_aux = in_score.shape[1], len(in_aux)
+    assert r_score.dtype == torch.float32 and r_score.dim() == 2 and r_score.is_contiguous()
+    assert all(t.dtype == torch.int32 and t.shape == (Q, k) and t.is_contiguous() for t in (r_shard, r_row))
+    assert in_score.dtype == torch.float32 and in_score.shape == (Q, k_in) and in_score.is_contiguous()
+    assert all(t.dtype == torch.int32 and t.shape == (Q, k_in) and t.is_contiguous() for t in (in_row, *in_aux))
+    assert (r_aux is None and n_aux == 0) or (r_aux is not None and r_aux.dtype == torch.int32 and r_aux.shape == (n_aux, Q, k)
+                                               and r_aux.is_contiguous())
+    aux = [_ptr(t) for t in in_aux] + [None] * (3 - n_aux) if n_aux <= 3 else [None] * 3   # n_aux > 3: the entry point refuses it
+    _lib.check(_lib.lib().tan_topk_fold(_f32(r_score), _ptr(r_shard), _ptr(r_row), _ptr(r_aux), Q, k, n_aux, int(bool(reset)),
+                                        _f32(in_score), _ptr(in_row), *aux, k_in, int(shard), _stream()), "tan_topk_fold")
+    return run
+
+
 def clip_chunk():
     """elements per chunk of the gradient-clipping tables (tan_clip_chunk)"""
     return int(_lib.lib().tan_clip_chunk())

@@ -26,12 +26,18 @@ sentence is ranked against all of it:
     every second, the part of the video input that depends on neither window nor text), run through the joint stack
     (`TemporalAligner.joint_from_stem`) and reduced by `tan_rerank_tail` to the joint cosine, the second the joint encoder picks,
     its softmax confidence and the alignability logit; `tan_rerank_select` orders the candidates (`query --rerank`).
+  * `ShardedIndex`: several index files (one per `index --worker-id`) searched together, or one corpus larger than the card streamed
+    from pinned host memory.  Every shard is swept on its own and `tan_topk_fold` folds the per-shard lists on the device under the
+    sweeps' own order: `search`, `search_moments` and `search_sequences` return what they return for `VideoIndex.concat` of the
+    shards, bit for bit (`query --shard`, `query --host-resident`, `merge`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --moments [--width 0.07] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --sequence "crack two eggs" "whisk them" "pour into the pan"
     python -m temporalalignnet_amd.search index ... --keep-stem;  ... query ... --rerank [--pool 32] "crack two eggs" ...
+    python -m temporalalignnet_amd.search query ... --index I0.npz --shard I1.npz --shard I2.npz [--host-resident] "crack two eggs" ...
+    python -m temporalalignnet_amd.search merge --out I.npz I0.npz I1.npz ...
 """
 from __future__ import annotations
 
@@ -133,6 +139,38 @@ class VideoIndex:
     def e4m3(self):
         return self.scale is not None
 
+    @property
+    def device(self):
+        return self.feat.device
+
+    @property
+    def row_dtype(self):
+        """torch.float32, torch.bfloat16, or torch.uint8 for e4m3 codes"""
+        return self.feat.dtype
+
+    @classmethod
+    def concat(cls, indices):
+        """One index holding the rows, scales, stems, vids and v_off of `indices` one after the other, on the device of the first
+        (CPU tensors work: `load(path, device="cpu")`).  Equal vid strings stay separate videos.  ValueError unless all share one
+        row format (f32, bf16 or e4m3) and either all have a stem of one dtype or none has one, and for 2^31 rows or more."""
+        indices = list(indices)
+        if not indices:
+            raise ValueError("VideoIndex.concat: no indices")
+        head = indices[0]
+        dev = head.feat.device
+        if any(ix.feat.dtype != head.feat.dtype for ix in indices):
+            raise ValueError("VideoIndex.concat: the indices differ in row format (f32 / bf16 / e4m3)")
+        if any((ix.stem is None) != (head.stem is None) or (ix.stem is not None and ix.stem.dtype != head.stem.dtype) for ix in indices):
+            raise ValueError("VideoIndex.concat: either every index has a stem of one dtype or none has one")
+        base = np.concatenate([[0], np.cumsum([len(ix) for ix in indices])]).astype(np.int64)
+        if int(base[-1]) >= 2 ** 31:
+            raise ValueError("VideoIndex.concat: 2^31 rows or more; query the files together as a ShardedIndex instead")
+        cat = lambda ts: torch.cat([t.to(dev) for t in ts], 0).contiguous()                       # noqa: E731
+        v_off = np.concatenate([ix.v_off[:-1] + b for ix, b in zip(indices, base)] + [base[-1:]])
+        return cls(cat([ix.feat for ix in indices]), v_off, [v for ix in indices for v in ix.vids],
+                   cat([ix.scale for ix in indices]) if head.e4m3 else None,
+                   cat([ix.stem for ix in indices]) if head.stem is not None else None)
+
     def quantize(self):
         """The e4m3 index of this bf16 / f32 one (tan_quantize_rows_e4m3), with the same stem; an e4m3 index is returned as it is."""
         if self.e4m3:
@@ -174,6 +212,130 @@ class VideoIndex:
                 stem = torch.from_numpy(st.view(np.int16)).view(torch.bfloat16) if st.dtype == np.uint16 else torch.from_numpy(st)
                 stem = stem.to(device).contiguous()
             return cls(f.to(device).contiguous(), z["v_off"], [str(v) for v in z["vids"]], scale, stem)
+
+
+class ShardedIndex:
+    """Several `VideoIndex` shards (whole videos each; the files `index --worker-id i --num-workers n` writes) searched together:
+    `search`, `search_moments` and `search_sequences` return for it exactly what they return for `VideoIndex.concat(shards)` --
+    every shard is swept on its own and the per-shard lists are folded on the device by `tan_topk_fold`.  Equal vid
+    strings in two shards are two videos, as inside one index.  Every shard holds fewer than 2^31 rows; their total may exceed it.
+      vids                      every shard's, in shard order
+      v_off [n_videos + 1]      int64, global: each video's first row
+      row_base / video_base     int64 [S + 1]: the rows / videos before shard s; the last entry is the total
+      locate(shard, row)        shard-local rows -> (global video number, second)
+    resident="device": the shards' rows are where the caller put them, all on one device (files from several workers).
+    resident="host":   rows and scales stay in PINNED host memory and only each shard's int32 v_off lives on `device`; a search
+      streams the shards through two device slots sized to the largest shard, the copy of the next shard running under the sweep of
+      the current one (`shard_views`).  This is for a corpus larger than the card.  Every call then moves the whole index over the
+      host link (PCIe Gen5 x16: 63 GB/s by its specification), which bounds it whatever the sweeps cost -- accepted, and the reason
+      to batch many queries per call.  Unpinned host rows raise: a pageable copy would synchronise silently.
+    Stems are not used (`search_rerank` refuses a ShardedIndex)."""
+
+    def __init__(self, shards, resident="device", device=None):
+        self.shards = list(shards)
+        if not self.shards:
+            raise ValueError("ShardedIndex: no shards")
+        if resident not in ("device", "host"):
+            raise ValueError("ShardedIndex: resident is 'device' or 'host'")
+        head = self.shards[0]
+        if any(sh.feat.dtype != head.feat.dtype for sh in self.shards):
+            raise ValueError("ShardedIndex: the shards differ in row format (f32 / bf16 / e4m3)")
+        if any(len(sh) < 1 or len(sh) >= 2 ** 31 for sh in self.shards):
+            raise ValueError("ShardedIndex: a shard holds 1 to 2^31 - 1 rows")
+        self.resident = resident
+        if resident == "host":
+            self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            for sh in self.shards:
+                if any(t.is_cuda or not t.is_pinned() for t in (sh.feat, sh.scale) if t is not None):
+                    raise ValueError("ShardedIndex: resident='host' needs rows and scales in pinned host memory (ShardedIndex.load "
+                                     "pins them); a pageable copy would not run under the sweeps")
+            self._v_off_dev = [torch.from_numpy(sh.v_off.astype(np.int32)).to(self.device) for sh in self.shards]
+        else:
+            self.device = head.feat.device
+            if any(sh.feat.device != self.device for sh in self.shards) or (device is not None and torch.device(device) != self.device):
+                raise ValueError("ShardedIndex: resident='device' needs every shard on one device")
+        self.row_dtype = head.feat.dtype
+        self.e4m3 = head.e4m3
+        self.row_base = np.concatenate([[0], np.cumsum([len(sh) for sh in self.shards])]).astype(np.int64)
+        self.video_base = np.concatenate([[0], np.cumsum([len(sh.vids) for sh in self.shards])]).astype(np.int64)
+        self.vids = [v for sh in self.shards for v in sh.vids]
+        self.v_off = np.concatenate([sh.v_off[:-1] + b for sh, b in zip(self.shards, self.row_base)] + [self.row_base[-1:]])
+        self._slots = self._side = None
+        self._free = [None, None]
+
+    @classmethod
+    def load(cls, paths, device="cuda", resident="device"):
+        """The index files `paths`, in this order.  resident="host": rows and scales are read into pinned host memory."""
+        if resident != "host":
+            return cls([VideoIndex.load(p, device) for p in paths], resident)
+        shards = []
+        for p in paths:
+            ix = VideoIndex.load(p, "cpu")
+            shards.append(VideoIndex(ix.feat.pin_memory(), ix.v_off, ix.vids, ix.scale.pin_memory() if ix.e4m3 else None, ix.stem))
+        return cls(shards, resident, device)
+
+    def __len__(self):
+        return int(self.row_base[-1])
+
+    def locate(self, shard, row):
+        """(shard, shard-local row) -> (global video number, second)"""
+        shard, row = np.asarray(shard, dtype=np.int64), np.asarray(row, dtype=np.int64)
+        g = self.row_base[shard] + row
+        v = np.searchsorted(self.v_off, g, side="right") - 1
+        return v, g - self.v_off[v]
+
+    def shard_views(self, order=None):
+        """Yields (s, feat, scale, v_off) -- device tensors of shard s, v_off its int32 offsets -- for s in `order` (default: every
+        shard).  The caller issues EVERY kernel that reads a shard's views on the current stream before it asks for the next shard.
+        resident="host": shard order[i] lives in slot i % 2 while it is swept; the copy of order[i + 1] into the other slot is issued
+        on a side stream before shard i is handed out, so it runs under shard i's sweep."""
+        order = list(range(len(self.shards))) if order is None else list(order)
+        if self.resident == "device":
+            for s in order:
+                sh = self.shards[s]
+                yield s, sh.feat, sh.scale, sh.v_off_device
+            return
+        comp = torch.cuda.current_stream(self.device)
+        if self._slots is None:
+            rows = max(len(sh) for sh in self.shards)
+            self._slots = [(torch.empty(rows, 512, dtype=self.row_dtype, device=self.device),
+                            torch.empty(rows, dtype=torch.float32, device=self.device) if self.e4m3 else None) for _ in range(2)]
+            self._side = torch.cuda.Stream(device=self.device)
+            self._side.wait_stream(comp)               # the allocator may hand out memory that work queued on `comp` still uses
+        side, in_flight = self._side, {}
+
+        def issue(i):
+            sh, (feat, scale) = self.shards[order[i]], self._slots[i % 2]
+            n = len(sh)
+            if not sh.feat.is_pinned() or (self.e4m3 and not sh.scale.is_pinned()):
+                raise ValueError("ShardedIndex: a host-resident shard is not in pinned memory")
+            if self._free[i % 2] is not None:
+                side.wait_event(self._free[i % 2])     # the slot's previous shard has been read to the end (see below)
+            with torch.cuda.stream(side):
+                feat[:n].copy_(sh.feat, non_blocking=True)
+                if self.e4m3:
+                    scale[:n].copy_(sh.scale, non_blocking=True)
+                in_flight[i] = torch.cuda.Event()
+                in_flight[i].record(side)
+            return feat[:n], (scale[:n] if self.e4m3 else None)
+
+        try:
+            nxt = issue(0) if order else None
+            for i, s in enumerate(order):
+                cur, nxt = nxt, (issue(i + 1) if i + 1 < len(order) else None)
+                comp.wait_event(in_flight.pop(i))
+                try:
+                    yield s, cur[0], cur[1], self._v_off_dev[s]
+                finally:
+                    # The copy of a LATER shard into this slot must not start before the last kernel that read this one has
+                    # finished.  The caller has issued all of them by now (the fold; for moments the extent, for sequence phase 2
+                    # the score blocks), so an event recorded on the compute stream HERE is behind them; the next copy into the
+                    # slot, in this call or a later one, waits on it on the side stream.
+                    self._free[i % 2] = torch.cuda.Event()
+                    self._free[i % 2].record(comp)
+        finally:
+            for ev in in_flight.values():              # an early exit: no slot is left being written behind the caller's back
+                comp.wait_event(ev)
 
 
 @torch.no_grad()
@@ -224,19 +386,36 @@ def build_index(model, videos, seq_len=64, windows_per_pass=256, dtype=torch.bfl
 def query_features(index, model, embed_text, queries, text_batch=1024):
     """Unit text features [Q, 512] in the index's dtype; for an e4m3 index (codes uint8 [Q, 512], scale f32 [Q])."""
     net = _aligner(model)
-    dev = index.feat.device
+    dev = index.device
     t = torch.cat([net.get_textual_feature(embed_text(list(queries[a:a + text_batch])).to(dev)).float().reshape(-1, 512)
                    for a in range(0, len(queries), text_batch)], 0).contiguous()
     t = ops.l2norm_fwd(t, torch.empty_like(t), None, t.shape[0], 512)
     if index.e4m3:
         return ops.quantize_rows_e4m3(t)
-    return t if index.feat.dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.feat.dtype, device=dev))
+    return t if index.row_dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.row_dtype, device=dev))
+
+
+def _run_lists(Q, k, n_aux, dev):
+    """`ops.topk_fold`'s running lists for Q queries, uninitialised: the first fold resets them"""
+    return (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev),
+            torch.empty(Q, k, dtype=torch.int32, device=dev), torch.empty(n_aux, Q, k, dtype=torch.int32, device=dev) if n_aux else None)
+
+
+def _read_lists(run):
+    """One read-back of the folded lists: score [Q, k] f32 (travelling as its bit pattern) and int32 [2 + n_aux, Q, k] = shard, row,
+    then the payload columns."""
+    score, shard, row, aux = run
+    ints = torch.stack((shard, row)) if aux is None else torch.cat((torch.stack((shard, row)), aux))
+    back = torch.cat((score.view(torch.int32)[None], ints)).cpu().numpy()
+    return back[0].view(np.float32), back[1:]
 
 
 @torch.no_grad()
 def search(index, model, embed_text, queries, k=10, splits=0):
     """Per query the k best seconds of the corpus: [[(vid, second, score)] * k] * len(queries), by descending score (equal scores
-    by index row).  score = <index row, unit text feature>: the stitched dual cosine; / 0.07 gives the evaluation's logit."""
+    by index row).  score = <index row, unit text feature>: the stitched dual cosine; / 0.07 gives the evaluation's logit.
+    `index`: a `VideoIndex`, or a `ShardedIndex` -- then exactly what `VideoIndex.concat` of its shards gives (as for
+    `search_moments` and `search_sequences`): one sweep and one `tan_topk_fold` per shard, one read-back at the end."""
     queries = list(queries)
     if not queries:
         return []
@@ -244,6 +423,18 @@ def search(index, model, embed_text, queries, k=10, splits=0):
     if not 1 <= k <= 32:
         raise ValueError("search: k must lie in [1, 32]")
     tq = query_features(index, model, embed_text, queries)
+    if isinstance(index, ShardedIndex):
+        run = _run_lists(len(queries), k, 0, index.device)
+        for i, (s, feat, scale, _) in enumerate(index.shard_views()):
+            k_s = min(k, feat.shape[0])
+            if index.e4m3:
+                _, _, score, row = ops.rank_topk_e4m3(*tq, feat, scale, None, k_s, splits=splits)
+            else:
+                _, _, score, row = ops.rank_topk(tq, feat, None, k_s, splits=splits)
+            ops.topk_fold(run, (score, row), s, reset=i == 0)
+        score, (shard, row) = _read_lists(run)
+        v, sec = index.locate(shard, row)
+        return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
     if index.e4m3:
         _, _, score, row = ops.rank_topk_e4m3(*tq, index.feat, index.scale, None, k, splits=splits)
     else:
@@ -270,6 +461,24 @@ def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, s
     if not width >= 0:
         raise ValueError("search_moments: width must be >= 0")
     tq = query_features(index, model, embed_text, queries)
+    if isinstance(index, ShardedIndex):
+        tq, q_scale = tq if index.e4m3 else (tq, None)
+        run = _run_lists(len(queries), k, 3, index.device)
+        for i, (s, feat, scale, v_off) in enumerate(index.shard_views()):
+            k_s = min(k, v_off.numel() - 1)
+            scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
+            score, row, video = ops.rank_topk_video(tq, feat, v_off, k_s, splits=splits, **scales)
+            # the extents of the shard's OWN list, before the fold: the shard's rows are passed over once (and are gone afterwards
+            # when they are streamed), at the price of extents for hits the fold drops
+            start, end = ops.moment_extent(tq, feat, v_off, score, row, video, width, **scales)
+            ops.topk_fold(run, (score, row, video, start, end), s, reset=i == 0)
+        score, (shard, row, video, start, end) = _read_lists(run)              # all shard-local
+        first = np.zeros_like(row)
+        for s in np.unique(shard):
+            first[shard == s] = index.shards[s].v_off[video[shard == s]]
+        gv = index.video_base[shard] + video
+        return [[Moment(index.vids[gv[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
+                        int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
     tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
     v_off = index.v_off_device
     score, row, video = ops.rank_topk_video(tq, index.feat, v_off, k, splits=splits, **scales)
@@ -297,38 +506,73 @@ def search_sequences(index, model, embed_text, sequences, k=10, splits=0):
     k = min(int(k), len(index.vids))
     if not 1 <= k <= 32:
         raise ValueError("search_sequences: k must lie in [1, 32]")
-    dev = index.feat.device
+    dev = index.device
     m = np.array([len(seq) for seq in sequences], dtype=np.int64)
     s_off = torch.from_numpy(np.concatenate([[0], np.cumsum(m)]).astype(np.int32)).to(dev)
     tq = query_features(index, model, embed_text, [sentence for seq in sequences for sentence in seq])
+    n_seq = len(sequences)
+    if isinstance(index, ShardedIndex):
+        tq, q_scale = tq if index.e4m3 else (tq, None)
+        # phase 1: every shard's best videos, folded with row = the shard-local video number
+        run = _run_lists(n_seq, k, 0, dev)
+        for i, (s, feat, scale, v_off) in enumerate(index.shard_views()):
+            scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
+            ops.topk_fold(run, ops.sequence_topk(tq, feat, s_off, v_off, min(k, v_off.numel() - 1), splits=splits, **scales), s,
+                          reset=i == 0)
+        shard, video = (a.reshape(-1).astype(np.int64) for a in torch.stack(run[1:3]).cpu().numpy())   # read-back 1: the winners
+        # phase 2: the seconds, shard by shard over the shards that hold winners, each over its own hits
+        seq_of_hit = np.repeat(np.arange(n_seq), k)
+        parts = []
+        holders = [int(s) for s in np.unique(shard)]
+        for s, feat, scale, v_off in index.shard_views(holders):
+            scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
+            at = np.flatnonzero(shard == s)
+            parts.append((at, *_sequence_seconds(tq, feat, s_off, v_off, index.shards[s].v_off, m, seq_of_hit[at], video[at], scales)))
+        back = torch.cat([run[0].reshape(-1).view(torch.int32)] + [ts for _, ts, _ in parts]).cpu().numpy()   # read-back 2
+        score, a0 = back[:n_seq * k].view(np.float32), n_seq * k
+        seconds = [None] * (n_seq * k)
+        for at, ts, first in parts:
+            for j, h in enumerate(at):
+                seconds[h] = tuple(int(t) for t in back[a0 + first[j]:a0 + first[j + 1]])
+            a0 += int(first[-1])
+        gv = index.video_base[shard] + video
+        return [[SequenceHit(index.vids[gv[p * k + i]], seconds[p * k + i], float(score[p * k + i])) for i in range(k)]
+                for p in range(n_seq)]
     tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
     v_off = index.v_off_device
     top_s, top_v = ops.sequence_topk(tq, index.feat, s_off, v_off, k, splits=splits, **scales)
     video = top_v.cpu().numpy().astype(np.int64)                   # read-back 1: [n_seq, k] winners
-    # one [m, V] block of scores per hit, and the decode's tables: one "video" per hit, its m rows in step order
-    n_seq = len(sequences)
-    hm = np.repeat(m, k)
-    hv = (index.v_off[video + 1] - index.v_off[video]).reshape(-1)
-    x_off = np.concatenate([[0], np.cumsum(hm * hv)])
-    if x_off[-1] >= 2 ** 31:
-        raise ValueError("search_sequences: the winners' score blocks exceed the int32 decode tables; lower k or split the call")
-    first = np.concatenate([[0], np.cumsum(hm)])
-    hit_of_row = np.repeat(np.arange(n_seq * k), hm)
-    step = np.arange(first[-1]) - first[hit_of_row]
-    rows = np.stack((x_off[hit_of_row] + step * hv[hit_of_row], hv[hit_of_row]), 1)
-    vtab = np.stack((first[:-1], hm, np.concatenate([[0], np.cumsum(hv)])[:-1]), 1)
-    hits = np.stack((np.repeat(np.arange(n_seq), k), video.reshape(-1)), 1)
-    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)          # noqa: E731
-    x = torch.empty(int(x_off[-1]), dtype=torch.float32, device=dev)
-    ops.sequence_scores(tq, index.feat, s_off, v_off, i32(hits), torch.from_numpy(x_off[:-1].copy()).to(dev), x, **scales)
-    ts = torch.empty(int(first[-1]), dtype=torch.int32, device=dev)
-    path = torch.empty(n_seq * k, dtype=torch.float32, device=dev)
-    ops.monotonic_decode(x, i32(rows), torch.arange(int(first[-1]), dtype=torch.int32, device=dev), i32(vtab), None,
-                         torch.empty(x.numel(), dtype=torch.int32, device=dev), torch.empty(int(hv.sum()), device=dev), ts, path)
+    ts, first = _sequence_seconds(tq, index.feat, s_off, v_off, index.v_off, m, np.repeat(np.arange(n_seq), k), video.reshape(-1), scales)
     back = torch.cat((top_s.reshape(-1).view(torch.int32), ts)).cpu().numpy()                  # read-back 2: scores and seconds
     score, ts = back[:n_seq * k].view(np.float32), back[n_seq * k:]
     return [[SequenceHit(index.vids[video[p, i]], tuple(int(t) for t in ts[first[p * k + i]:first[p * k + i + 1]]),
                          float(score[p * k + i])) for i in range(k)] for p in range(n_seq)]
+
+
+def _sequence_seconds(tq, feat, s_off, v_off_dev, v_off, m, seq, video, scales):
+    """The seconds of P hits (seq [P], video [P]: a sequence and a video of THIS index each) -- one [m, V] block of scores per hit
+    (`tan_sequence_scores`) and the decode's tables: one "video" per hit, its m rows in step order.  Returns (ts: int32 on the
+    device, the hits' seconds one after the other, first [P + 1]: where each hit's begin).  Nothing is read back."""
+    dev, P = feat.device, len(seq)
+    hm = m[seq]
+    hv = v_off[video + 1] - v_off[video]
+    x_off = np.concatenate([[0], np.cumsum(hm * hv)])
+    if x_off[-1] >= 2 ** 31:
+        raise ValueError("search_sequences: the winners' score blocks exceed the int32 decode tables; lower k or split the call")
+    first = np.concatenate([[0], np.cumsum(hm)])
+    hit_of_row = np.repeat(np.arange(P), hm)
+    step = np.arange(first[-1]) - first[hit_of_row]
+    rows = np.stack((x_off[hit_of_row] + step * hv[hit_of_row], hv[hit_of_row]), 1)
+    vtab = np.stack((first[:-1], hm, np.concatenate([[0], np.cumsum(hv)])[:-1]), 1)
+    hits = np.stack((seq, video), 1)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)          # noqa: E731
+    x = torch.empty(int(x_off[-1]), dtype=torch.float32, device=dev)
+    ops.sequence_scores(tq, feat, s_off, v_off_dev, i32(hits), torch.from_numpy(x_off[:-1].copy()).to(dev), x, **scales)
+    ts = torch.empty(int(first[-1]), dtype=torch.int32, device=dev)
+    path = torch.empty(P, dtype=torch.float32, device=dev)
+    ops.monotonic_decode(x, i32(rows), torch.arange(int(first[-1]), dtype=torch.int32, device=dev), i32(vtab), None,
+                         torch.empty(x.numel(), dtype=torch.int32, device=dev), torch.empty(int(hv.sum()), device=dev), ts, path)
+    return ts, first
 
 
 def rerank_window(sec, vlen, seq_len=64):
@@ -371,6 +615,8 @@ def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, 
     clamped to the number of videos too, 1 <= k <= pool.  The Q * pool windows run in passes of `windows_per_pass`; one read-back.
     return_sim: also return every window's cosines, (hits, sim [Q, pool, seq_len] f32, candidates in dual rank order, -inf beyond
     a window's seconds), a second read-back."""
+    if isinstance(index, ShardedIndex):
+        raise ValueError("search_rerank: not built for a ShardedIndex; merge the shards")
     net = _aligner(model)
     if index.stem is None:
         raise ValueError("search_rerank: the index has no stem store (build_index(..., keep_stem=True) / index --keep-stem)")
@@ -473,7 +719,14 @@ def _parser():
                    help="two stages: the --pool best distinct videos of the dual sweep rescored by the joint encoder, the k best as "
                         "`sentence vid second score confidence alignability dual_second dual_score` (needs index --keep-stem)")
     p.add_argument("--pool", type=int, default=None, help="with --rerank: candidates per sentence, 1 to 32 (default 32)")
+    p.add_argument("--shard", action="append", default=None, metavar="PATH",
+                   help="a further index file searched together with --index, in the order given (repeatable)")
+    p.add_argument("--host-resident", action="store_true",
+                   help="keep the rows in pinned host memory and stream them through the card: for an index larger than the card")
     p.add_argument("sentences", nargs="+")
+    p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
+    p.add_argument("--out", required=True, help="index file (.npz)")
+    p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
     return ap
 
 
@@ -486,6 +739,8 @@ def parse_args(argv=None):
         ap.error("--sequence takes at most 32 sentences")
     if a.cmd == "query" and a.rerank and (a.sequence or a.moments):
         ap.error("--rerank does not go with --sequence / --moments")
+    if a.cmd == "query" and a.rerank and (a.shard or a.host_resident):
+        ap.error("--rerank does not go with --shard / --host-resident; merge the index files")
     if a.cmd == "query" and a.pool is not None and not a.rerank:
         ap.error("--pool needs --rerank")
     if a.cmd == "query" and a.pool is not None and not 1 <= a.pool <= 32:
@@ -501,6 +756,11 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
+    if a.cmd == "merge":
+        idx = VideoIndex.concat([VideoIndex.load(p, device="cpu") for p in a.inputs])
+        idx.save(a.out)
+        print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos from {len(a.inputs)} files", file=sys.stderr)
+        return 0
     from .infer_align import build_aligner, make_embed_text, read_corpus
     vocab = np.load(a.vocab)
     model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
@@ -513,7 +773,10 @@ def main(argv=None):
         return 0
     from .word2vec_model import Word2VecTokenizer
     embed = make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab))
-    idx = VideoIndex.load(a.index)
+    if a.shard or a.host_resident:
+        idx = ShardedIndex.load([a.index] + (a.shard or []), resident="host" if a.host_resident else "device")
+    else:
+        idx = VideoIndex.load(a.index)
     if a.sequence:
         for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
             print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))

@@ -4,6 +4,7 @@ process, device events around each call, caller-owned outputs and scratch.  Prin
     python tools/search_bench.py [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE] [--moments]
     python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --rerank [--rows 4194304] [--queries 1 64] [--pool 32] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py --shards [8] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
 
 Rows: seeded random unit rows, made in slices.  4 Mi rows are 4 GiB of bf16 and 2 GiB + 16 MiB of e4m3 codes and scales: both far
 beyond the 256 MB last-level cache, so every sweep streams its index from HBM.  Bytes per second count the index once per sweep
@@ -26,7 +27,14 @@ rows) and a randomly initialised 6 + 6 layer model with the alignability head, b
 `ops.rerank_select`), and `end_to_end_ms` (`search_rerank` itself on the host clock: text features, the window table and the read-back
 included).  Beside them, same run: `moments_ms` (`rank_topk_video` + `moment_extent` at k = 10: the device work of `search_moments`)
 and `eval_windows_ms` (`model.eval_windows` over as many windows of raw 1024-d features: projection, BOTH stacks and the [S, W, T, K]
-similarities -- the joint half of it is what stem + tail replace)."""
+similarities -- the joint half of it is what stem + tail replace).
+
+--shards [S] times sharded search INSTEAD (`search.ShardedIndex`, S = 8 equal shards of the same rows), bf16 and e4m3, per Q:
+`single_ms` (`ops.rank_topk` over the whole index: the yardstick), `device_shards_ms` (S sweeps + S `ops.topk_fold` over device-resident
+shards) and their ratio, `fold_us_per_launch` (the S folds alone), `host_shards_ms` (the same loop with the shards streamed from pinned
+host memory through `ShardedIndex.shard_views`' two slots) as `host_GBps` of index bytes, and `copy_ms` / `copy_GBps`: a plain pinned
+`copy_` of the same bytes into one slot in the same run -- the host link's rate, which `host_shards` cannot beat.  `equals_single`:
+the folded lists have the single sweep's scores (bit patterns) and rows."""
 import argparse
 import json
 import os
@@ -145,6 +153,68 @@ def sequences_table(N, k, idx_of, a):
     return rows
 
 
+def shards_table(N, k, v16, v8, s8, a):
+    """One row per (format, Q): the single sweep, S device-resident shards, S host-resident shards, the fold alone, a plain pinned
+    copy of the same bytes."""
+    from temporalalignnet_amd import search
+    S = a.shards
+    cuts = [N * i // S for i in range(S + 1)]
+    base = torch.tensor(cuts[:-1], device="cuda")
+    rows = []
+    for fmt, vn, vs, row_bytes in (("bf16", v16, None, 1024), ("e4m3", v8, s8, 516)):
+        parts = [search.VideoIndex(vn[c0:c1], [0, c1 - c0], [f"s{i}"], None if vs is None else vs[c0:c1])
+                 for i, (c0, c1) in enumerate(zip(cuts[:-1], cuts[1:]))]
+        dev = search.ShardedIndex(parts)
+        host = search.ShardedIndex([search.VideoIndex(p.feat.cpu().pin_memory(), p.v_off, p.vids, None if vs is None else p.scale.cpu().pin_memory())
+                                    for p in parts], resident="host")
+        n_max = max(len(p) for p in parts)
+        slot = torch.empty(n_max, 512, dtype=vn.dtype, device="cuda")
+        slot_s = torch.empty(n_max, device="cuda") if vs is not None else None
+
+        def copy_all():
+            for p in host.shards:
+                slot[:len(p)].copy_(p.feat, non_blocking=True)
+                if vs is not None:
+                    slot_s[:len(p)].copy_(p.scale, non_blocking=True)
+        t_copy, _ = timed(copy_all, a.warmup, a.reps)
+        for Q in a.queries:
+            q = unit_rows(Q, 1 << 30)
+            tq, qs = (q.to(torch.bfloat16), None) if vs is None else ops.quantize_rows_e4m3(q)
+            ws = torch.empty(max(ops.rank_topk_ws_bytes(Q, n, k) for n in [N] + [len(p) for p in parts]), dtype=torch.uint8, device="cuda")
+            one = (None, None, torch.empty(Q, k, device="cuda"), torch.empty(Q, k, dtype=torch.int32, device="cuda"))
+            out = (None, None, torch.empty(Q, k, device="cuda"), torch.empty(Q, k, dtype=torch.int32, device="cuda"))
+            run = (torch.empty(Q, k, device="cuda"), torch.empty(Q, k, dtype=torch.int32, device="cuda"),
+                   torch.empty(Q, k, dtype=torch.int32, device="cuda"), None)
+
+            def sweep(feat, scale, o):
+                if vs is None:
+                    ops.rank_topk(tq, feat, None, k, out=o, ws=ws)
+                else:
+                    ops.rank_topk_e4m3(tq, qs, feat, scale, None, k, out=o, ws=ws)
+
+            def sharded(index):
+                for i, (s, feat, scale, _) in enumerate(index.shard_views()):
+                    sweep(feat, scale, out)
+                    ops.topk_fold(run, out[2:], s, reset=i == 0)
+
+            def folds():
+                for s in range(S):
+                    ops.topk_fold(run, out[2:], s, reset=s == 0)
+            t_one, _ = timed(lambda: sweep(vn, vs, one), a.warmup, a.reps)
+            t_dev, _ = timed(lambda: sharded(dev), a.warmup, a.reps)
+            same_dev = bool(torch.equal(run[0].view(torch.int32), one[2].view(torch.int32)) and torch.equal(base[run[1].long()] + run[2], one[3].long()))
+            t_fold, _ = timed(folds, a.warmup, a.reps)
+            t_host, _ = timed(lambda: sharded(host), a.warmup, a.reps)
+            same_host = bool(torch.equal(run[0].view(torch.int32), one[2].view(torch.int32)) and torch.equal(base[run[1].long()] + run[2], one[3].long()))
+            rows.append({"fmt": fmt, "Q": Q, "shards": S, "single_ms": round(t_one, 4), "device_shards_ms": round(t_dev, 4),
+                         "device_over_single": round(t_dev / t_one, 3), "fold_us_per_launch": round(t_fold / S * 1e3, 2),
+                         "host_shards_ms": round(t_host, 3), "host_GBps": round(N * row_bytes / t_host * 1e-6, 2),
+                         "copy_ms": round(t_copy, 3), "copy_GBps": round(N * row_bytes / t_copy * 1e-6, 2),
+                         "host_over_copy": round(t_host / t_copy, 3), "equals_single": same_dev and same_host})
+        del host, slot, slot_s
+    return rows
+
+
 def rerank_table(N, v16, stem, a):
     import time
 
@@ -241,6 +311,8 @@ def main():
     ap.add_argument("--sequences", action="store_true", help="time sequence_topk against the video and row sweeps instead (see the module docstring)")
     ap.add_argument("--rerank", action="store_true", help="time the stages of search_rerank instead (see the module docstring)")
     ap.add_argument("--pool", type=int, default=32)
+    ap.add_argument("--shards", type=int, nargs="?", const=8, default=0, metavar="S",
+                    help="time sharded search over S shards (default 8) instead (see the module docstring)")
     a = ap.parse_args()
     N, k = a.rows, a.k
     if a.rerank:
@@ -274,6 +346,22 @@ def main():
         v16[r:r + SLICE] = x.to(torch.bfloat16)
         ops.quantize_rows_e4m3(x, v8[r:r + SLICE], s8[r:r + SLICE])
     del x
+    if a.shards:
+        rows = shards_table(N, k, v16, v8, s8, a)
+        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "shards": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --shards {a.shards} --rows {N} -k {k}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
+                fh.write("# single = one rank_topk sweep; device_shards = a sweep + a tan_topk_fold per device-resident shard; host_shards = the same "
+                         "with the shards streamed from pinned host memory through two slots (GB/s of index bytes); copy = plain pinned copy_ of "
+                         "the same bytes into one slot, same run\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>18}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>18}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
     if a.sequences:
         def idx_of(q):
             q8, qs8 = ops.quantize_rows_e4m3(q)

@@ -938,6 +938,51 @@ int tan_topk_fold(float* run_score, int* run_shard, int* run_row, int* run_aux, 
                   const float* in_score, const int* in_row, const int* in_aux0, const int* in_aux1, const int* in_aux2, int k_in,
                   int shard, void* stream);
 
+/* ---- filtered search: a sweep restricted to row spans (`search.RowFilter`: a playlist, an exclusion list, time windows) ----
+ * A FILTER over an index of N rows is a list of row spans [lo, hi): spans [n_spans, 2] int32 on the device, ascending, disjoint,
+ * non-empty, inside [0, N).  Rows inside a span are ADMITTED.  A sweep reads a filter through its IMAGE:
+ * tan_row_filter_build: spans -> the image, in caller-owned device memory `filt` of tan_row_filter_bytes(N) bytes (16-byte
+ *   aligned; -1 for N outside [1, 2^31)).  With T = ceil(N / 64) 64-row tiles, T2 = T rounded up to 2, in int32 words:
+ *     [0]                     n_listed: how many tiles hold an admitted row
+ *     [1]                     T;  [2], [3]: 0
+ *     [4, 4 + T2)             the listed tiles' numbers, ascending (the first n_listed entries; the rest is not written)
+ *     [4 + T2, 4 + T2 + 2 T)  one 64-bit row mask per LISTED tile, in list order: bit r set <=> row 64 * tile + r is admitted
+ *                             (never a row >= N)
+ *     the rest                scratch of the build (every tile's mask, then one count per 256 tiles); no sweep reads it
+ *   Three launches: a thread per tile finds the spans that meet its tile by binary search and counts per block, one block scans
+ *   the counts, a thread per tile writes its list entry.  No atomics: the image is bit-identical from run to run.  The same image
+ *   serves every Q, k, splits and row format of an index of N rows.
+ *   Spans that break their contract are the CALLER's error: every span is cut to its tile and to [0, N), at most 64 spans are
+ *   looked at per tile, nothing is read or written out of bounds, and the image is then unspecified.  1 <= n_spans < 2^30; a NULL
+ *   pointer or a size outside these ranges: TAN_ERR_BAD_ARG, nothing launched.
+ * tan_rank_topk_filtered / _e4m3: tan_rank_topk / _e4m3 without pair, higher and ties, over the admitted rows only; 1 <= k <= 32,
+ *   k <= N.  tan_rank_topk_video_filtered / _e4m3: tan_rank_topk_video / _e4m3 the same way: a video's entry is its best ADMITTED
+ *   row, a video without an admitted row never appears.
+ *   Result: the lists equal, bit for bit, the plain entry point's lists over the index made by gathering the admitted rows in
+ *     order -- a score does not depend on where its row sits in a tile, a split or an index -- with top_row the row in THIS index
+ *     and top_video the video of THIS v_off; equal scores by ascending row.  When fewer than k rows / videos are admitted the tail
+ *     holds empty slots (-inf, row 0x7fffffff, video -1), which tan_topk_fold sorts last.  A filter that admits every row gives
+ *     exactly the plain entry point's lists.
+ *   A split walks a contiguous range of the image's tile list and streams only those tiles: the sweep's work follows the listed
+ *     tiles, not N.  n_listed is read on the device: the grid is sized from (Q, N, splits) as for the plain call, and a workgroup
+ *     whose range is empty writes empty lists and leaves.  The result does not depend on `splits`; no float atomics.
+ *   filt: an image built for the same N (16-byte aligned).  An image of another N or a damaged one is the CALLER's error: list
+ *     positions and tile numbers are clamped, nothing is read or written out of bounds, and the lists are unspecified.
+ *   ws: tan_rank_topk_ws_bytes(Q, N, k) / tan_rank_topk_video_ws_bytes(Q, N, n_videos, k) bytes, as for the plain calls.
+ *   Argument rules otherwise as tan_rank_topk / tan_rank_topk_video; k == 0 or a NULL filt: TAN_ERR_BAD_ARG, nothing launched.  */
+long tan_row_filter_bytes(long N);
+int tan_row_filter_build(const int* spans, long n_spans, long N, void* filt, void* stream);
+int tan_rank_topk_filtered(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const void* filt, int k, int splits,
+                           float* top_score, int* top_row, void* ws, void* stream);
+int tan_rank_topk_filtered_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                                const void* filt, int k, int splits, float* top_score, int* top_row, void* ws, void* stream);
+int tan_rank_topk_video_filtered(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos,
+                                 const void* filt, int k, int splits, float* top_score, int* top_row, int* top_video, void* ws,
+                                 void* stream);
+int tan_rank_topk_video_filtered_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N,
+                                      int C, const int* v_off, long n_videos, const void* filt, int k, int splits, float* top_score,
+                                      int* top_row, int* top_video, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,9 @@
 // tan_sequence_topk ranks videos by the best ORDER-PRESERVING path of a sequence of up to 32 query rows (tan_decode.hip's recurrence
 // fused into the sweep: seq_kernel, which shares the load / MFMA routine tile_scores with rank_kernel), and tan_sequence_scores
 // writes the winners' step x second scores, with the sweep's bits, for tan_monotonic_decode to backtrack.
+// tan_rank_topk_filtered / tan_rank_topk_video_filtered sweep only the rows a FILTER admits (rank_kernel's FILTER mode): the image
+// tan_row_filter_build makes from row spans lists the 64-row tiles that hold an admitted row, with a row mask each; a split walks a
+// range of that list and masks the other rows, so the lists are the plain sweep's over the gathered admitted rows, bit for bit.
 //
 // tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
 // of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
@@ -43,6 +46,7 @@ constexpr int CAP = 64;                     // candidate slots per query
 constexpr int KMAX = 32;
 constexpr int MAX_SPLITS = 256;
 constexpr int SENT_ROW = 0x7fffffff;
+constexpr int FILT_HEAD = 4;                // int32 words before a filter image's tile list (include/tan_hip.h)
 
 template <typename T> struct RCfg;
 template <> struct RCfg<bf16_t> { static constexpr int KC = 128, LD = 136; };     // 256 B of a row per chunk; 272-B pitch: b128 reads conflict-free
@@ -196,7 +200,13 @@ __device__ __forceinline__ void tile_scores(T* tile, float* sc, int tid, int lan
 // buffers: a wave may start tile t + 1 while another still reads tile t's).  Compaction keeps the k best distinct videos
 // (distinct64) and the threshold is the k-th distinct video's score, -inf while fewer are held: a row below it cannot enter the
 // final list, and a dropped entry is dominated by a kept row of its own video.  Nothing in the compaction touches global memory.
-template <typename T, bool PAIR, bool VIDEO = false>
+// FILTER = true: the sweeps of tan_rank_topk_filtered / _video_filtered.  `pair` carries the filter IMAGE (include/tan_hip.h; these
+// sweeps have no paired rows, and the existing instantiations keep their arguments): a split walks a contiguous range of the image's
+// tile list -- the loop counter is a LIST position, the tile it names and its row mask are fetched one position ahead -- and a row
+// whose mask bit is clear is neither a candidate nor threshold material, in the one-video fast path too.  tvid is indexed by list
+// position.  The count of listed tiles is read here, so the grid does not depend on it; a workgroup whose range is empty writes
+// empty lists and leaves before it loads its queries.  Every other instantiation is compiled as before (`if constexpr`).
+template <typename T, bool PAIR, bool VIDEO = false, bool FILTER = false>
 __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Q, long N,
                                                    const int* __restrict__ pair, int k, long tiles_per_split, long n_tiles,
                                                    float* __restrict__ dscore, int* __restrict__ higher, int* __restrict__ ties,
@@ -223,6 +233,32 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
     const long qme = qblk + wave * 32 + col;
     const bool qok = qme < Q;
 
+    // FILTER: the split's range [f0, f1) of the image's tile list; whatever the image holds, every position and tile is in range
+    long f0 = 0, f1 = 0;
+    const int* ftile = nullptr;
+    const unsigned long long* fmask = nullptr;
+    if constexpr (FILTER) {
+        ftile = pair + FILT_HEAD;
+        fmask = reinterpret_cast<const unsigned long long*>(pair + FILT_HEAD + (n_tiles + 1) / 2 * 2);
+        long nl = pair[0];
+        nl = nl < 0 ? 0 : (nl > n_tiles ? n_tiles : nl);
+        const long per = (nl + gridDim.y - 1) / gridDim.y;
+        f0 = (long)blockIdx.y * per;
+        f1 = f0 + per < nl ? f0 + per : nl;
+        if (f0 >= f1) {                                            // block-uniform: nothing listed for this split
+            for (int e = tid; e < BQ * k; e += 256) {
+                const long q = qblk + e / k;
+                if (q < Q) {
+                    const long o = ((long)blockIdx.y * Q + q) * k + e % k;
+                    part_s[o] = -INFINITY;
+                    part_n[o] = SENT_ROW;
+                    if constexpr (VIDEO) part_v[o] = -1;
+                }
+            }
+            return;
+        }
+    }
+
     frag_t qf[NFR];                                                // the wave's 32 queries, resident
     {
         const T* qrow = Tq + (qok ? qme : Q - 1) * RC;
@@ -235,9 +271,14 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
 
     long t0, t1;
     if (PAIR) { t0 = 0; t1 = 2; }
+    else if (FILTER) { t0 = f0; t1 = f1; }
     else { t0 = (long)blockIdx.y * tiles_per_split; t1 = t0 + tiles_per_split < n_tiles ? t0 + tiles_per_split : n_tiles; }
+    auto listed = [&](long it) {                                   // FILTER: the tile at list position `it`
+        const long t = ftile[it];
+        return t < 0 ? 0 : (t >= n_tiles ? n_tiles - 1 : t);
+    };
 
-    const bool counting = !PAIR && !VIDEO && pair != nullptr;
+    const bool counting = !PAIR && !VIDEO && !FILTER && pair != nullptr;
     const float dq = (counting && qok) ? dscore[qme] : 0.0f;
     int hi = 0, eq = 0, fill = 0;
     float thr = -INFINITY, dval = 0.0f;
@@ -305,20 +346,33 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
     if constexpr (VIDEO) {
         if (t0 < t1) tv_next = tvid[t0];
     }
-    if (t0 < t1) issue(t0, 0);
-    for (long t = t0; t < t1; ++t) {
+    long ft_next = 0;                                              // FILTER: the next position's tile and row mask
+    unsigned long long fm_next = 0;
+    if constexpr (FILTER) {
+        ft_next = listed(t0);                                      // t0 < t1 here
+        fm_next = fmask[t0];
+        issue(ft_next, 0);
+    } else {
+        if (t0 < t1) issue(t0, 0);
+    }
+    for (long it = t0; it < t1; ++it) {                            // `it`: the tile, or with FILTER its position in the image's list
+        const long t = FILTER ? ft_next : it;
+        const unsigned long long rows_in = fm_next;                // FILTER: bit r = row 64 t + r is admitted
+        if constexpr (FILTER) {
+            if (it + 1 < t1) { ft_next = listed(it + 1); fm_next = fmask[it + 1]; }
+        }
         const int2 tv = tv_next;
         if constexpr (VIDEO) {
-            if (t + 1 < t1) tv_next = tvid[t + 1];
+            if (it + 1 < t1) tv_next = tvid[it + 1];
             if (tv.x != tv.y && tid < BN) {                        // a video boundary in the tile: every row's video, for the epilogue
                 const long n = t * BN + tid;
-                vt[(t & 1) * BN + tid] = video_search(v_off, n < N ? n : N - 1, tv.x, tv.y);
+                vt[(it & 1) * BN + tid] = video_search(v_off, n < N ? n : N - 1, tv.x, tv.y);
             }
         }
         f32x16 acc[2];
         tile_scores<T>(tile, sc, tid, lane, pre, psc, qf, qs, acc, [&](int kc) {
             if (kc + 1 < NCH) issue(t, kc + 1);
-            else if (t + 1 < t1) issue(t + 1, 0);
+            else if (it + 1 < t1) issue(FILTER ? ft_next : t + 1, 0);
         });
         if (PAIR) {
             if (t == (wave >> 1)) {
@@ -335,12 +389,16 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
                 float ms = -INFINITY;
                 int mn = SENT_ROW;
 #pragma unroll
-                for (int rt = 0; rt < 2; ++rt)
+                for (int rt = 0; rt < 2; ++rt) {
+                    const unsigned mine = (unsigned)(rows_in >> (rt * 32 + 4 * (lane >> 5)));    // FILTER: bit acc_row(r, 0) = the lane's row r
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const long n = r0 + rt * 32 + acc_row(r, lane);
-                        if (n < N && better(acc[rt][r], (int)n, ms, mn)) { ms = acc[rt][r]; mn = (int)n; }
+                        bool valid = n < N;
+                        if constexpr (FILTER) valid = valid && ((mine >> acc_row(r, 0)) & 1);
+                        if (valid && better(acc[rt][r], (int)n, ms, mn)) { ms = acc[rt][r]; mn = (int)n; }
                     }
+                }
                 const float os = __shfl_xor(ms, 32, 64);
                 const int on = __shfl_xor(mn, 32, 64);
                 if (better(os, on, ms, mn)) { ms = os; mn = on; }
@@ -355,9 +413,11 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
         for (int rt = 0; rt < 2; ++rt) {
             const long nbase = t * BN + rt * 32;
             unsigned mask = 0;
+            const unsigned mine = (unsigned)(rows_in >> (rt * 32 + 4 * (lane >> 5)));            // FILTER: bit acc_row(r, 0) = the lane's row r
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const bool valid = nbase + acc_row(r, lane) < N;
+                bool valid = nbase + acc_row(r, lane) < N;
+                if constexpr (FILTER) valid = valid && ((mine >> acc_row(r, 0)) & 1);
                 const float v = acc[rt][r];
                 hi += (valid && v > dq) ? 1 : 0;
                 eq += (valid && v == dq) ? 1 : 0;
@@ -372,7 +432,7 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
                 if ((mask >> r) & 1) {
                     bs[off] = acc[rt][r];
                     bn[off] = (int)(nbase + acc_row(r, lane));
-                    if constexpr (VIDEO) bv[off] = vt[(t & 1) * BN + rt * 32 + acc_row(r, lane)];
+                    if constexpr (VIDEO) bv[off] = vt[(it & 1) * BN + rt * 32 + acc_row(r, lane)];
                     ++off;
                 }
             fill += need;
@@ -480,6 +540,104 @@ __global__ void __launch_bounds__(256) tile_video_kernel(const int* __restrict__
         found[e] = video_search(v_off, n, 0, n_videos - 1);
     }
     tvid[t] = make_int2(found[0], found[1]);
+}
+
+// tile_video_kernel over a filter image's tile list: tvid[i] = the videos of the first and last row of the tile at list position i
+__global__ void __launch_bounds__(256) tile_video_listed_kernel(const int* __restrict__ v_off, int n_videos, long N, long n_tiles,
+                                                                const int* __restrict__ filt, int2* __restrict__ tvid) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    long nl = filt[0];
+    nl = nl > n_tiles ? n_tiles : nl;
+    if (i >= nl) return;
+    long t = filt[FILT_HEAD + i];
+    t = t < 0 ? 0 : (t >= n_tiles ? n_tiles - 1 : t);
+    int found[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const long n = e == 0 ? t * BN : (t * BN + BN < N ? t * BN + BN : N) - 1;
+        found[e] = video_search(v_off, n, 0, n_videos - 1);
+    }
+    tvid[i] = make_int2(found[0], found[1]);
+}
+
+// ---- the filter image of tan_row_filter_build (layout: include/tan_hip.h), in int32 words with T tiles, T2 = T rounded up to 2 and
+// NB = ceil(T / 256):  [0] listed tiles, [1] T, [2..3] 0 | tile list [T2] | row masks u64 [T] | scratch: every tile's mask u64 [T],
+// then NB block counts, scanned in place.  Three launches (counts / scan / fill), no atomics: the image does not depend on timing.
+inline long filt_words(long T) { return FILT_HEAD + (T + 1) / 2 * 2 + 4 * T + (T + 255) / 256; }
+
+// launch 1: one thread per tile -- the first span that ends above the tile's first row by binary search, then the spans that begin
+// inside the tile (at most 64 when they keep their contract, and never more are looked at); a block's admitted tiles are counted
+__global__ void __launch_bounds__(256) filter_mask_kernel(const int* __restrict__ spans, long n_spans, long N, long T,
+                                                          int* __restrict__ img) {
+    unsigned long long* dense = reinterpret_cast<unsigned long long*>(img + FILT_HEAD + (T + 1) / 2 * 2) + T;
+    int* bcnt = img + FILT_HEAD + (T + 1) / 2 * 2 + 4 * T;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long m = 0;
+    if (t < T) {
+        const long r0 = t * BN, r1 = r0 + BN < N ? r0 + BN : N;
+        long lo = 0, hi = n_spans;
+        while (lo < hi) {
+            const long mid = (lo + hi) >> 1;
+            if (spans[2 * mid + 1] > r0) hi = mid; else lo = mid + 1;
+        }
+        for (int j = 0; j < BN && lo + j < n_spans; ++j) {
+            const long a = spans[2 * (lo + j)], b = spans[2 * (lo + j) + 1];
+            if (a >= r1) break;
+            const long ca = a < r0 ? r0 : a, cb = b > r1 ? r1 : b;  // cut to the tile, which is cut to the index
+            if (cb > ca) m |= (cb - ca == 64 ? ~0ull : ((1ull << (cb - ca)) - 1)) << (ca - r0);
+        }
+        dense[t] = m;
+    }
+    const int c = __syncthreads_count(m != 0);
+    if (threadIdx.x == 0) bcnt[blockIdx.x] = c;
+}
+
+// an exclusive scan over the block's 256 values; `total`: their sum.  All 256 threads must call it.
+__device__ __forceinline__ int block_scan256(int v, int* wsum, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int l = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += l;
+    }
+    __syncthreads();                                               // the previous call's readers are done
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += wsum[w];
+    total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    return before + inc - v;
+}
+
+// launch 2: ONE block turns the block counts into each block's first list position and writes the header
+__global__ void __launch_bounds__(256) filter_scan_kernel(long T, int* __restrict__ img) {
+    __shared__ int wsum[4];
+    int* bcnt = img + FILT_HEAD + (T + 1) / 2 * 2 + 4 * T;
+    const long NB = (T + 255) / 256;
+    int carry = 0;
+    for (long b0 = 0; b0 < NB; b0 += 256) {
+        const long b = b0 + threadIdx.x;
+        int total;
+        const int ex = block_scan256(b < NB ? bcnt[b] : 0, wsum, total);
+        if (b < NB) bcnt[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) { img[0] = carry; img[1] = (int)T; img[2] = 0; img[3] = 0; }
+}
+
+// launch 3: an admitted tile's list position = its block's first position + the admitted tiles before it in the block
+__global__ void __launch_bounds__(256) filter_fill_kernel(long T, int* __restrict__ img) {
+    __shared__ int wsum[4];
+    int* tiles = img + FILT_HEAD;
+    unsigned long long* masks = reinterpret_cast<unsigned long long*>(img + FILT_HEAD + (T + 1) / 2 * 2);
+    const unsigned long long* dense = masks + T;
+    const int* bcnt = img + FILT_HEAD + (T + 1) / 2 * 2 + 4 * T;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long m = t < T ? dense[t] : 0;
+    int total;
+    const long pos = (long)bcnt[blockIdx.x] + block_scan256(m != 0 ? 1 : 0, wsum, total);
+    if (m != 0 && pos >= 0 && pos < T) { tiles[pos] = (int)t; masks[pos] = m; }
 }
 
 // ---- ordered-sequence search: videos ranked by the best order-preserving path of a sequence of steps (include/tan_hip.h) ----
@@ -959,6 +1117,55 @@ int video_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_of
     return 0;
 }
 
+// the filtered sweeps: rank_launch / video_launch without the pair launch, the grid sized from (Q, N, splits) as theirs, the filter
+// image in the kernel's `pair` argument.  ws: as the plain launches lay it out.
+template <typename T>
+int rank_filtered_launch(const void* Tq, const void* Vn, long Q, long N, const int* filt, int k, int splits, float* top_s, int* top_n,
+                         void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
+    const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
+    long tps;
+    const int ns = n_splits(Q, N, splits, &tps);
+    float* part_s = (float*)ws + (Q + 3) / 4 * 4;
+    int* part_n = (int*)(part_s + (long)ns * Q * k);
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, false, true>, sweep_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((rank_kernel<T, false, false, true>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), sweep_lds<T>(), st,
+                       (const T*)Tq, (const T*)Vn, Q, N, filt, k, tps, n_tiles, (float*)nullptr, (int*)nullptr, (int*)nullptr, part_s,
+                       part_n, q_scale, v_scale, (const int2*)nullptr, (const int*)nullptr, (int*)nullptr);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, Q, k, ns, top_s, top_n);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int video_filtered_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_off, int n_videos, const int* filt, int k,
+                          int splits, float* top_s, int* top_n, int* top_v, void* ws, hipStream_t st, const float* q_scale = nullptr,
+                          const float* v_scale = nullptr) {
+    long tps;
+    const int ns = n_splits(Q, N, splits, &tps);
+    const long n_tiles = n_index_tiles(N);
+    int2* tvid = (int2*)ws;
+    float* part_s = (float*)(tvid + (n_tiles + 1) / 2 * 2);
+    int* part_n = (int*)(part_s + (long)ns * Q * k);
+    int* part_v = part_n + (long)ns * Q * k;
+    hipLaunchKernelGGL(tile_video_listed_kernel, dim3(cdiv(n_tiles, 256)), dim3(256), 0, st, v_off, n_videos, N, n_tiles, filt, tvid);
+    TAN_LAUNCH_CHECK();
+    static std::atomic<unsigned long long> lds_done{0};
+    constexpr int lds = sweep_lds<T, true>();
+    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, true, true>, lds, lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((rank_kernel<T, false, true, true>), dim3((unsigned)((Q + BQ - 1) / BQ), (unsigned)ns), dim3(256), lds, st,
+                       (const T*)Tq, (const T*)Vn, Q, N, filt, k, tps, n_tiles, (float*)nullptr, (int*)nullptr, (int*)nullptr, part_s,
+                       part_n, q_scale, v_scale, (const int2*)tvid, v_off, part_v);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, Q, k, ns, top_s,
+                       top_n, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
 template <typename T>
 int extent_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_off, int n_videos, int k, const float* top_s,
                   const int* top_n, const int* top_v, float width, int* start, int* end, hipStream_t st,
@@ -1085,6 +1292,68 @@ extern "C" int tan_rank_topk_video_e4m3(const void* Tq, const float* q_scale, co
     TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
     return video_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, (hipStream_t)stream,
                                 q_scale, v_scale);
+}
+
+extern "C" long tan_row_filter_bytes(long N) {
+    if (N < 1 || N >= (1L << 31)) return TAN_ERR_BAD_ARG;
+    return (filt_words(n_index_tiles(N)) * 4 + 15) / 16 * 16;
+}
+
+extern "C" int tan_row_filter_build(const int* spans, long n_spans, long N, void* filt, void* stream) {
+    TAN_REQUIRE(spans && filt && n_spans >= 1 && n_spans < (1L << 30) && N >= 1 && N < (1L << 31));
+    TAN_REQUIRE((uintptr_t)filt % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    const long T = n_index_tiles(N);
+    hipLaunchKernelGGL(filter_mask_kernel, dim3(cdiv(T, 256)), dim3(256), 0, st, spans, n_spans, N, T, (int*)filt);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, st, T, (int*)filt);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(filter_fill_kernel, dim3(cdiv(T, 256)), dim3(256), 0, st, T, (int*)filt);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tan_rank_topk_filtered(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const void* filt, int k,
+                                      int splits, float* top_score, int* top_row, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && Vn && filt && top_score && top_row && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= N && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16 ? rank_filtered_launch<bf16_t>(Tq, Vn, Q, N, (const int*)filt, k, splits, top_score, top_row, ws, st)
+                             : rank_filtered_launch<float>(Tq, Vn, Q, N, (const int*)filt, k, splits, top_score, top_row, ws, st);
+}
+
+extern "C" int tan_rank_topk_filtered_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N,
+                                           int C, const void* filt, int k, int splits, float* top_score, int* top_row, void* ws,
+                                           void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && filt && top_score && top_row && ws);
+    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= N && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
+    return rank_filtered_launch<e4m3_t>(Tq, Vn, Q, N, (const int*)filt, k, splits, top_score, top_row, ws, (hipStream_t)stream, q_scale,
+                                        v_scale);
+}
+
+extern "C" int tan_rank_topk_video_filtered(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off,
+                                            long n_videos, const void* filt, int k, int splits, float* top_score, int* top_row,
+                                            int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && Vn && v_off && filt && top_score && top_row && top_video && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16 ? video_filtered_launch<bf16_t>(Tq, Vn, Q, N, v_off, (int)n_videos, (const int*)filt, k, splits, top_score,
+                                                             top_row, top_video, ws, st)
+                             : video_filtered_launch<float>(Tq, Vn, Q, N, v_off, (int)n_videos, (const int*)filt, k, splits, top_score,
+                                                            top_row, top_video, ws, st);
+}
+
+extern "C" int tan_rank_topk_video_filtered_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q,
+                                                 long N, int C, const int* v_off, long n_videos, const void* filt, int k, int splits,
+                                                 float* top_score, int* top_row, int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && v_off && filt && top_score && top_row && top_video && ws);
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
+    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
+    return video_filtered_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, (const int*)filt, k, splits, top_score, top_row, top_video,
+                                         ws, (hipStream_t)stream, q_scale, v_scale);
 }
 
 extern "C" int tan_moment_extent(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos, int k,

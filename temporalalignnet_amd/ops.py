@@ -426,6 +426,88 @@ def rank_topk_video(tq, vn, v_off, k, *, q_scale=None, v_scale=None, splits=0, c
     return top_s, top_r, top_v
 
 
+def row_filter_bytes(N):
+    n = _lib.lib().tan_row_filter_bytes(N)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_row_filter_bytes({N}): bad argument")
+    return n
+
+
+def row_filter_build(spans, N, out=None):
+    """The filter image of row spans over an index of N rows (tan_row_filter_build; layout in include/tan_hip.h): spans [n, 2] int32
+    (device, contiguous), [lo, hi) each, ascending, disjoint, non-empty, inside [0, N) -- the caller's contract.  Returns the image,
+    uint8 [row_filter_bytes(N)]; out: caller-owned memory instead of a fresh one.  Nothing is read back."""
+    assert spans.dtype == torch.int32 and spans.dim() == 2 and spans.shape[1] == 2 and spans.is_contiguous()
+    need = _lib.lib().tan_row_filter_bytes(N)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if out is None:
+            out = torch.empty(need, dtype=torch.uint8, device=spans.device)
+        assert out.dtype == torch.uint8 and out.numel() >= need and out.is_contiguous()
+    _lib.check(_lib.lib().tan_row_filter_build(_ptr(spans), spans.shape[0], N, _ptr(out), _stream()), "tan_row_filter_build")
+    return out
+
+
+def rank_topk_filtered(tq, vn, filt, k, *, q_scale=None, v_scale=None, splits=0, out=None, ws=None):
+    """The k best ADMITTED rows per query (tan_rank_topk_filtered / _e4m3): tq [Q, 512], vn [N, 512], both bf16, both f32, or both
+    uint8 e4m3 codes with q_scale [Q] / v_scale [N]; filt: `row_filter_build`'s image for N rows.  Returns (top_score [Q, k] f32,
+    top_row [Q, k] int32: rows of vn), by descending score, equal scores by ascending row: bit for bit `rank_topk` over the
+    gathered admitted rows; with fewer than k of them the tail is (-inf, 0x7fffffff).  splits: 0 = automatic; the result does not
+    depend on it.  out / ws: caller-owned outputs (the same 2-tuple) and scratch (uint8, >= rank_topk_ws_bytes) instead of fresh
+    ones."""
+    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype
+    e4m3 = tq.dtype == torch.uint8
+    if (q_scale is not None) != e4m3 or (v_scale is not None) != e4m3:
+        raise TypeError("rank_topk_filtered: q_scale / v_scale go with uint8 e4m3 codes, and only with them")
+    Q, N, dev = tq.shape[0], vn.shape[0], tq.device
+    if e4m3:
+        assert q_scale.shape == (Q,) and v_scale.shape == (N,) and q_scale.is_contiguous() and v_scale.is_contiguous()
+    L = _lib.lib()
+    assert filt.dtype == torch.uint8 and filt.is_contiguous() and filt.numel() >= max(L.tan_row_filter_bytes(N), 0)
+    if out is None:
+        out = (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev))
+    top_s, top_r = out
+    need = L.tan_rank_topk_ws_bytes(Q, N, k)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    if e4m3:
+        _lib.check(L.tan_rank_topk_filtered_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(filt), k,
+                                                 splits, _f32(top_s), _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk_filtered_e4m3")
+    else:
+        _lib.check(L.tan_rank_topk_filtered(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(filt), k, splits, _f32(top_s),
+                                            _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk_filtered")
+    return top_s, top_r
+
+
+def rank_topk_video_filtered(tq, vn, v_off, filt, k, *, q_scale=None, v_scale=None, splits=0, out=None, ws=None):
+    """`rank_topk_video` over the admitted rows of filt (`row_filter_build`'s image for N rows; tan_rank_topk_video_filtered /
+    _e4m3): a video's entry is its best admitted row, a video without one never appears, and with fewer than k admitted videos the
+    tail is (-inf, 0x7fffffff, -1).  Everything else as `rank_topk_video`."""
+    e4m3 = _video_args("rank_topk_video_filtered", tq, vn, v_off, q_scale, v_scale)
+    Q, N, nv, dev = tq.shape[0], vn.shape[0], v_off.numel() - 1, tq.device
+    L = _lib.lib()
+    assert filt.dtype == torch.uint8 and filt.is_contiguous() and filt.numel() >= max(L.tan_row_filter_bytes(N), 0)
+    if out is None:
+        out = (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev),
+               torch.empty(Q, k, dtype=torch.int32, device=dev))
+    top_s, top_r, top_v = out
+    need = L.tan_rank_topk_video_ws_bytes(Q, N, nv, k)
+    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    if e4m3:
+        _lib.check(L.tan_rank_topk_video_filtered_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(v_off),
+                                                       nv, _ptr(filt), k, splits, _f32(top_s), _ptr(top_r), _ptr(top_v), _ptr(ws),
+                                                       _stream()), "tan_rank_topk_video_filtered_e4m3")
+    else:
+        _lib.check(L.tan_rank_topk_video_filtered(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(v_off), nv, _ptr(filt), k, splits,
+                                                  _f32(top_s), _ptr(top_r), _ptr(top_v), _ptr(ws), _stream()),
+                   "tan_rank_topk_video_filtered")
+    return top_s, top_r, top_v
+
+
 def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scale=None, v_scale=None, out=None):
     """(start, end) int32 [Q, k]: for every hit of `rank_topk_video`'s lists, the contiguous run of index rows around top_row,
     inside the hit's video, whose score is >= top_score - width -- global rows, inclusive (tan_moment_extent / _e4m3; the exact

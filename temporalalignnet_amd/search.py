@@ -30,6 +30,10 @@ sentence is ranked against all of it:
     from pinned host memory.  Every shard is swept on its own and `tan_topk_fold` folds the per-shard lists on the device under the
     sweeps' own order: `search`, `search_moments` and `search_sequences` return what they return for `VideoIndex.concat` of the
     shards, bit for bit (`query --shard`, `query --host-resident`, `merge`).
+  * `restrict`: `index.restrict(videos=, exclude=, windows=)` gives a `RowFilter` -- a playlist, the videos already shown, known
+    time windows -- that `search`, `search_moments` and `search_rerank` take as `restrict=`.  The sweep walks only the 64-row tiles
+    that hold an admitted row (`tan_row_filter_build`, `tan_rank_topk_filtered`) and returns those rows with the unrestricted
+    sweep's scores; a host-resident shard without an admitted row is not copied (`query --only / --exclude / --within`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -37,6 +41,7 @@ sentence is ranked against all of it:
     python -m temporalalignnet_amd.search query ... --sequence "crack two eggs" "whisk them" "pour into the pan"
     python -m temporalalignnet_amd.search index ... --keep-stem;  ... query ... --rerank [--pool 32] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --index I0.npz --shard I1.npz --shard I2.npz [--host-resident] "crack two eggs" ...
+    python -m temporalalignnet_amd.search query ... --only VID --only-file vids.txt --exclude VID --within VID:30-90 "crack two eggs" ...
     python -m temporalalignnet_amd.search merge --out I.npz I0.npz I1.npz ...
 """
 from __future__ import annotations
@@ -114,6 +119,130 @@ def _index_chunks(videos, seq_len, windows_per_pass):
         yield _IndexChunk(items, seq_len, windows_per_pass)
 
 
+def _video_numbers(vids, names, what):
+    """Video numbers named by `names` (vid strings: EVERY video that carries the string; or video numbers), ascending, distinct."""
+    by_name = None
+    out = set()
+    for name in names:
+        if isinstance(name, str):
+            if by_name is None:
+                by_name = {}
+                for v, s in enumerate(vids):
+                    by_name.setdefault(s, []).append(v)
+            if name not in by_name:
+                raise KeyError(f"{what}: no video {name!r} in the index")
+            out.update(by_name[name])
+        else:
+            v = int(name)
+            if v != name or not 0 <= v < len(vids):
+                raise KeyError(f"{what}: no video number {name!r} in the index")
+            out.add(v)
+    return sorted(out)
+
+
+def restrict_spans(v_off, vids, videos=None, exclude=None, windows=None):
+    """(spans int64 [n, 2]: the admitted global rows as merged [lo, hi) spans, ascending; n_videos: videos with an admitted row) --
+    the arithmetic of `VideoIndex.restrict` / `ShardedIndex.restrict`, on the host."""
+    v_off = np.asarray(v_off, dtype=np.int64)
+    admitted = list(range(len(vids))) if videos is None else _video_numbers(vids, videos, "restrict(videos)")
+    if exclude is not None:
+        drop = set(_video_numbers(vids, exclude, "restrict(exclude)"))
+        admitted = [v for v in admitted if v not in drop]
+    cut = {}
+    for name, first, last in (windows or ()):
+        for v in _video_numbers(vids, [name], "restrict(windows)"):
+            vlen = int(v_off[v + 1] - v_off[v])
+            a, b = max(int(first), 0), min(int(last), vlen - 1)
+            cut.setdefault(v, [])
+            if a <= b:
+                cut[v].append((int(v_off[v]) + a, int(v_off[v]) + b + 1))
+    spans, n_videos = [], 0
+    for v in admitted:
+        mine = sorted(cut[v]) if v in cut else [(int(v_off[v]), int(v_off[v + 1]))]
+        n_videos += bool(mine)
+        for lo, hi in mine:
+            if spans and lo <= spans[-1][1]:
+                spans[-1][1] = max(spans[-1][1], hi)
+            else:
+                spans.append([lo, hi])
+    return np.asarray(spans, dtype=np.int64).reshape(-1, 2), n_videos
+
+
+class RowFilter:
+    """What `index.restrict(...)` returns and `search(..., restrict=)` takes: the rows of ONE index a search may return.
+      spans [n, 2]   int64, global rows [lo, hi), ascending, merged (adjacent videos and overlapping windows give one span)
+      n_rows         admitted rows;  n_videos: videos with an admitted row
+      windowed       built with `windows`: `search_rerank` refuses it
+      shards()       the shards that hold an admitted row, ascending (a `VideoIndex` is shard 0)
+      shard_spans(s) / shard_rows(s) / shard_videos(s)   shard s's part: spans in the shard's OWN rows, admitted rows and videos
+      image(s)       the device image of shard s's spans (`ops.row_filter_build`), built on first use and kept
+    It belongs to the index that made it and refuses any other."""
+
+    def __init__(self, index, spans, n_videos, windowed):
+        self._index, self.spans, self.n_videos, self.windowed = index, spans, int(n_videos), bool(windowed)
+        self.n_rows = int((spans[:, 1] - spans[:, 0]).sum())
+        if self.n_rows == 0:
+            raise ValueError("restrict: the filter admits no row")
+        sharded = isinstance(index, ShardedIndex)
+        row_base = index.row_base if sharded else np.array([0, len(index)], dtype=np.int64)
+        shard_v_off = [sh.v_off for sh in index.shards] if sharded else [index.v_off]
+        self._parts, self._images = {}, {}
+        for s in range(len(row_base) - 1):
+            lo, hi = np.maximum(spans[:, 0], row_base[s]), np.minimum(spans[:, 1], row_base[s + 1])
+            local = np.stack((lo, hi), 1)[lo < hi] - row_base[s]
+            if len(local):
+                first = np.searchsorted(shard_v_off[s], local[:, 0], side="right") - 1         # the videos a span touches
+                last = np.searchsorted(shard_v_off[s], local[:, 1] - 1, side="right") - 1
+                videos = int((last - first + 1).sum() - (first[1:] == last[:-1]).sum())         # spans ascend: only neighbours share one
+                self._parts[s] = (local, int((local[:, 1] - local[:, 0]).sum()), videos)
+
+    def check(self, index):
+        if index is not self._index:
+            raise ValueError("this RowFilter was made by another index's restrict()")
+
+    def shards(self):
+        return sorted(self._parts)
+
+    def ready(self):
+        """`shards()`, with every image built: nothing of the filter is left to do between the shards' sweeps"""
+        return [s for s in self.shards() if self.image(s) is not None]
+
+    def shard_spans(self, s):
+        return self._parts[s][0]
+
+    def shard_rows(self, s):
+        return self._parts[s][1]
+
+    def shard_videos(self, s):
+        return self._parts[s][2]
+
+    def image(self, s=0):
+        if s not in self._images:
+            sharded = isinstance(self._index, ShardedIndex)
+            n = len(self._index.shards[s]) if sharded else len(self._index)
+            spans = torch.from_numpy(self.shard_spans(s).astype(np.int32)).to(self._index.device)
+            self._images[s] = ops.row_filter_build(spans, n)
+        return self._images[s]
+
+    def clip(self, row, start, end):
+        """Global rows: [start, end] cut to the admitted span that holds `row`."""
+        i = np.searchsorted(self.spans[:, 0], row, side="right") - 1
+        return np.maximum(start, self.spans[i, 0]), np.minimum(end, self.spans[i, 1] - 1)
+
+
+def _restrict(index, videos, exclude, windows):
+    spans, n_videos = restrict_spans(index.v_off, index.vids, videos, exclude, windows)
+    return RowFilter(index, spans, n_videos, windows is not None)
+
+
+_RESTRICT_DOC = """The `RowFilter` that admits only some of this index's rows, for `search`, `search_moments` and `search_rerank`
+        (`restrict=`).  videos: the videos to search (default: all); exclude: videos to leave out; both iterables of vid strings or
+        video numbers -- a string names EVERY video that carries it (equal strings are distinct videos), an unknown one raises
+        KeyError.  windows: iterable of (video, first_second, last_second), inclusive, clamped to the video; several windows of a
+        video are merged; an admitted video that `windows` names is narrowed to them, the others stay whole.  ValueError when
+        nothing is admitted."""
+
+
 class VideoIndex:
     """feat [sum vlen, 512] (device, bf16 or f32): one row per second; v_off [n_videos + 1]: each video's first row; vids.
     An e4m3 index holds feat as uint8 codes and scale [sum vlen] f32, one power of two per row; scale is None otherwise.
@@ -180,6 +309,11 @@ class VideoIndex:
 
     def __len__(self):
         return int(self.feat.shape[0])
+
+    def restrict(self, videos=None, exclude=None, windows=None):
+        return _restrict(self, videos, exclude, windows)
+
+    restrict.__doc__ = _RESTRICT_DOC
 
     def locate(self, rows):
         """index rows -> (video number, second)"""
@@ -276,6 +410,12 @@ class ShardedIndex:
 
     def __len__(self):
         return int(self.row_base[-1])
+
+    def restrict(self, videos=None, exclude=None, windows=None):
+        return _restrict(self, videos, exclude, windows)
+
+    restrict.__doc__ = _RESTRICT_DOC + """  Videos count over all shards, in shard order; the spans are cut per shard, and a search
+        leaves out the shards without an admitted row (resident="host": they are not copied)."""
 
     def locate(self, shard, row):
         """(shard, shard-local row) -> (global video number, second)"""
@@ -411,31 +551,40 @@ def _read_lists(run):
 
 
 @torch.no_grad()
-def search(index, model, embed_text, queries, k=10, splits=0):
+def search(index, model, embed_text, queries, k=10, splits=0, restrict=None):
     """Per query the k best seconds of the corpus: [[(vid, second, score)] * k] * len(queries), by descending score (equal scores
     by index row).  score = <index row, unit text feature>: the stitched dual cosine; / 0.07 gives the evaluation's logit.
     `index`: a `VideoIndex`, or a `ShardedIndex` -- then exactly what `VideoIndex.concat` of its shards gives (as for
-    `search_moments` and `search_sequences`): one sweep and one `tan_topk_fold` per shard, one read-back at the end."""
+    `search_moments` and `search_sequences`): one sweep and one `tan_topk_fold` per shard, one read-back at the end.
+    restrict: a `RowFilter` of this index (`index.restrict(...)`): only its rows are swept (`tan_rank_topk_filtered`) and returned,
+    with the scores and the order the unrestricted call gives them; k is clamped to the admitted rows."""
     queries = list(queries)
     if not queries:
         return []
-    k = min(int(k), len(index))
+    if restrict is not None:
+        restrict.check(index)
+    k = min(int(k), len(index) if restrict is None else restrict.n_rows)
     if not 1 <= k <= 32:
         raise ValueError("search: k must lie in [1, 32]")
     tq = query_features(index, model, embed_text, queries)
     if isinstance(index, ShardedIndex):
         run = _run_lists(len(queries), k, 0, index.device)
-        for i, (s, feat, scale, _) in enumerate(index.shard_views()):
-            k_s = min(k, feat.shape[0])
-            if index.e4m3:
-                _, _, score, row = ops.rank_topk_e4m3(*tq, feat, scale, None, k_s, splits=splits)
+        for i, (s, feat, scale, _) in enumerate(index.shard_views(None if restrict is None else restrict.ready())):
+            if restrict is not None:
+                tq_, scales = (tq[0], dict(q_scale=tq[1], v_scale=scale)) if index.e4m3 else (tq, {})
+                score, row = ops.rank_topk_filtered(tq_, feat, restrict.image(s), min(k, restrict.shard_rows(s)), splits=splits, **scales)
+            elif index.e4m3:
+                _, _, score, row = ops.rank_topk_e4m3(*tq, feat, scale, None, min(k, feat.shape[0]), splits=splits)
             else:
-                _, _, score, row = ops.rank_topk(tq, feat, None, k_s, splits=splits)
+                _, _, score, row = ops.rank_topk(tq, feat, None, min(k, feat.shape[0]), splits=splits)
             ops.topk_fold(run, (score, row), s, reset=i == 0)
         score, (shard, row) = _read_lists(run)
         v, sec = index.locate(shard, row)
         return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
-    if index.e4m3:
+    if restrict is not None:
+        tq_, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
+        score, row = ops.rank_topk_filtered(tq_, index.feat, restrict.image(), k, splits=splits, **scales)
+    elif index.e4m3:
         _, _, score, row = ops.rank_topk_e4m3(*tq, index.feat, index.scale, None, k, splits=splits)
     else:
         _, _, score, row = ops.rank_topk(tq, index.feat, None, k, splits=splits)
@@ -445,17 +594,22 @@ def search(index, model, embed_text, queries, k=10, splits=0):
 
 
 @torch.no_grad()
-def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, splits=0):
+def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, splits=0, restrict=None):
     """Per query the k best DISTINCT videos of the corpus, [[Moment(vid, start, end, second, score)] * k] * len(queries), by
     descending score (equal scores by index row).  `second` is where the sentence fits the video best and `score` its score, as
     `search` defines it; [start, end] (seconds of the video, inclusive) is the contiguous run around `second` whose scores stay
     >= score - width.  k is clamped to the number of videos and must lie in [1, 32].
     The default width = 0.07 is one unit of the evaluation's logit score / 0.07: the seconds whose softmax-over-time weight is at
-    least e^-1 of the peak's.  That is a definition chosen here, not a measurement of where moments end."""
+    least e^-1 of the peak's.  That is a definition chosen here, not a measurement of where moments end.
+    restrict: a `RowFilter` of this index: a video's peak is its best ADMITTED second (`tan_rank_topk_video_filtered`), a video
+    without one never appears, k is clamped to the admitted videos, and [start, end] is the extent as defined above cut to the
+    admitted span that holds the peak (a clip on the host; the extent walk itself does not know the filter)."""
     queries = list(queries)
     if not queries:
         return []
-    k = min(int(k), len(index.vids))
+    if restrict is not None:
+        restrict.check(index)
+    k = min(int(k), len(index.vids) if restrict is None else restrict.n_videos)
     if not 1 <= k <= 32:
         raise ValueError("search_moments: k must lie in [1, 32]")
     if not width >= 0:
@@ -464,10 +618,13 @@ def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, s
     if isinstance(index, ShardedIndex):
         tq, q_scale = tq if index.e4m3 else (tq, None)
         run = _run_lists(len(queries), k, 3, index.device)
-        for i, (s, feat, scale, v_off) in enumerate(index.shard_views()):
-            k_s = min(k, v_off.numel() - 1)
+        for i, (s, feat, scale, v_off) in enumerate(index.shard_views(None if restrict is None else restrict.ready())):
             scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
-            score, row, video = ops.rank_topk_video(tq, feat, v_off, k_s, splits=splits, **scales)
+            if restrict is not None:
+                score, row, video = ops.rank_topk_video_filtered(tq, feat, v_off, restrict.image(s), min(k, restrict.shard_videos(s)),
+                                                                 splits=splits, **scales)
+            else:
+                score, row, video = ops.rank_topk_video(tq, feat, v_off, min(k, v_off.numel() - 1), splits=splits, **scales)
             # the extents of the shard's OWN list, before the fold: the shard's rows are passed over once (and are gone afterwards
             # when they are streamed), at the price of extents for hits the fold drops
             start, end = ops.moment_extent(tq, feat, v_off, score, row, video, width, **scales)
@@ -477,14 +634,22 @@ def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, s
         for s in np.unique(shard):
             first[shard == s] = index.shards[s].v_off[video[shard == s]]
         gv = index.video_base[shard] + video
+        if restrict is not None:
+            base = index.row_base[shard]
+            start, end = (a - base for a in restrict.clip(base + row, base + start, base + end))
         return [[Moment(index.vids[gv[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
                         int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
     tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
     v_off = index.v_off_device
-    score, row, video = ops.rank_topk_video(tq, index.feat, v_off, k, splits=splits, **scales)
+    if restrict is not None:
+        score, row, video = ops.rank_topk_video_filtered(tq, index.feat, v_off, restrict.image(), k, splits=splits, **scales)
+    else:
+        score, row, video = ops.rank_topk_video(tq, index.feat, v_off, k, splits=splits, **scales)
     start, end = ops.moment_extent(tq, index.feat, v_off, score, row, video, width, **scales)
     score = score.cpu().numpy()                                    # the one read-back: the int32 results travel together
     row, video, start, end = torch.stack((row, video, start, end)).cpu().numpy()
+    if restrict is not None:
+        start, end = restrict.clip(row, start, end)
     first = index.v_off[video]
     return [[Moment(index.vids[video[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
                     int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
@@ -497,7 +662,9 @@ def search_sequences(index, model, embed_text, sequences, k=10, splits=0):
     one second of the video per step, non-decreasing (equal seconds allowed): the assignment with the largest summed score, ties to
     the smallest last second, then the smallest second to last, as `align_corpus(decode="monotonic")` breaks them.  `score` is that
     sum of the steps' stitched dual cosines (`search`'s score); / 0.07 gives the summed logit.  k is clamped to the number of
-    videos and must lie in [1, 32].  Two read-backs: the winning videos (to size the score blocks), then seconds and scores."""
+    videos and must lie in [1, 32].  Two read-backs: the winning videos (to size the score blocks), then seconds and scores.
+    There is no `restrict=` here: a `RowFilter` is not taken by this call (a path needs its whole video, and whole-video filters
+    for the sequence sweep are not built)."""
     sequences = [list(seq) for seq in sequences]
     if not sequences:
         return []
@@ -598,7 +765,8 @@ def _rerank_table(v_off, d_row, d_video, T):
 
 
 @torch.no_grad()
-def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, windows_per_pass=256, splits=0, return_sim=False):
+def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, windows_per_pass=256, splits=0, return_sim=False,
+                  restrict=None):
     """Two-stage search.  Per query the `pool` best distinct videos of the dual sweep (`search_moments`' candidates: the same
     `tan_rank_topk_video` call), each rescored by the joint encoder on ONE window of `seq_len` seconds around its best dual second
     (`rerank_window`), and the k best of them: [[Reranked(vid, second, score, confidence, alignability, dual_second, dual_score)]
@@ -614,9 +782,16 @@ def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, 
     The index needs a stem (`build_index(keep_stem=True)`).  pool is clamped to the number of videos and must lie in [1, 32]; k is
     clamped to the number of videos too, 1 <= k <= pool.  The Q * pool windows run in passes of `windows_per_pass`; one read-back.
     return_sim: also return every window's cosines, (hits, sim [Q, pool, seq_len] f32, candidates in dual rank order, -inf beyond
-    a window's seconds), a second read-back."""
+    a window's seconds), a second read-back.
+    restrict: a `RowFilter` of this index made of whole videos (`videos` / `exclude`): it applies to the CANDIDATE stage
+    (`tan_rank_topk_video_filtered`); pool and k are clamped to the admitted videos.  One built with `windows` raises ValueError:
+    the joint window is cut around the dual second whatever the filter says."""
     if isinstance(index, ShardedIndex):
         raise ValueError("search_rerank: not built for a ShardedIndex; merge the shards")
+    if restrict is not None:
+        restrict.check(index)
+        if restrict.windowed:
+            raise ValueError("search_rerank: a filter built with windows does not go with the joint window; restrict by videos / exclude")
     net = _aligner(model)
     if index.stem is None:
         raise ValueError("search_rerank: the index has no stem store (build_index(..., keep_stem=True) / index --keep-stem)")
@@ -626,7 +801,7 @@ def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, 
     queries = list(queries)
     if not queries:
         return ([], np.zeros((0, 0, seq_len), np.float32)) if return_sim else []
-    n_videos = len(index.vids)
+    n_videos = len(index.vids) if restrict is None else restrict.n_videos
     pool, k = min(int(pool), n_videos), min(int(k), n_videos)
     if not 1 <= pool <= 32:
         raise ValueError("search_rerank: pool must lie in [1, 32]")
@@ -642,7 +817,10 @@ def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, 
     tq = query_features(index, model, embed_text, queries)
     tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
     v_off = index.v_off_device
-    d_score, d_row, d_video = ops.rank_topk_video(tq, index.feat, v_off, pool, splits=splits, **scales)
+    if restrict is not None:
+        d_score, d_row, d_video = ops.rank_topk_video_filtered(tq, index.feat, v_off, restrict.image(), pool, splits=splits, **scales)
+    else:
+        d_score, d_row, d_video = ops.rank_topk_video(tq, index.feat, v_off, pool, splits=splits, **scales)
     table = _rerank_table(v_off, d_row, d_video, T)
     # stage 2: the joint stack over the stem windows, reduced per pass
     emb = embed_text(queries).to(dev).float().reshape(Q, -1).contiguous()
@@ -723,6 +901,12 @@ def _parser():
                    help="a further index file searched together with --index, in the order given (repeatable)")
     p.add_argument("--host-resident", action="store_true",
                    help="keep the rows in pinned host memory and stream them through the card: for an index larger than the card")
+    p.add_argument("--only", action="append", default=None, metavar="VID", help="search only this video (repeatable)")
+    p.add_argument("--only-file", default=None, metavar="PATH", help="search only the videos listed here, one vid per line")
+    p.add_argument("--exclude", action="append", default=None, metavar="VID", help="leave this video out (repeatable)")
+    p.add_argument("--exclude-file", default=None, metavar="PATH", help="leave out the videos listed here, one vid per line")
+    p.add_argument("--within", action="append", default=None, metavar="VID:FIRST-LAST",
+                   help="search this video only between these seconds, inclusive (repeatable; other videos stay whole)")
     p.add_argument("sentences", nargs="+")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
@@ -751,7 +935,40 @@ def parse_args(argv=None):
         ap.error("--width must be >= 0")
     if a.cmd == "index" and not 0 <= a.worker_id < a.num_workers:
         ap.error("--worker-id must lie in [0, --num-workers)")
+    if a.cmd == "query":
+        filtered = any(x is not None for x in (a.only, a.only_file, a.exclude, a.exclude_file, a.within))
+        if filtered and a.sequence:
+            ap.error("--only / --exclude / --within do not go with --sequence")
+        if a.within is not None and a.rerank:
+            ap.error("--within does not go with --rerank (the joint window is cut around the dual second)")
+        try:
+            a.within = None if a.within is None else [parse_within(w) for w in a.within]
+        except ValueError as e:
+            ap.error(str(e))
     return a
+
+
+def parse_within(text):
+    """'VID:FIRST-LAST' -> (vid, first, last); the vid may hold colons itself"""
+    vid, sep, span = text.rpartition(":")
+    first, dash, last = span.partition("-")
+    if not sep or not vid or not dash or not first.isdigit() or not last.isdigit():
+        raise ValueError(f"--within takes VID:FIRST-LAST (seconds, inclusive), not {text!r}")
+    return vid, int(first), int(last)
+
+
+def _read_vids(path):
+    with open(path) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def restrict_from_args(index, a):
+    """The `RowFilter` of `query`'s --only / --only-file / --exclude / --exclude-file / --within, or None without any of them"""
+    only = (a.only or []) + (_read_vids(a.only_file) if a.only_file else [])
+    exclude = (a.exclude or []) + (_read_vids(a.exclude_file) if a.exclude_file else [])
+    if not (only or exclude or a.within or a.only is not None or a.only_file):
+        return None
+    return index.restrict(videos=only if (a.only is not None or a.only_file) else None, exclude=exclude or None, windows=a.within)
 
 
 def main(argv=None):
@@ -781,20 +998,21 @@ def main(argv=None):
         for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
             print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))
         return 0
+    only = restrict_from_args(idx, a)
     if a.rerank:
         pool = 32 if a.pool is None else a.pool
-        for sentence, hits in zip(a.sentences, search_rerank(idx, model, embed, a.sentences, min(a.k, pool), pool)):
+        for sentence, hits in zip(a.sentences, search_rerank(idx, model, embed, a.sentences, min(a.k, pool), pool, restrict=only)):
             for h in hits:
                 al = "" if h.alignability is None else f"{h.alignability:.6f}"
                 print(f"{sentence}\t{h.vid}\t{h.second}\t{h.score:.6f}\t{h.confidence:.6f}\t{al}\t{h.dual_second}\t{h.dual_score:.6f}")
         return 0
     if a.moments:
         width = TEMPERATURE if a.width is None else a.width
-        for sentence, hits in zip(a.sentences, search_moments(idx, model, embed, a.sentences, a.k, width)):
+        for sentence, hits in zip(a.sentences, search_moments(idx, model, embed, a.sentences, a.k, width, restrict=only)):
             for m in hits:
                 print(f"{sentence}\t{m.vid}\t{m.start}\t{m.end}\t{m.second}\t{m.score:.6f}")
         return 0
-    for sentence, hits in zip(a.sentences, search(idx, model, embed, a.sentences, a.k)):
+    for sentence, hits in zip(a.sentences, search(idx, model, embed, a.sentences, a.k, restrict=only)):
         for vid, sec, score in hits:
             print(f"{sentence}\t{vid}\t{sec}\t{score:.6f}")
     return 0

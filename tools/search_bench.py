@@ -5,6 +5,7 @@ process, device events around each call, caller-owned outputs and scratch.  Prin
     python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --rerank [--rows 4194304] [--queries 1 64] [--pool 32] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --shards [8] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py --restrict [--parent-lib PARENT.so] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--out FILE]
 
 Rows: seeded random unit rows, made in slices.  4 Mi rows are 4 GiB of bf16 and 2 GiB + 16 MiB of e4m3 codes and scales: both far
 beyond the 256 MB last-level cache, so every sweep streams its index from HBM.  Bytes per second count the index once per sweep
@@ -34,7 +35,14 @@ similarities -- the joint half of it is what stem + tail replace).
 shards) and their ratio, `fold_us_per_launch` (the S folds alone), `host_shards_ms` (the same loop with the shards streamed from pinned
 host memory through `ShardedIndex.shard_views`' two slots) as `host_GBps` of index bytes, and `copy_ms` / `copy_GBps`: a plain pinned
 `copy_` of the same bytes into one slot in the same run -- the host link's rate, which `host_shards` cannot beat.  `equals_single`:
-the folded lists have the single sweep's scores (bit patterns) and rows."""
+the folded lists have the single sweep's scores (bit patterns) and rows.
+
+--restrict times the filtered sweep INSTEAD (`ops.rank_topk_filtered` under `ops.row_filter_build`'s image), bf16 and e4m3, per Q, for
+filters that admit 1, 1/2, 1/16 and 1/256 of 64-row videos drawn uniformly with a fixed seed: `build_ms` (the image, apart from the
+sweep), `filtered_ms`, `plain_ms` (`ops.rank_topk` over the whole index) beside `parent_plain_ms` (the same entry point of
+`--parent-lib`, the parent commit's build, the two alternating call by call in this run), and `gather_ms` (what a caller does without
+the feature: `index_select` of the admitted rows, then the plain sweep over them, the gather included).  `equals_gather`: the filtered
+lists have the gathered sweep's scores (bit patterns) and rows."""
 import argparse
 import json
 import os
@@ -215,6 +223,103 @@ def shards_table(N, k, v16, v8, s8, a):
     return rows
 
 
+RESTRICT_FRACTIONS = ((1, 1), (1, 2), (1, 16), (1, 256))
+RESTRICT_VLEN = 64
+
+
+def timed_pair(fa, fb, warmup, reps):
+    """Median ms of fa and of fb, the two alternating call by call (A B A B ...): what one of them gains from the other's leftovers in
+    the caches, or loses to a neighbour on the machine, the other gets too."""
+    for _ in range(warmup):
+        fa()
+        fb()
+    ms = ([], [])
+    for _ in range(reps):
+        for fn, acc in ((fa, ms[0]), (fb, ms[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            acc.append(a.elapsed_time(b))
+    return float(np.median(ms[0])), float(np.median(ms[1]))
+
+
+def parent_sweep(path):
+    """The plain sweep entry points of ANOTHER build of the library (the parent commit's), called as `ops.rank_topk` calls them"""
+    import ctypes as C
+
+    from temporalalignnet_amd import _lib
+    L, protos = C.CDLL(path), _lib.declared_prototypes()
+    for name in ("tan_rank_topk", "tan_rank_topk_e4m3"):
+        getattr(L, name).restype, getattr(L, name).argtypes = protos[name]
+
+    def run(tq, vn, kw, k, out, ws):
+        Q, N, st = tq.shape[0], vn.shape[0], torch.cuda.current_stream().cuda_stream
+        if kw:
+            rc = L.tan_rank_topk_e4m3(tq.data_ptr(), kw["q_scale"].data_ptr(), vn.data_ptr(), kw["v_scale"].data_ptr(), Q, N, 512, None, k, 0,
+                                      None, None, out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), st)
+        else:
+            rc = L.tan_rank_topk(tq.data_ptr(), vn.data_ptr(), ops.TAN_BF16, Q, N, 512, None, k, 0, None, None, out[0].data_ptr(),
+                                 out[1].data_ptr(), ws.data_ptr(), st)
+        assert rc == 0, rc
+    return run
+
+
+def restrict_table(N, k, v16, v8, s8, a):
+    """One row per (format, Q, admitted fraction): whole videos of 64 rows drawn uniformly with a fixed seed.  build_ms =
+    `ops.row_filter_build` (spans already on the device); filtered_ms = `ops.rank_topk_filtered`; plain_ms = `ops.rank_topk` over the
+    whole index, and parent_plain_ms the same entry point of --parent-lib, the two alternating call by call; gather_ms = what a
+    caller does without the feature: `index_select` of the admitted rows (and scales), then `ops.rank_topk` over them."""
+    nv = N // RESTRICT_VLEN
+    parent = parent_sweep(a.parent_lib) if a.parent_lib else None
+    rows = []
+    for fmt, vn, vs in (("bf16", v16, None), ("e4m3", v8, s8)):
+        for Q in a.queries:
+            q = unit_rows(Q, 1 << 30)
+            tq, qs = (q.to(torch.bfloat16), None) if vs is None else ops.quantize_rows_e4m3(q)
+            kw = {} if vs is None else dict(q_scale=qs, v_scale=vs)
+            ws = torch.empty(ops.rank_topk_ws_bytes(Q, N, k), dtype=torch.uint8, device="cuda")
+            out = (torch.empty(Q, k, device="cuda"), torch.empty(Q, k, dtype=torch.int32, device="cuda"))
+            pout = (torch.empty(Q, k, device="cuda"), torch.empty(Q, k, dtype=torch.int32, device="cuda"))
+
+            def plain(feat=vn, scales=kw, o=out):
+                if scales:
+                    ops.rank_topk_e4m3(tq, qs, feat, scales["v_scale"], None, k, out=(None, None, *o), ws=ws)
+                else:
+                    ops.rank_topk(tq, feat, None, k, out=(None, None, *o), ws=ws)
+            if parent:
+                t_plain, t_parent = timed_pair(plain, lambda: parent(tq, vn, kw, k, pout, ws), a.warmup, a.reps)
+                same_parent = bool(torch.equal(out[0].view(torch.int32), pout[0].view(torch.int32)) and torch.equal(out[1], pout[1]))
+            else:
+                (t_plain, _), t_parent, same_parent = timed(plain, a.warmup, a.reps), None, None
+            for num, den in RESTRICT_FRACTIONS:
+                picked = np.sort(np.random.default_rng(den).permutation(nv)[:nv * num // den]).astype(np.int64)
+                edge = np.flatnonzero(np.diff(picked) != 1)                                    # adjacent videos merge into one span
+                first, last = picked[np.concatenate([[0], edge + 1])], picked[np.concatenate([edge, [len(picked) - 1]])]
+                spans = torch.from_numpy(np.stack((first, last + 1), 1).astype(np.int32) * RESTRICT_VLEN).cuda()
+                rows_t = (torch.from_numpy(picked).cuda()[:, None] * RESTRICT_VLEN + torch.arange(RESTRICT_VLEN, device="cuda")[None]).reshape(-1)
+                filt = torch.empty(ops.row_filter_bytes(N), dtype=torch.uint8, device="cuda")
+                t_build, _ = timed(lambda: ops.row_filter_build(spans, N, out=filt), a.warmup, a.reps)
+                t_filt, _ = timed(lambda: ops.rank_topk_filtered(tq, vn, filt, k, out=out, ws=ws, **kw), a.warmup, a.reps)
+                got_s, got_r = out[0].clone(), out[1].clone()
+
+                def gather():
+                    g = torch.index_select(vn, 0, rows_t)
+                    plain(g, dict(v_scale=torch.index_select(vs, 0, rows_t)) if kw else {}, pout)
+                t_gather, _ = timed(gather, a.warmup, a.reps)
+                same = bool(torch.equal(got_s.view(torch.int32), pout[0].view(torch.int32)) and torch.equal(got_r.long(), rows_t[pout[1].long()]))
+                rows.append({"fmt": fmt, "Q": Q, "fraction": f"{num}/{den}", "spans": int(spans.shape[0]), "admitted_rows": int(rows_t.numel()),
+                             "build_ms": round(t_build, 4), "filtered_ms": round(t_filt, 4), "plain_ms": round(t_plain, 4),
+                             "parent_plain_ms": None if t_parent is None else round(t_parent, 4),
+                             "plain_over_parent": None if t_parent is None else round(t_plain / t_parent, 3),
+                             "filtered_over_plain": round(t_filt / t_plain, 4), "filtered_over_fraction": round(t_filt / (t_plain * num / den), 3),
+                             "gather_ms": round(t_gather, 4), "gather_over_filtered": round(t_gather / t_filt, 2),
+                             "equals_gather": same, "plain_equals_parent": same_parent})
+                del rows_t, filt
+    return rows
+
+
 def rerank_table(N, v16, stem, a):
     import time
 
@@ -313,6 +418,9 @@ def main():
     ap.add_argument("--pool", type=int, default=32)
     ap.add_argument("--shards", type=int, nargs="?", const=8, default=0, metavar="S",
                     help="time sharded search over S shards (default 8) instead (see the module docstring)")
+    ap.add_argument("--restrict", action="store_true", help="time the filtered sweep instead (see the module docstring)")
+    ap.add_argument("--parent-lib", default=None, metavar="PATH",
+                    help="with --restrict: libtan_hip.so of the parent commit's build, whose plain sweep is timed in the same run")
     a = ap.parse_args()
     N, k = a.rows, a.k
     if a.rerank:
@@ -346,6 +454,22 @@ def main():
         v16[r:r + SLICE] = x.to(torch.bfloat16)
         ops.quantize_rows_e4m3(x, v8[r:r + SLICE], s8[r:r + SLICE])
     del x
+    if a.restrict:
+        rows = restrict_table(N, k, v16, v8, s8, a)
+        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "restrict": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --restrict --rows {N} -k {k}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
+                fh.write(f"# {N // RESTRICT_VLEN} videos of {RESTRICT_VLEN} rows, whole videos drawn uniformly (fixed seed); build = row_filter_build; "
+                         "filtered = rank_topk_filtered; plain = rank_topk over the whole index, parent_plain = the parent commit's build of it, "
+                         "alternating call by call; gather = index_select of the admitted rows + rank_topk over them\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>22}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>22}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
     if a.shards:
         rows = shards_table(N, k, v16, v8, s8, a)
         res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "shards": rows}

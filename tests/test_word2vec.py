@@ -57,6 +57,13 @@ def _hip_model(dtype):
     return m.cuda()
 
 
+# The gradient fingerprints against the golden ones, relative to the gradient's norm: (norm, each of the 16 sampled elements).  Measured
+# on MI355X: fp32 1.0e-8 / 2.5e-8 (fc1.bias; the golden values are f32 themselves), bf16 4.1e-4 (fc1.weight) / 1.4e-4 (fc2.bias).  The
+# earlier bounds were 1e-3 / 1e-4 in fp32 and 2.0 / 0.2 in bf16 -- twice the norm: a gradient of zeros passed.  Every element against
+# float64 autograd: tests/test_w2v_fp64_gpu.py.
+GRAD_FP_TOL = {"fp32": (1e-7, 1e-7), "bf16": (1e-3, 3e-4)}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype,tol", [("fp32", 2e-5), ("bf16", 4e-2)])
 def test_hip_word2vec_forward_backward(golden, dtype, tol):
@@ -74,8 +81,10 @@ def test_hip_word2vec_forward_backward(golden, dtype, tol):
     for k in ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"):
         got, want = _fp(named[k].grad), g["grad/" + k]
         scale = abs(want[1])
-        assert abs(got[1] - want[1]) < 50 * tol * scale, (k, got[1], want[1])
-        assert np.abs(got[2:] - want[2:]).max() < 50 * tol * scale / 10 + 1e-6, k
+        e_norm, e_el = abs(got[1] - want[1]) / scale, np.abs(got[2:] - want[2:]).max() / scale
+        print(f"\n[word2vec golden] {dtype} {k}: norm {e_norm:.3e}, elements {e_el:.3e}")
+        assert e_norm <= GRAD_FP_TOL[dtype][0], (k, got[1], want[1])
+        assert e_el <= GRAD_FP_TOL[dtype][1], (k, e_el)
 
 
 @pytest.mark.gpu

@@ -732,6 +732,33 @@ int tan_window_stitch_final(float* acc_j, const float* acc_d, const float* cnt, 
 int tan_monotonic_decode(const float* sim, const int* rows, const int* order, const int* vtab, int n_videos,
                          const unsigned char* keep, long n_rows, long n_acc, long n_run, int* bp, float* run, int* ts,
                          float* path, void* stream);
+/* Aligned intervals: a segmental decode over the same stitched rows.  tan_monotonic_decode gives every kept sentence one second; this
+ * gives it an inclusive interval [s, e], the intervals of one video decided together: ordered by decode order and disjoint.  Per video,
+ * with its kept rows r_0 .. r_{m-1} in decode order, V = vlen, x_i[t] = sim[r_i][t] (as stitched, -6e4 cells included) and the gain
+ * g_i[t] = x_i[t] - bias[r_i] (one f32 subtraction): segments [s_i, e_i] with s_i <= e_i and e_i < s_{i+1} (gaps allowed) that maximise
+ * sum_i sum_{t in [s_i, e_i]} g_i[t].  As a recurrence (-inf is IEEE; every + is one f32 add, round to nearest, never contracted):
+ *     G_{-1}[t] = 0 for t >= -1;   for i >= 0: G_i[-1] = -inf, E_i[-1] = -inf
+ *     c = G_{i-1}[t-1];  p = E_i[t-1]
+ *     E_i[t] = g_i[t] + max(p, c)              S_i[t] = t if c > p, else S_i[t-1]        (a tie extends the running segment)
+ *     G_i[t] = max(G_i[t-1], E_i[t])           B_i[t] = the SMALLEST t' <= t with E_i[t'] == G_i[t]
+ *     path = G_{m-1}[V-1];   e_{m-1} = B_{m-1}[V-1],  s_i = S_i[e_i],  e_{i-1} = B_{i-1}[s_i - 1]
+ * E_i[t] (the best sum with sentence i's segment ending exactly at t) is finite exactly for t >= i; the problem is feasible iff
+ * m <= V.  With exact sums the result is the optimum, and among optima the one with the smallest e_{m-1}, then the smallest s_{m-1},
+ * then the smallest e_{m-2}, and so on; for m = 1 it is the maximum-sum run of g_0 (Kadane).  Every cell is one rounded add on top of
+ * exact maxima and the dependency graph is fixed by the recurrence, so the bits of `path` and the segments do not depend on how the cells
+ * are scheduled -- which is why it runs along t and is NOT restated as a prefix sum or a (max, +) scan: those re-associate the adds.
+ *   sim, rows, order, vtab, keep, n_rows, n_acc, n_run: as for tan_monotonic_decode, with the same contract for a broken table entry
+ *   (it takes no part; nothing is read or written out of bounds).  bias [n_rows] f32, by packed row id.
+ *   bp [2 * n_acc] int32 (two planes laid out like sim: S_i[B_i[t]] and B_i[t]) and run [n_run] f32 (n_run >= sum of vlen: the G row
+ *   one block of 256 sentences hands to the next) are scratch and need no initialisation.
+ *   seg [n_rows, 2] int32 <- (s, e), inclusive, for every kept row; (-1, -1) for every other row a video lists (a row no video lists
+ *   is not written).  path [n_videos] f32 <- the path score; 0 for a video without a kept row; -inf for a video with more kept rows
+ *   than seconds, all of whose listed rows get (-1, -1).
+ * Any vlen >= 1, any m.  One launch, one workgroup per video, no atomics, no host synchronisation.
+ * NULL pointers (other than keep) or non-positive counts: TAN_ERR_BAD_ARG, nothing launched.                                       */
+int tan_segment_decode(const float* sim, const int* rows, const int* order, const int* vtab, int n_videos,
+                       const unsigned char* keep, const float* bias, long n_rows, long n_acc, long n_run, int* bp, float* run,
+                       int* seg, float* path, void* stream);
 
 /* ---- zero-shot retrieval (eval/eval_zeroshot_retrieval.py:13-27,157-256) and corpus search over a per-second index ----
  * tan_rank_topk: a matrix-free sweep over scores[q, n] = <Tq[q, :], Vn[n, :]>, Tq [Q, C], Vn [N, C], C == 512, both `dtype`

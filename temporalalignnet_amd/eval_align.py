@@ -142,17 +142,67 @@ def monotonic_seconds(sim, start, keep=None):
     return ts.cpu().long(), float(path)
 
 
+def check_width(width):
+    """The segmental decode's `width`, as a float; negative or NaN raises ValueError."""
+    width = float(width)
+    if not width >= 0:
+        raise ValueError(f"width: a non-negative number of logits, not {width!r}")
+    return width
+
+
+@torch.no_grad()
+def segment_seconds(sim, start, keep=None, width=1.0):
+    """One video's aligned intervals (tan_segment_decode): sim [K, vlen] f32 on the device, `start` [K] the ASR starts that order the
+    sentences (equal starts by sentence index), keep [K] bool or None = all.  Returns ([K, 2] int64 on the host: inclusive (start, end)
+    seconds, ordered and disjoint, (-1, -1) where not kept or when more sentences are kept than the video has seconds; the path's
+    score).  A second adds sim - (row maximum - width) to its sentence's segment: `width` (logits) is how far below its row's peak a
+    second may lie and still pay.  The default 1.0 is `search_moments`' default (its TEMPERATURE, 0.07 in cosine) on the stitched
+    rows' 1/0.07 scale: a convention, tuned on nothing."""
+    from . import ops
+    width = check_width(width)
+    K, vlen = sim.shape
+    if K == 0:
+        return torch.zeros(0, 2, dtype=torch.int64), 0.0
+    dev = sim.device
+    sim = sim.float().contiguous()
+    tab = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)                 # noqa: E731
+    rows = tab(np.stack([np.arange(K) * vlen, np.full(K, vlen)], 1))
+    order = tab(np.argsort(np.asarray(start, dtype=np.float64), kind="stable"))
+    keep_d = None if keep is None else torch.from_numpy(np.asarray(keep).astype(bool)).to(dev)
+    bias = sim.max(-1).values - torch.full((), width, dtype=torch.float32, device=dev)                 # one f32 subtraction
+    seg = torch.empty(K, 2, dtype=torch.int32, device=dev)
+    path = torch.empty(1, device=dev)
+    ops.segment_decode(sim.view(-1), rows, order, tab([[0, K, 0]]), keep_d, bias, torch.empty(2 * K * vlen, dtype=torch.int32, device=dev),
+                       torch.empty(vlen, device=dev), seg, path)
+    return seg.cpu().long(), float(path)
+
+
+def temporal_iou(seg_start, seg_end, start, end):
+    """IoU of the decoded seconds [seg_start, seg_end + 1) with the annotated [floor(start), ceil(end)]; 0 without a segment."""
+    if seg_start < 0:
+        return 0.0
+    lo, hi = math.floor(start), math.ceil(end)
+    inter = max(0, min(seg_end + 1, hi) - max(seg_start, lo))
+    return inter / ((seg_end + 1 - seg_start) + (hi - lo) - inter)
+
+
 @torch.no_grad()
 def test_alignment_htm(get_text_visual_sim, videos, device="cuda", seq_len=64, use_alignability_head=True,
-                       method="overlap-seq", return_per_video=False, batched_sim=None, decode=None):
+                       method="overlap-seq", return_per_video=False, batched_sim=None, decode=None, width=1.0):
     """`videos`: iterable of {'video' [vlen, Dv], 'start' [K], 'end' [K], 'aligned' [K] 0/1, 'str' list[str]}
     (htm_align.json schema, htm_align/readme.md:11-20).  Returns {'Recall', 'AUC'}.  `batched_sim` (make_batched_sim_fn): the
     windows of a video are evaluated together instead of one model call per window (same results, see the GPU tests).
     `decode="monotonic"` (either method): the aligned sentences' seconds come from `monotonic_seconds` -- non-decreasing in ASR start
-    order -- instead of each row's own arg-max (:222,237), so Recall shows what the ordering does to R@1; AUC is not affected."""
-    if decode not in (None, "monotonic"):
-        raise ValueError(f"decode: None or 'monotonic', not {decode!r}")
-    recall, scores, tgts, per_video = [], [], [], []
+    order -- instead of each row's own arg-max (:222,237), so Recall shows what the ordering does to R@1; AUC is not affected.
+    `decode="segments"` (either method): the aligned sentences get ordered, disjoint intervals from `segment_seconds(.., width)`; a
+    sentence's second is the best one inside its interval (the first arg-max of sim[k, s:e+1]; -1 without an interval), the metric
+    gains 'IoU' -- the mean `temporal_iou` of [s, e + 1) with [floor(start), ceil(end)] over the aligned sentences -- and the
+    per-video dicts gain 'segments' ([n_aligned, 2] int64)."""
+    if decode not in (None, "monotonic", "segments"):
+        raise ValueError(f"decode: None, 'monotonic' or 'segments', not {decode!r}")
+    if decode == "segments":
+        width = check_width(width)
+    recall, ious, scores, tgts, per_video = [], [], [], [], []
     for item in videos:
         video = torch.as_tensor(item["video"]).float().to(device)[None]
         text = list(item["str"])
@@ -206,10 +256,20 @@ def test_alignment_htm(get_text_visual_sim, videos, device="cuda", seq_len=64, u
         tgts.append(aligned.astype(np.int64))
         if decode is None:
             am = prob[torch.from_numpy(aligned).to(device)].argmax(-1).cpu()
-        else:
+        elif decode == "monotonic":
             am = monotonic_seconds(sim, start, aligned)[0][torch.from_numpy(aligned)]
+        else:
+            segs = segment_seconds(sim, start, aligned, width)[0][torch.from_numpy(aligned)]
+            rows = sim[torch.from_numpy(aligned).to(device)].cpu()
+            am = torch.tensor([int(a) + int(r[a:b + 1].argmax()) if a >= 0 else -1 for r, (a, b) in zip(rows, segs.tolist())],
+                              dtype=torch.int64)
+            ious += [temporal_iou(a, b, s, e) for (a, b), s, e in zip(segs.tolist(), start[aligned], end[aligned])]
         for k, (s, e) in enumerate(zip(start[aligned], end[aligned])):
             recall.append(math.floor(s) <= int(am[k]) <= math.ceil(e))
         per_video.append({"sim": sim.cpu(), "argmax": am, "score": score.cpu()})
+        if decode == "segments":
+            per_video[-1]["segments"] = segs
     metric = {"Recall": float(np.mean(recall)), "AUC": roc_auc_score(np.concatenate(tgts), np.concatenate(scores))}
+    if decode == "segments":
+        metric["IoU"] = float(np.mean(ious))
     return (metric, per_video) if return_per_video else metric

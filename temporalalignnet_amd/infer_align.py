@@ -13,6 +13,8 @@ every sentence as a window candidate (a corpus has no ground truth):
     pinned memory and copied on a side stream while the current chunk computes.
   * on request (`decode="monotonic"`, `--decode monotonic`): one `tan_monotonic_decode` launch per chunk between the two, a
     dynamic program over the stitched rows that gives every video's sentences non-decreasing seconds in ASR start order.
+  * on request (`decode="segments"`, `--decode segments [--width W]`): one `tan_segment_decode` launch per chunk instead, which
+    gives every video's sentences ordered, disjoint intervals of seconds.
 
     python -m temporalalignnet_amd.infer_align --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out X.csv
 """
@@ -31,7 +33,7 @@ import torch
 
 from . import ops
 from .data_htm import read_vlen_csv
-from .eval_align import plan_windows
+from .eval_align import check_width, plan_windows
 
 # include/tan_hip.h, tan_attn_*: the joint stack's sequence (seq_len frames + the window's sentences) is at most 448 (f32) / 320 (bf16)
 JOINT_MAX_LEN = {torch.float32: 448, torch.bfloat16: 320}
@@ -187,7 +189,7 @@ def _prefetch(chunks, device):
 
 @torch.no_grad()
 def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, candidates=None, return_sim=False, on_reject=None,
-                 decode=None, keep_threshold=None):
+                 decode=None, keep_threshold=None, width=1.0):
     """Yield per video {'vid', 'str', 'timestamp' [K] int64, 'confidence' [K], 'score' [K], 'covered' [K] bool, ('sim' [K, vlen])}.
 
     `videos`: iterable of {'vid', 'start' [K], 'end' [K], 'str' [K], 'video'} -- 'video' is [vlen, Dv] (array / tensor, f32 / f16 /
@@ -204,10 +206,24 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
     ties go to the earliest seconds, last sentence first (include/tan_hip.h has the recurrence).  A constant added to a row does
     not move the path, so it is also the Viterbi path under each row's log-softmax over time, the quantity 'timestamp' arg-maxes.
     Results gain 'ordered_timestamp' [K] int64 (-1 where not kept), 'ordered' [K] bool (kept) and 'path_score' (float, the sum
-    along the path; 0.0 without a kept sentence); the other keys are what they are without `decode`."""
-    if decode not in (None, "monotonic"):
-        raise ValueError(f"decode: None or 'monotonic', not {decode!r}")
-    ordered = decode is not None
+    along the path; 0.0 without a kept sentence); the other keys are what they are without `decode`.
+
+    `decode="segments"`: aligned intervals on top of the above (one `tan_segment_decode` launch per chunk).  Per video, the same kept
+    sentences in the same order as for "monotonic" get inclusive intervals [segment_start, segment_end] of seconds that are ordered
+    and disjoint (gaps allowed) and maximise the summed gain sim[i][t] - bias[i] over their seconds, bias[i] = sim[i][timestamp_i] -
+    width: a second pays while it lies within `width` logits of its row's peak (include/tan_hip.h has the recurrence and the tie
+    rule).  `width` >= 0 (else ValueError); the default 1.0 is `search_moments`' default (its TEMPERATURE, 0.07 in cosine) on the
+    stitched rows' 1/0.07 scale -- a convention, tuned on nothing (no real data was available when it was chosen).  Results gain
+    'segment_start' / 'segment_end' [K] int64 (-1 where not kept, or when the video has more kept sentences than seconds),
+    'segmented' [K] bool (kept) and 'path_score' (float; 0.0 without a kept sentence, -inf for such an infeasible video); the
+    other keys are what they are without `decode`."""
+    if decode not in (None, "monotonic", "segments"):
+        raise ValueError(f"decode: None, 'monotonic' or 'segments', not {decode!r}")
+    if decode == "segments":
+        width = check_width(width)
+    ordered = decode is not None                      # either decode reads the chunk's order / vtab tables
+    empty = {None: None, "monotonic": (np.zeros(0, np.int32), 0.0),
+             "segments": (np.zeros((0, 2), np.int32), 0.0, np.zeros(0, bool))}[decode]
     net = _aligner(model)
     head = bool(net.use_alignability_head)
     if head and net.num_decoder_layers < 3:
@@ -220,7 +236,7 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
         if ch.n_rows == 0:
             for it in ch.items:
                 yield _result(it, np.zeros((4, 0), np.float32), None if not return_sim else np.zeros((0, it["vlen"]), np.float32),
-                              (np.zeros(0, np.int32), 0.0) if ordered else None)
+                              decode, empty)
             continue
         emb = embed_text([s for it in ch.items for s in it["str"]]).contiguous()
         acc_j, acc_d, cnt = (torch.zeros(ch.n_acc, device=device) for _ in range(3))
@@ -243,10 +259,18 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
             keep = res[3] > 0                         # covered; the threshold compares as write_rows does, in f64
             if keep_threshold is not None:
                 keep = keep & (res[2].double() > float(keep_threshold))
-            ts = torch.empty(ch.n_rows, dtype=torch.int32, device=device)
             path = torch.empty(len(ch.items), device=device)
+            run = torch.empty(int(ch.v_off[-1]), device=device)
+        if decode == "monotonic":
+            ts = torch.empty(ch.n_rows, dtype=torch.int32, device=device)
             ops.monotonic_decode(acc_j, ch.rows_d, ch.order_d, ch.vtab_d, keep, torch.empty(ch.n_acc, dtype=torch.int32, device=device),
-                                 torch.empty(int(ch.v_off[-1]), device=device), ts, path)
+                                 run, ts, path)
+        elif decode == "segments":
+            # bias = the row's maximum (the stitched row at its first arg-max, res[0]) - width: a gather and one f32 subtraction
+            bias = acc_j[ch.rows_d[:, 0].long() + res[0].long()] - torch.full((), width, dtype=torch.float32, device=device)
+            ts = torch.empty(ch.n_rows, 2, dtype=torch.int32, device=device)
+            ops.segment_decode(acc_j, ch.rows_d, ch.order_d, ch.vtab_d, keep, bias,
+                               torch.empty(2 * ch.n_acc, dtype=torch.int32, device=device), run, ts, path)
         res_h = torch.empty(res.shape, pin_memory=True)
         res_h.copy_(res, non_blocking=True)
         if return_sim:
@@ -256,22 +280,34 @@ def align_corpus(model, videos, embed_text, seq_len=64, windows_per_pass=256, ca
             ts_h, path_h = torch.empty(ts.shape, dtype=ts.dtype, pin_memory=True), torch.empty(path.shape, pin_memory=True)
             ts_h.copy_(ts, non_blocking=True)
             path_h.copy_(path, non_blocking=True)
+        if decode == "segments":                      # the mask the kernel read: an infeasible video's kept rows carry no segment
+            keep_h = torch.empty(keep.shape, dtype=torch.bool, pin_memory=True)
+            keep_h.copy_(keep, non_blocking=True)
         torch.cuda.current_stream(device).synchronize()
         res_h = res_h.numpy()
         for i, it in enumerate(ch.items):
             k0, k1 = ch.k_off[i], ch.k_off[i + 1]
             sim = sim_h.numpy()[ch.a_off[i]:ch.a_off[i + 1]].reshape(k1 - k0, it["vlen"]).copy() if return_sim else None
-            yield _result(it, res_h[:, k0:k1], sim, (ts_h.numpy()[k0:k1], float(path_h[i])) if ordered else None)
+            decoded = (ts_h.numpy()[k0:k1], float(path_h[i])) if ordered else None
+            if decode == "segments":
+                decoded += (keep_h.numpy()[k0:k1],)
+            yield _result(it, res_h[:, k0:k1], sim, decode, decoded)
 
 
-def _result(it, res, sim, decoded=None):
+def _result(it, res, sim, decode=None, decoded=None):
+    """`decoded`, for decode="monotonic": (seconds [K] int32 with -1 where not kept, path score); for decode="segments": ((start, end)
+    [K, 2] int32 with (-1, -1) where not kept or infeasible, path score, kept [K] bool)."""
     out = {"vid": it.get("vid"), "str": it["str"], "timestamp": res[0].astype(np.int64), "confidence": res[1].copy(),
            "score": res[2].copy(), "covered": res[3] > 0}
     if sim is not None:
         out["sim"] = sim
-    if decoded is not None:                           # (seconds [K] int32 with -1 where not kept, path score)
+    if decode == "monotonic":
         out["ordered_timestamp"] = decoded[0].astype(np.int64)
         out["ordered"] = decoded[0] >= 0
+        out["path_score"] = decoded[1]
+    elif decode == "segments":
+        out["segment_start"], out["segment_end"] = decoded[0][:, 0].astype(np.int64), decoded[0][:, 1].astype(np.int64)
+        out["segmented"] = decoded[2].copy()
         out["path_score"] = decoded[1]
     return out
 
@@ -308,19 +344,24 @@ def read_corpus(feature_dir, asr_json, vlen_csv, worker_id=0, num_workers=1):
 
 
 CSV_COLUMNS = ("vid", "timestamp", "text", "score", "confidence")
+SEGMENT_COLUMNS = ("start", "end")                    # appended by --decode segments
 
 
 def write_rows(writer, result, threshold=None):
     """HTM-AA rows of one video: covered sentences only, and with `threshold` only those with score > threshold.  A result of
     `align_corpus(decode="monotonic")` writes its ordered timestamps in the `timestamp` column (decode it with the same threshold as
-    `keep_threshold`: the rows written are then exactly the decoded ones); rows and columns are the same either way."""
+    `keep_threshold`: the rows written are then exactly the decoded ones); rows and columns are the same either way.  A result of
+    `align_corpus(decode="segments")` keeps every column as it is without a decode and appends SEGMENT_COLUMNS, the interval's
+    inclusive first and last second (-1 -1 for a video with more rows than seconds), again for the decoded rows under the same threshold."""
     stamp = result["ordered_timestamp"] if "ordered_timestamp" in result else result["timestamp"]
     n = 0
     for k, text in enumerate(result["str"]):
         if not result["covered"][k] or (threshold is not None and not float(result["score"][k]) > threshold):
             continue
-        writer.writerow([result["vid"], int(stamp[k]), text, repr(float(result["score"][k])),
-                         repr(float(result["confidence"][k]))])
+        row = [result["vid"], int(stamp[k]), text, repr(float(result["score"][k])), repr(float(result["confidence"][k]))]
+        if "segment_start" in result:
+            row += [int(result["segment_start"][k]), int(result["segment_end"][k])]
+        writer.writerow(row)
         n += 1
     return n
 
@@ -363,7 +404,7 @@ def make_embed_text(model, tokenizer):
     return embed_text
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--feature-dir", required=True)
@@ -376,12 +417,24 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=None, help="keep rows with score > threshold (default: every covered sentence)")
     ap.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
     ap.add_argument("--model", choices=("init", "cotrain"), default="init")
-    ap.add_argument("--decode", choices=("argmax", "monotonic"), default="argmax",
+    ap.add_argument("--decode", choices=("argmax", "monotonic", "segments"), default="argmax",
                     help="timestamp column: each sentence's own arg-max (default), or per video the non-decreasing seconds in ASR "
-                         "start order with the largest summed similarity over the rows written (--threshold picks them)")
+                         "start order with the largest summed similarity over the rows written (--threshold picks them); "
+                         "segments: the arg-max column, and appended columns start,end -- per video ordered, disjoint intervals "
+                         "of inclusive seconds for the rows written")
+    ap.add_argument("--width", type=float, default=1.0,
+                    help="--decode segments: a second counts for its sentence while its similarity lies within this many logits "
+                         "of the row's peak (>= 0; the default is a convention, tuned on nothing)")
     a = ap.parse_args(argv)
     if not 0 <= a.worker_id < a.num_workers:
         ap.error("--worker-id must lie in [0, --num-workers)")
+    if not a.width >= 0:
+        ap.error("--width must be a non-negative number")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     from .word2vec_model import Word2VecTokenizer
     vocab = np.load(a.vocab)
     model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
@@ -396,9 +449,9 @@ def main(argv=None):
     n_vid = n_rows = 0
     with open(a.out, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
+        w.writerow(CSV_COLUMNS + (SEGMENT_COLUMNS if a.decode == "segments" else ()))
         for res in align_corpus(model, corpus, embed, on_reject=on_reject, decode=None if a.decode == "argmax" else a.decode,
-                                keep_threshold=a.threshold if a.decode == "monotonic" else None):
+                                keep_threshold=a.threshold if a.decode != "argmax" else None, width=a.width):
             n_rows += write_rows(w, res, a.threshold)
             n_vid += 1
     print(f"{a.out}: {n_rows} sentences from {n_vid} videos" + (f", {len(rejected)} skipped" if rejected else ""), file=sys.stderr)

@@ -296,6 +296,24 @@ def monotonic_decode(sim, rows, order, vtab, keep, bp, run, ts, path):
                "tan_monotonic_decode")
 
 
+def segment_decode(sim, rows, order, vtab, keep, bias, bp, run, seg, path):
+    """seg [sum K, 2] int32 <- per video the ordered, disjoint inclusive intervals (s, e) with the largest summed gain
+    sim[r][t] - bias[r] over its kept rows, (-1, -1) for the rows not kept; path [n_videos] f32 <- the path's score, -inf for a video
+    with more kept rows than seconds (tan_segment_decode).  sim, rows, order, vtab, keep: as for monotonic_decode; bias [sum K] f32.
+    Scratch: bp [2 * sim.numel()] int32, run [>= sum vlen] f32."""
+    n = rows.shape[0]
+    assert rows.dtype == torch.int32 and rows.shape == (n, 2) and rows.is_contiguous() and sim.is_contiguous()
+    assert order.dtype == torch.int32 and order.shape == (n,) and order.is_contiguous()
+    assert vtab.dtype == torch.int32 and vtab.dim() == 2 and vtab.shape[1] == 3 and vtab.is_contiguous()
+    assert keep is None or (keep.dtype in (torch.bool, torch.uint8) and keep.shape == (n,) and keep.is_contiguous())
+    assert bias.dtype == torch.float32 and bias.shape == (n,) and bias.is_contiguous()
+    assert bp.dtype == torch.int32 and bp.numel() == 2 * sim.numel() and bp.is_contiguous() and run.is_contiguous()
+    assert seg.dtype == torch.int32 and seg.shape == (n, 2) and seg.is_contiguous() and path.shape == (vtab.shape[0],)
+    _lib.check(_lib.lib().tan_segment_decode(_f32(sim), _ptr(rows), _ptr(order), _ptr(vtab), vtab.shape[0], _ptr(keep), _f32(bias),
+                                             n, sim.numel(), run.numel(), _ptr(bp), _f32(run), _ptr(seg), _f32(path), _stream()),
+               "tan_segment_decode")
+
+
 def rank_topk_ws_bytes(Q, N, k):
     n = _lib.lib().tan_rank_topk_ws_bytes(Q, N, k)
     if n < 0:

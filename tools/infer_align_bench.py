@@ -2,13 +2,16 @@
 `make_batched_sim_fn`, every sentence a candidate), same model, same synthetic corpus, one process, ABBA order, device-synchronised
 wall clocks.  Prints one JSON line.
 
-    python tools/infer_align_bench.py [--videos 256] [--reps 2] [--only corpus] [--decode monotonic]
+    python tools/infer_align_bench.py [--videos 256] [--reps 2] [--only corpus] [--decode monotonic|segments]
 
 Corpus: seeded, vlen uniform in [120, 900] s, one sentence per ~8 s, [vlen, 1024] f16 features, random [K, 512] sentence embeddings
 (looked up, so neither path pays for a language model).  Model: E6D6, bf16, alignability head, random weights.
 `--only corpus` runs align_corpus alone (for a `rocprofv3 --kernel-trace --stats` run of its own).
 `--decode monotonic` measures instead what the order-preserving decode costs: align_corpus with it against align_corpus without,
 ABBA in one process (with `--only corpus`: align_corpus with the decode alone).
+`--decode segments` measures the segmental decode against both yardsticks in one process: align_corpus plain, with the monotonic decode
+and with the segmental one, in alternating order (A B C C B A), medians; and the two decode launches alone over the corpus's own chunk
+tables (random stitched rows, every row kept, bias = row maximum - 1), alternating, device events, median per chunk.
 """
 import argparse
 import json
@@ -41,13 +44,43 @@ def corpus(n, seed=0):
     return vids
 
 
+def decode_launch_us(vids, windows_per_pass, reps=20):
+    """The two decode launches alone over the chunk tables align_corpus builds for `vids` (random stitched rows, every row kept):
+    per chunk the median device-event time in microseconds, the two kernels alternating."""
+    from temporalalignnet_amd import ops
+    from temporalalignnet_amd.infer_align import JOINT_MAX_LEN, _chunks
+    out = []
+    for ch in _chunks(vids, 64, windows_per_pass, None, (JOINT_MAX_LEN[torch.bfloat16] - 64) // 8 * 8, None, ordered=True):
+        sim = torch.randn(ch.n_acc, device="cuda") * 5
+        rows, order, vtab = ch.rows.cuda(), ch.order.cuda(), ch.vtab.cuda()
+        bias = torch.cat([sim[ch.a_off[i]:ch.a_off[i + 1]].view(-1, it["vlen"]).max(-1).values for i, it in enumerate(ch.items)]) - 1.0
+        bp = torch.empty(2 * ch.n_acc, dtype=torch.int32, device="cuda")
+        run, path = torch.empty(int(ch.v_off[-1]), device="cuda"), torch.empty(len(ch.items), device="cuda")
+        ts, seg = (torch.empty(s, dtype=torch.int32, device="cuda") for s in ((ch.n_rows,), (ch.n_rows, 2)))
+        fns = {"monotonic": lambda: ops.monotonic_decode(sim, rows, order, vtab, None, bp[:ch.n_acc], run, ts, path),
+               "segments": lambda: ops.segment_decode(sim, rows, order, vtab, None, bias, bp, run, seg, path)}
+        us = {k: [] for k in fns}
+        for r in range(reps + 2):              # the first two rounds warm up
+            for k in sorted(fns, reverse=bool(r % 2)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fns[k]()
+                e1.record()
+                e1.synchronize()
+                if r >= 2:
+                    us[k].append(e0.elapsed_time(e1) * 1e3)
+        out.append({"videos": len(ch.items), "sentences": ch.n_rows, "longest_vlen": int(max(it["vlen"] for it in ch.items)),
+                    **{k: round(float(np.median(v)), 1) for k, v in us.items()}})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--videos", type=int, default=256)
     ap.add_argument("--reps", type=int, default=2, help="ABBA blocks")
     ap.add_argument("--windows-per-pass", type=int, default=256)
     ap.add_argument("--only", choices=("corpus",), default=None)
-    ap.add_argument("--decode", choices=("argmax", "monotonic"), default="argmax")
+    ap.add_argument("--decode", choices=("argmax", "monotonic", "segments"), default="argmax")
     a = ap.parse_args()
     decode = None if a.decode == "argmax" else a.decode
     torch.manual_seed(0)
@@ -72,12 +105,19 @@ def main():
             warnings.simplefilter("ignore")
             test_alignment_htm(None, vids, return_per_video=True, batched_sim=make_batched_sim_fn(model, embed))
 
+    def run_monotonic():
+        for _ in align_corpus(model, vids, embed, windows_per_pass=a.windows_per_pass, decode="monotonic"):
+            pass
+
     other = "per_video" if decode is None else "argmax"             # what `corpus` is measured against
     paths = {"corpus": run_corpus} if a.only else {"corpus": run_corpus, other: run_per_video if decode is None else run_argmax}
+    order = ["corpus"] if a.only else ["corpus", other, other, "corpus"]
+    if decode == "segments" and not a.only:    # both yardsticks in the same run
+        paths["monotonic"] = run_monotonic
+        order = ["argmax", "monotonic", "corpus", "corpus", "monotonic", "argmax"]
     for f in paths.values():                   # warm-up: code objects, workspaces of every pass shape
         f()
     times = {k: [] for k in paths}
-    order = ["corpus"] if a.only else ["corpus", other, other, "corpus"]
     for _ in range(a.reps):
         for k in order:
             torch.cuda.synchronize()
@@ -94,6 +134,15 @@ def main():
         out["speedup_median"] = round(float(np.median(times["per_video"]) / np.median(times["corpus"])), 2)
     if "argmax" in out:
         out["decode_cost_median"] = round(float(np.median(times["corpus"]) / np.median(times["argmax"])), 4)
+    if "monotonic" in out:
+        out["monotonic_cost_median"] = round(float(np.median(times["monotonic"]) / np.median(times["argmax"])), 4)
+    if decode == "segments" and not a.only:    # (a run to trace holds align_corpus's own launches only)
+        per_chunk = decode_launch_us(vids, a.windows_per_pass)
+        tot = {k: sum(c[k] for c in per_chunk) for k in ("monotonic", "segments")}
+        out["decode_launch_us_per_chunk"] = per_chunk
+        out["segments_over_monotonic_launch"] = round(tot["segments"] / tot["monotonic"], 3)
+        if "argmax" in out:                    # the launch against everything the plain path does for the same chunks, host time included
+            out["segments_launch_share_of_plain_wall"] = round(tot["segments"] * 1e-6 / float(np.median(times["argmax"])), 5)
     print(json.dumps(out))
 
 

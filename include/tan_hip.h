@@ -1010,6 +1010,41 @@ int tan_rank_topk_video_filtered_e4m3(const void* Tq, const float* q_scale, cons
                                       int C, const int* v_off, long n_videos, const void* filt, int k, int splits, float* top_score,
                                       int* top_row, int* top_video, void* ws, void* stream);
 
+/* ---- corpus annotation: which of a fixed vocabulary of labels does every row of the index show (`search.annotate`) ----
+ * tan_label_topk: the k best labels of every index row.  Tl [L, 512] label features, Vn [N, 512] index rows, in the formats of
+ *   tan_rank_topk (TAN_F32: exact-f32 MFMA; TAN_BF16), 16-byte aligned.  top_score / top_label [N, k]: row n's k best
+ *   (score f32, label int32) by descending score, equal scores by ascending label; score(l, n) is the f32 accumulation of the
+ *   operand products, by the MFMA chain of tan_rank_topk(Tq = Tl, Vn).  1 <= k <= min(32, L), 1 <= L < 2^31, 1 <= N < 2^31.
+ *   One launch, one workgroup per 128 index rows: the rows stay in registers (each is read from memory once in the whole launch),
+ *   the labels stream through LDS in 64-label tiles, and a row's list is complete inside its workgroup -- nothing whose size
+ *   grows with N * L is stored, no scratch, no merge launch, no atomics: bit-identical from run to run.  Tails in N and L are
+ *   masked in the kernel.  Another width, k out of range, an unknown dtype, a NULL pointer, bad sizes: TAN_ERR_BAD_ARG, nothing
+ *   launched.
+ * tan_label_topk_e4m3: the same over the e4m3 codes and per-row power-of-two scales of tan_rank_topk_e4m3 (l_scale [L],
+ *   v_scale [N]); score(l, n) = (acc * v_scale[n]) * l_scale[l], two f32 multiplies in that order -- tan_rank_topk_e4m3's formula
+ *   with the label in the query's place.
+ * tan_label_runs: the rows' best labels -> label segments.  lab[n] = top_label[n * stride] if top_score[n * stride] >= threshold,
+ *   else -1 (background; a NaN score is background).  Only column 0 of the [N, stride] lists is read.  v_off [n_videos + 1] as in
+ *   tan_rank_topk_video.  A RUN is a maximal range of rows [a, b] inside one video with lab constant and not -1 (two adjacent
+ *   videos that end and begin with the same label give two runs); runs shorter than min_len (>= 1) are dropped.  The kept runs
+ *   are written in ascending a: run_video, run_start = a, run_end = b (inclusive), run_label, run_peak_score = the largest
+ *   top_score[n * stride] of the run and run_peak_row = the smallest row that attains it.  n_runs[0] = the number of kept runs,
+ *   even above cap; only the first cap are written.  label_rows [L], if not NULL, is overwritten with the number of rows whose
+ *   lab is l, whatever min_len is (integer atomics).  ws: tan_label_runs_ws_bytes(N) bytes (-1 for N outside [1, 2^31)), 4-byte
+ *   aligned.  Six launches (flags / scan / fill / keep / scan / emit) and a memset of label_rows; every result is
+ *   order-independent or computed in a fixed order: bit-identical from run to run.  A label outside [0, L) or a v_off that breaks
+ *   its contract is the CALLER's error: labels and positions are clamped, nothing is read or written out of bounds, and the runs
+ *   are then unspecified.  threshold NaN, min_len < 1, cap < 0, stride < 1, n_videos outside [1, N], a NULL pointer other than
+ *   label_rows, sizes outside the ranges above: TAN_ERR_BAD_ARG, nothing launched.                                               */
+int tan_label_topk(const void* Tl, const void* Vn, int dtype, long L, long N, int C, int k, float* top_score, int* top_label,
+                   void* stream);
+int tan_label_topk_e4m3(const void* Tl, const float* l_scale, const void* Vn, const float* v_scale, long L, long N, int C, int k,
+                        float* top_score, int* top_label, void* stream);
+long tan_label_runs_ws_bytes(long N);
+int tan_label_runs(const float* top_score, const int* top_label, int stride, long N, long L, const int* v_off, long n_videos,
+                   float threshold, int min_len, long cap, int* n_runs, int* run_video, int* run_start, int* run_end, int* run_label,
+                   int* run_peak_row, float* run_peak_score, int* label_rows, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@
 // tan_rank_topk_filtered / tan_rank_topk_video_filtered sweep only the rows a FILTER admits (rank_kernel's FILTER mode): the image
 // tan_row_filter_build makes from row spans lists the 64-row tiles that hold an admitted row, with a row mask each; a split walks a
 // range of that list and masks the other rows, so the lists are the plain sweep's over the gathered admitted rows, bit for bit.
+// tan_label_topk / _e4m3 answer the transposed question, the k best LABELS of every index row: label_kernel is the sweep with the
+// roles swapped (a tile of index rows resident, the label matrix streamed; tile_scores, the candidate buffers and sort64 carry over),
+// one workgroup per 128 rows, no splits, no scratch, no merge.  tan_label_runs compacts the rows' best labels into label segments.
 //
 // tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
 // of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
@@ -1230,6 +1233,301 @@ int seq_scores_launch(const void* Tq, const void* Vn, long Qt, long N, const int
     return 0;
 }
 
+// ---- corpus annotation: the k best LABELS of every index row (include/tan_hip.h) ----
+// rank_kernel's sweep with the roles swapped: a workgroup owns one tile of BQ = 128 index rows -- a wave keeps its 32 rows in
+// registers as the B fragments, read from HBM once in the whole launch -- and the label matrix streams through LDS in 64-label tiles
+// by tile_scores.  A lane's 16 accumulators belong to ONE index row, whose candidates (score, label) at or above its threshold go
+// to its 64-slot LDS buffer; sort64 compacts a buffer that would overflow and raises the threshold.  A row's list is complete
+// inside its workgroup: no splits, no scratch, no merge -- the epilogue sorts each buffer once more and writes the k best to
+// top_s / top_l.  e4m3: tile_scores multiplies by the TILE's scale first and the resident column's second, and the score is defined
+// as (acc * v_scale[n]) * l_scale[l] (tan_rank_topk_e4m3's formula with the label as the query), so tile_scores gets a tile scale
+// of 1 and the row's scale as the column's -- a multiply by 1 is exact -- and the label tile's 64 scales, loaded with the tile's
+// first chunk, wait in a buffer of their own (two, by tile parity: a wave may stage tile t + 1's while another still reads tile
+// t's) for the multiply after the MFMA loop.
+template <typename T> constexpr int label_lds() { return sweep_lds<T>() + (sizeof(T) == 1 ? 2 * BN * 4 : 0); }
+
+template <typename T>
+__global__ void __launch_bounds__(256) label_kernel(const T* __restrict__ Tl, const T* __restrict__ Vn, long L, long N, int k,
+                                                    long l_tiles, float* __restrict__ top_s, int* __restrict__ top_l,
+                                                    const float* __restrict__ l_scale, const float* __restrict__ v_scale) {
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int LD = RCfg<T>::LD, KS = M::KS, NCH = RC / RCfg<T>::KC, NFR = RC / KS;
+    constexpr int TS = BN * LD;
+    constexpr long ROWB = (long)RC * sizeof(T);
+    constexpr bool F8 = sizeof(T) == 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* tile = reinterpret_cast<T*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + 2 * TS * sizeof(T));   // F8: tile_scores' tile scales, all 1 here
+    float* bs = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16);
+    int* bn = reinterpret_cast<int*>(bs + 4 * 32 * CAP);
+    float* lsc = reinterpret_cast<float*>(bn + 4 * 32 * CAP);         // F8: the label scales of two tiles
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
+    const long nblk = (long)blockIdx.x * BQ;
+    const long nme = nblk + wave * 32 + col;
+    const long nrow = nme < N ? nme : N - 1;                       // a tail column repeats the last row and is not written
+
+    frag_t qf[NFR];                                                // the wave's 32 index rows, resident
+    {
+        const T* vrow = Vn + nrow * RC;
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(vrow, j, lane);
+    }
+    float vs = 1.0f, pls = 0.0f;
+    const float one = 1.0f;
+    if constexpr (F8) vs = v_scale[nrow];
+
+    int fill = 0;
+    float thr = -INFINITY;
+    const int bbase = (wave * 32 + col) * CAP;
+
+    uint4 pre[4];
+    auto issue = [&](long t, int kc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
+            const long l = t * BN + row;
+            pre[i] = l < L ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Tl) + l * ROWB + kc * 256 + c16 * 16)
+                           : make_uint4(0, 0, 0, 0);
+        }
+        if constexpr (F8) {
+            if (kc == 0 && tid < BN) {                             // the label scales ride with the tile's first chunk
+                const long l = t * BN + tid;
+                pls = l < L ? l_scale[l] : 0.0f;
+            }
+        }
+    };
+
+    // rank_kernel's compaction: sorts every buffer of the wave that `need` more entries would overflow, keeps its k best and raises
+    // the row's threshold
+    auto compact = [&](int need) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (int qi = 0; qi < 32; ++qi) {
+            const int f = __builtin_amdgcn_readlane(fill, qi), nd = __builtin_amdgcn_readlane(need, qi);
+            if (f + nd <= CAP) continue;
+            const int b = (wave * 32 + qi) * CAP;
+            float s = lane < f ? bs[b + lane] : -INFINITY;
+            int n = lane < f ? bn[b + lane] : SENT_ROW;
+            sort64(s, n, lane);
+            const int nf = f < k ? f : k;
+            if (lane < nf) { bs[b + lane] = s; bn[b + lane] = n; }
+            const float th = __shfl(s, k - 1, 64);
+            if (col == qi) { fill = nf; thr = th; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    };
+
+    issue(0, 0);                                                   // l_tiles >= 1
+    for (long t = 0; t < l_tiles; ++t) {
+        if constexpr (F8) {
+            // read after this tile's barriers; the buffer's next write follows tile t + 1's barriers, which no wave passes before
+            // every wave has left this tile's epilogue
+            if (tid < BN) lsc[(t & 1) * BN + tid] = pls;
+        }
+        f32x16 acc[2];
+        tile_scores<T>(tile, sc, tid, lane, pre, one, qf, vs, acc, [&](int kc) {
+            if (kc + 1 < NCH) issue(t, kc + 1);
+            else if (t + 1 < l_tiles) issue(t + 1, 0);
+        });
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            if constexpr (F8) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 s4 = *reinterpret_cast<const float4*>(lsc + (t & 1) * BN + rt * 32 + 8 * g + 4 * (lane >> 5));
+                    acc[rt][4 * g + 0] *= s4.x;
+                    acc[rt][4 * g + 1] *= s4.y;
+                    acc[rt][4 * g + 2] *= s4.z;
+                    acc[rt][4 * g + 3] *= s4.w;
+                }
+            }
+            const long lbase = t * BN + rt * 32;
+            unsigned mask = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (lbase + acc_row(r, lane) < L && acc[rt][r] >= thr) mask |= 1u << r;
+            const int c_me = __popc(mask), c_pt = __shfl_xor(c_me, 32, 64), need = c_me + c_pt;
+            if (__any(fill + need > CAP)) compact(need);
+            int off = bbase + fill + ((lane >> 5) ? c_pt : 0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if ((mask >> r) & 1) {
+                    bs[off] = acc[rt][r];
+                    bn[off] = (int)(lbase + acc_row(r, lane));
+                    ++off;
+                }
+            fill += need;
+        }
+    }
+
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    for (int qi = 0; qi < 32; ++qi) {
+        const int f = __builtin_amdgcn_readlane(fill, qi);
+        const int b = (wave * 32 + qi) * CAP;
+        float s = lane < f ? bs[b + lane] : -INFINITY;
+        int n = lane < f ? bn[b + lane] : SENT_ROW;
+        sort64(s, n, lane);
+        const long row = nblk + wave * 32 + qi;
+        if (row < N && lane < k) {
+            top_s[row * k + lane] = s;
+            top_l[row * k + lane] = n;
+        }
+    }
+}
+
+template <typename T>
+int label_launch(const void* Tl, const void* Vn, long L, long N, int k, float* top_s, int* top_l, hipStream_t st,
+                 const float* l_scale = nullptr, const float* v_scale = nullptr) {
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)label_kernel<T>, label_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((label_kernel<T>), dim3(cdiv(N, BQ)), dim3(256), label_lds<T>(), st, (const T*)Tl, (const T*)Vn, L, N, k,
+                       n_index_tiles(L), top_s, top_l, l_scale, v_scale);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- tan_label_runs: the rows' best labels -> label segments (include/tan_hip.h) ----
+// lab[n] is the row's column-0 label (clamped into [0, L)) if its score is >= threshold, else -1.  A row STARTS a run if lab != -1
+// and the row before it is in another video or has another lab, and ENDS one by the same rule on the row after it: every maximal
+// run has one start and one end, and the i-th start belongs with the i-th end.  Six launches, all results order-independent:
+//   1. flags : per row, its start / end flags (a byte) and the block's counts of each
+//   2. scan  : one block per count array turns the block counts into first positions (filter_scan_kernel's loop) and stores the total
+//   3. fill  : the i-th start / end row -> rs[i] / re[i]
+//   4. keep  : per run, length >= min_len -> its position among the block's kept runs (or -1) and the block's count; the run's
+//              length is added to label_rows[label] (integer atomics: order-independent)
+//   5. scan  : the kept counts -> first positions; the total is n_runs[0]
+//   6. emit  : 16 lanes per run fold its (score, row) by better() -- the largest score, its smallest row -- and lane 0 writes the
+//              run at its kept position if that is below cap
+// ws (int32 words, NB = ceil(N / 256)): rs [N] | re [N] | kpos [N] | counts 3 x [NB] | totals [4] | flags, N bytes
+constexpr int RUN_LANES = 16;
+inline long runs_ws_words(long N) { const long NB = (N + 255) / 256; return 3 * N + 3 * NB + 4 + (N + 3) / 4; }
+
+struct RunsWs {
+    int *rs, *re, *kpos, *cs, *ce, *ck, *tot;
+    unsigned char* flags;
+    __host__ __device__ RunsWs(int* w, long N) {
+        const long NB = (N + 255) / 256;
+        rs = w; re = rs + N; kpos = re + N; cs = kpos + N; ce = cs + NB; ck = ce + NB; tot = ck + NB;
+        flags = reinterpret_cast<unsigned char*>(tot + 4);
+    }
+};
+
+__device__ __forceinline__ int row_lab(const float* __restrict__ ts, const int* __restrict__ tl, int stride, long n, long L, float thr) {
+    if (!(ts[n * stride] >= thr)) return -1;                       // NaN: background
+    const long l = tl[n * stride];
+    return (int)(l < 0 ? 0 : (l >= L ? L - 1 : l));
+}
+
+__global__ void __launch_bounds__(256) runs_flag_kernel(const float* __restrict__ ts, const int* __restrict__ tl, int stride, long N, long L,
+                                                        const int* __restrict__ v_off, int n_videos, float thr, int* __restrict__ w) {
+    const RunsWs ws(w, N);
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;
+    bool st = false, en = false;
+    if (n < N) {
+        const int lab = row_lab(ts, tl, stride, n, L, thr);
+        if (lab != -1) {
+            // first(r): row r is the first row of its video -- one function of r, whatever v_off holds
+            auto first = [&](long r) { return (long)v_off[video_search(v_off, r, 0, n_videos - 1)] == r; };
+            st = n == 0 || row_lab(ts, tl, stride, n - 1, L, thr) != lab || first(n);
+            en = n == N - 1 || row_lab(ts, tl, stride, n + 1, L, thr) != lab || first(n + 1);
+        }
+        ws.flags[n] = (unsigned char)((st ? 1 : 0) | (en ? 2 : 0));
+    }
+    const int c_st = __syncthreads_count(st), c_en = __syncthreads_count(en);
+    if (threadIdx.x == 0) { ws.cs[blockIdx.x] = c_st; ws.ce[blockIdx.x] = c_en; }
+}
+
+// block b of the grid scans count array cnt + b * NB in place (exclusive) and stores its total in tot[b] and, if out, in out[0]
+__global__ void __launch_bounds__(256) runs_scan_kernel(int* __restrict__ cnt, long NB, int* __restrict__ tot, int* __restrict__ out) {
+    __shared__ int wsum[4];
+    int* c = cnt + (long)blockIdx.x * NB;
+    int carry = 0;
+    for (long b0 = 0; b0 < NB; b0 += 256) {
+        const long b = b0 + threadIdx.x;
+        int total;
+        const int ex = block_scan256(b < NB ? c[b] : 0, wsum, total);
+        if (b < NB) c[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        tot[blockIdx.x] = carry;
+        if (out) out[0] = carry;
+    }
+}
+
+__global__ void __launch_bounds__(256) runs_fill_kernel(long N, int* __restrict__ w) {
+    __shared__ int wsum[4];
+    const RunsWs ws(w, N);
+    const long n = (long)blockIdx.x * 256 + threadIdx.x;
+    const int f = n < N ? ws.flags[n] : 0;
+    int total;
+    const long ps = (long)ws.cs[blockIdx.x] + block_scan256(f & 1, wsum, total);
+    const long pe = (long)ws.ce[blockIdx.x] + block_scan256((f >> 1) & 1, wsum, total);
+    if ((f & 1) && ps >= 0 && ps < N) ws.rs[ps] = (int)n;
+    if ((f & 2) && pe >= 0 && pe < N) ws.re[pe] = (int)n;
+}
+
+__global__ void __launch_bounds__(256) runs_keep_kernel(const int* __restrict__ tl, int stride, long N, long L, int min_len,
+                                                        int* __restrict__ label_rows, int* __restrict__ w) {
+    __shared__ int wsum[4];
+    const RunsWs ws(w, N);
+    const long R = ws.tot[0] < ws.tot[1] ? ws.tot[0] : ws.tot[1];  // equal: one start and one end per run
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    bool keep = false;
+    if (i < R) {
+        const long a = ws.rs[i], b = ws.re[i];
+        if (a >= 0 && b >= a && b < N) {
+            keep = b - a + 1 >= min_len;
+            if (label_rows) {
+                const long l = tl[a * stride];
+                atomicAdd(&label_rows[l < 0 ? 0 : (l >= L ? L - 1 : l)], (int)(b - a + 1));
+            }
+        }
+    }
+    int total;
+    const int local = block_scan256(keep ? 1 : 0, wsum, total);
+    if (i < N) ws.kpos[i] = keep ? local : -1;
+    if (threadIdx.x == 0) ws.ck[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256) runs_emit_kernel(const float* __restrict__ ts, const int* __restrict__ tl, int stride, long N, long L,
+                                                        const int* __restrict__ v_off, int n_videos, long cap, int* __restrict__ run_video,
+                                                        int* __restrict__ run_start, int* __restrict__ run_end, int* __restrict__ run_label,
+                                                        int* __restrict__ run_peak_row, float* __restrict__ run_peak_score,
+                                                        int* __restrict__ w) {
+    const RunsWs ws(w, N);
+    const long R = ws.tot[0] < ws.tot[1] ? ws.tot[0] : ws.tot[1];
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) / RUN_LANES;
+    const int sub = threadIdx.x % RUN_LANES;
+    const int local = i < R ? ws.kpos[i] : -1;                     // the same for a run's 16 lanes
+    const long p = local < 0 ? -1 : (long)ws.ck[i / 256] + local;
+    const bool live = p >= 0 && p < cap;
+    const long a = live ? ws.rs[i] : 0, b = live ? ws.re[i] : -1;  // kept: 0 <= a <= b < N
+    float s = -INFINITY;
+    int n = SENT_ROW;
+    for (long r = a + sub; r <= b; r += RUN_LANES) {
+        const float v = ts[r * stride];
+        if (better(v, (int)r, s, n)) { s = v; n = (int)r; }
+    }
+#pragma unroll
+    for (int o = RUN_LANES / 2; o > 0; o >>= 1) {
+        const float os = __shfl_xor(s, o, 64);
+        const int on = __shfl_xor(n, o, 64);
+        if (better(os, on, s, n)) { s = os; n = on; }
+    }
+    if (live && sub == 0) {
+        const long l = tl[a * stride];
+        run_video[p] = video_search(v_off, a, 0, n_videos - 1);
+        run_start[p] = (int)a;
+        run_end[p] = (int)b;
+        run_label[p] = (int)(l < 0 ? 0 : (l >= L ? L - 1 : l));
+        run_peak_row[p] = n;
+        run_peak_score[p] = s;
+    }
+}
+
 }  // namespace
 }  // namespace tal
 
@@ -1425,6 +1723,61 @@ extern "C" int tan_sequence_scores_e4m3(const void* Tq, const float* q_scale, co
     TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)x_off % 8 == 0);
     return seq_scores_launch<e4m3_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, (hipStream_t)stream,
                                      q_scale, v_scale);
+}
+
+extern "C" int tan_label_topk(const void* Tl, const void* Vn, int dtype, long L, long N, int C, int k, float* top_score, int* top_label,
+                              void* stream) {
+    TAN_REQUIRE(Tl && Vn && top_score && top_label && (dtype == TAN_F32 || dtype == TAN_BF16));
+    TAN_REQUIRE(C == RC && L >= 1 && L < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= L);
+    TAN_REQUIRE((uintptr_t)Tl % 16 == 0 && (uintptr_t)Vn % 16 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == TAN_BF16 ? label_launch<bf16_t>(Tl, Vn, L, N, k, top_score, top_label, st)
+                             : label_launch<float>(Tl, Vn, L, N, k, top_score, top_label, st);
+}
+
+extern "C" int tan_label_topk_e4m3(const void* Tl, const float* l_scale, const void* Vn, const float* v_scale, long L, long N, int C,
+                                   int k, float* top_score, int* top_label, void* stream) {
+    TAN_REQUIRE(Tl && l_scale && Vn && v_scale && top_score && top_label);
+    TAN_REQUIRE(C == RC && L >= 1 && L < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= L);
+    TAN_REQUIRE((uintptr_t)Tl % 16 == 0 && (uintptr_t)Vn % 16 == 0);
+    return label_launch<e4m3_t>(Tl, Vn, L, N, k, top_score, top_label, (hipStream_t)stream, l_scale, v_scale);
+}
+
+extern "C" long tan_label_runs_ws_bytes(long N) {
+    if (N < 1 || N >= (1L << 31)) return TAN_ERR_BAD_ARG;
+    return (runs_ws_words(N) * 4 + 15) / 16 * 16;
+}
+
+extern "C" int tan_label_runs(const float* top_score, const int* top_label, int stride, long N, long L, const int* v_off, long n_videos,
+                              float threshold, int min_len, long cap, int* n_runs, int* run_video, int* run_start, int* run_end,
+                              int* run_label, int* run_peak_row, float* run_peak_score, int* label_rows, void* ws, void* stream) {
+    TAN_REQUIRE(top_score && top_label && v_off && n_runs && run_video && run_start && run_end && run_label && run_peak_row &&
+                run_peak_score && ws);
+    TAN_REQUIRE(stride >= 1 && N >= 1 && N < (1L << 31) && L >= 1 && L < (1L << 31) && n_videos >= 1 && n_videos <= N);
+    TAN_REQUIRE(threshold == threshold && min_len >= 1 && cap >= 0 && (uintptr_t)ws % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    int* w = (int*)ws;
+    const RunsWs lay(w, N);
+    const long NB = (N + 255) / 256;
+    if (label_rows) {
+        const hipError_t e = hipMemsetAsync(label_rows, 0, (size_t)L * 4, st);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(runs_flag_kernel, dim3((unsigned)NB), dim3(256), 0, st, top_score, top_label, stride, N, L, v_off, (int)n_videos,
+                       threshold, w);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(runs_scan_kernel, dim3(2), dim3(256), 0, st, lay.cs, NB, lay.tot, (int*)nullptr);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(runs_fill_kernel, dim3((unsigned)NB), dim3(256), 0, st, N, w);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(runs_keep_kernel, dim3((unsigned)NB), dim3(256), 0, st, top_label, stride, N, L, min_len, label_rows, w);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(runs_scan_kernel, dim3(1), dim3(256), 0, st, lay.ck, NB, lay.tot + 2, n_runs);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(runs_emit_kernel, dim3(cdiv(N * RUN_LANES, 256)), dim3(256), 0, st, top_score, top_label, stride, N, L, v_off,
+                       (int)n_videos, cap, run_video, run_start, run_end, run_label, run_peak_row, run_peak_score, w);
+    TAN_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* codes, float* scale, void* stream) {

@@ -526,6 +526,107 @@ def rank_topk_video_filtered(tq, vn, v_off, filt, k, *, q_scale=None, v_scale=No
     return top_s, top_r, top_v
 
 
+def _label_out(what, N, k, dev, out):
+    if out is None:
+        return torch.empty(N, k, dtype=torch.float32, device=dev), torch.empty(N, k, dtype=torch.int32, device=dev)
+    top_s, top_l = out
+    if top_s.dtype != torch.float32 or top_l.dtype != torch.int32 or top_s.shape != (N, k) or top_l.shape != (N, k) \
+            or not top_s.is_contiguous() or not top_l.is_contiguous():
+        raise ValueError(f"{what}: out is (top_score f32 [N, k], top_label int32 [N, k]), contiguous")
+    return top_s, top_l
+
+
+def label_topk(tl, vn, k=1, *, out=None):
+    """The k best LABELS of every index row (tan_label_topk): tl [L, 512] label features, vn [N, 512] index rows, both bf16 or both
+    f32, contiguous.  Returns (top_score [N, k] f32, top_label [N, k] int32), by descending score, equal scores by ascending label;
+    1 <= k <= min(32, L).  One launch without scratch; nothing of size N * L is stored.  out: caller-owned outputs (the same
+    2-tuple) instead of fresh ones."""
+    if tl.dim() != 2 or vn.dim() != 2 or not tl.is_contiguous() or not vn.is_contiguous() or tl.dtype != vn.dtype:
+        raise ValueError("label_topk: tl [L, 512] and vn [N, 512] are contiguous and of one dtype")
+    if tl.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("label_topk: bf16 or f32 rows (e4m3 codes go to label_topk_e4m3)")
+    L_, N, dev = tl.shape[0], vn.shape[0], vn.device
+    if tl.shape[1] != 512 or vn.shape[1] != 512 or N < 1 or not 1 <= int(k) <= min(32, L_):
+        raise ValueError("label_topk: width 512, N >= 1 and 1 <= k <= min(32, L)")
+    top_s, top_l = _label_out("label_topk", N, int(k), dev, out)
+    _lib.check(_lib.lib().tan_label_topk(_ptr(tl), _ptr(vn), _dt(tl), L_, N, 512, int(k), _f32(top_s), _ptr(top_l), _stream()),
+               "tan_label_topk")
+    return top_s, top_l
+
+
+def label_topk_e4m3(tl, l_scale, vn, v_scale, k=1, *, out=None):
+    """`label_topk` over e4m3 rows (tan_label_topk_e4m3): tl [L, 512] / vn [N, 512] uint8 codes with their f32 row scales l_scale [L]
+    / v_scale [N], as `quantize_rows_e4m3` makes them; score = (acc * v_scale[n]) * l_scale[l].  Everything else as `label_topk`."""
+    if tl.dim() != 2 or vn.dim() != 2 or not tl.is_contiguous() or not vn.is_contiguous():
+        raise ValueError("label_topk_e4m3: tl [L, 512] and vn [N, 512] are contiguous")
+    if tl.dtype != torch.uint8 or vn.dtype != torch.uint8:
+        raise TypeError("label_topk_e4m3: uint8 e4m3 codes")
+    L_, N, dev = tl.shape[0], vn.shape[0], vn.device
+    if tl.shape[1] != 512 or vn.shape[1] != 512 or N < 1 or not 1 <= int(k) <= min(32, L_):
+        raise ValueError("label_topk_e4m3: width 512, N >= 1 and 1 <= k <= min(32, L)")
+    for s, n in ((l_scale, L_), (v_scale, N)):
+        if s is None or s.dtype != torch.float32 or s.shape != (n,) or not s.is_contiguous():
+            raise ValueError("label_topk_e4m3: l_scale [L] and v_scale [N] are contiguous f32")
+    top_s, top_l = _label_out("label_topk_e4m3", N, int(k), dev, out)
+    _lib.check(_lib.lib().tan_label_topk_e4m3(_ptr(tl), _f32(l_scale), _ptr(vn), _f32(v_scale), L_, N, 512, int(k), _f32(top_s),
+                                              _ptr(top_l), _stream()), "tan_label_topk_e4m3")
+    return top_s, top_l
+
+
+def label_runs_ws_bytes(N):
+    n = _lib.lib().tan_label_runs_ws_bytes(N)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_label_runs_ws_bytes({N}): bad argument")
+    return n
+
+
+RUN_FIELDS = ("video", "start", "end", "label", "peak_row")             # label_runs' int32 columns, in this order; then peak_score f32
+
+
+def label_runs(top_score, top_label, L, v_off, threshold, min_len=1, *, cap=None, label_rows=False, out=None, ws=None):
+    """Label segments from `label_topk`'s lists (tan_label_runs; the exact definition is in include/tan_hip.h): top_score f32 /
+    top_label int32 [N, k] (only column 0 is read), L labels, v_off [n_videos + 1] int32 (device).  A row's label is its best one
+    if its score is >= threshold, else background; a run is a maximal range of rows of one video with one label; runs shorter
+    than min_len are dropped.  Returns (n_runs int32 [1], runs int32 [5, cap]: RUN_FIELDS -- video, first and last row
+    (inclusive), label, peak row --, peak_score f32 [cap], label_rows int32 [L] or None), all on the device and nothing read
+    back: n_runs[0] is the number of kept runs even above cap (default: N, which always suffices), and only the first
+    min(n_runs, cap) columns are written.  label_rows=True: also count the rows of every label (whatever min_len is).
+    out: caller-owned (n_runs, runs, peak_score, label_rows) instead of fresh ones; ws: scratch (uint8, >= label_runs_ws_bytes)."""
+    if top_score.dim() != 2 or top_score.shape != top_label.shape or top_score.dtype != torch.float32 \
+            or top_label.dtype != torch.int32 or not top_score.is_contiguous() or not top_label.is_contiguous():
+        raise ValueError("label_runs: top_score f32 and top_label int32 are contiguous [N, k]")
+    N, stride = top_score.shape
+    if v_off.dtype != torch.int32 or v_off.dim() != 1 or v_off.numel() < 2 or not v_off.is_contiguous():
+        raise ValueError("label_runs: v_off is int32 [n_videos + 1], contiguous")
+    nv, dev = v_off.numel() - 1, top_score.device
+    threshold, min_len, cap = float(threshold), int(min_len), N if cap is None else int(cap)
+    if N < 1 or stride < 1 or int(L) < 1 or not 1 <= nv <= N or threshold != threshold or min_len < 1 or cap < 0:
+        raise ValueError("label_runs: N, k, L >= 1, 1 <= n_videos <= N, threshold not NaN, min_len >= 1, cap >= 0")
+    if out is None:
+        out = (torch.empty(1, dtype=torch.int32, device=dev), torch.empty(5, cap, dtype=torch.int32, device=dev),
+               torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(int(L), dtype=torch.int32, device=dev) if label_rows else None)
+    n_runs, runs, peak, counts = out
+    if n_runs.dtype != torch.int32 or n_runs.numel() < 1 or runs.dtype != torch.int32 or runs.shape != (5, cap) or not runs.is_contiguous() \
+            or peak.dtype != torch.float32 or peak.shape != (cap,) or not peak.is_contiguous():
+        raise ValueError("label_runs: out is (n_runs int32 [1], runs int32 [5, cap], peak_score f32 [cap], label_rows int32 [L] or None)")
+    if counts is not None and (counts.dtype != torch.int32 or counts.shape != (int(L),) or not counts.is_contiguous()):
+        raise ValueError("label_runs: label_rows is int32 [L], contiguous")
+    lib = _lib.lib()
+    need = lib.tan_label_runs_ws_bytes(N)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws.dtype != torch.uint8 or ws.numel() < need:
+        raise ValueError("label_runs: ws is uint8 of at least label_runs_ws_bytes(N) bytes")
+    if cap > 0:
+        _ptr(runs)
+        col = [C.c_void_p(runs.data_ptr() + 4 * cap * j) for j in range(5)] + [_f32(peak)]
+    else:
+        col = [_ptr(n_runs)] * 6                   # an empty tensor has no address, and with cap == 0 no run is written
+    _lib.check(lib.tan_label_runs(_f32(top_score), _ptr(top_label), stride, N, int(L), _ptr(v_off), nv, threshold, min_len, cap,
+                                  _ptr(n_runs), *col, _ptr(counts), _ptr(ws), _stream()), "tan_label_runs")
+    return n_runs, runs, peak, counts
+
+
 def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scale=None, v_scale=None, out=None):
     """(start, end) int32 [Q, k]: for every hit of `rank_topk_video`'s lists, the contiguous run of index rows around top_row,
     inside the hit's video, whose score is >= top_score - width -- global rows, inclusive (tan_moment_extent / _e4m3; the exact

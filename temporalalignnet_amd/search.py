@@ -34,6 +34,10 @@ sentence is ranked against all of it:
     time windows -- that `search`, `search_moments` and `search_rerank` take as `restrict=`.  The sweep walks only the 64-row tiles
     that hold an admitted row (`tan_row_filter_build`, `tan_rank_topk_filtered`) and returns those rows with the unrestricted
     sweep's scores; a host-resident shard without an admitted row is not copied (`query --only / --exclude / --within`).
+  * `annotate`: the transposed question -- given a fixed vocabulary of step or action descriptions, which label does every second
+    of every video show?  `tan_label_topk` keeps a tile of index rows resident and streams the LABEL matrix past it, so every row's
+    k best labels come out of one launch without scratch; `Annotation.segments` turns the best labels into (video, start, end,
+    label) runs on the device (`tan_label_runs`) and `Annotation.label_seconds` counts the seconds of every label (`annotate`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -43,6 +47,8 @@ sentence is ranked against all of it:
     python -m temporalalignnet_amd.search query ... --index I0.npz --shard I1.npz --shard I2.npz [--host-resident] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --only VID --only-file vids.txt --exclude VID --within VID:30-90 "crack two eggs" ...
     python -m temporalalignnet_amd.search merge --out I.npz I0.npz I1.npz ...
+    python -m temporalalignnet_amd.search annotate --checkpoint C --vocab s3d_dict.npy --index I.npz --labels steps.txt [-k K]
+        [--threshold X] [--min-len M] [--per-second] --out segments.csv
 """
 from __future__ import annotations
 
@@ -353,6 +359,7 @@ class ShardedIndex:
     `search`, `search_moments` and `search_sequences` return for it exactly what they return for `VideoIndex.concat(shards)` --
     every shard is swept on its own and the per-shard lists are folded on the device by `tan_topk_fold`.  Equal vid
     strings in two shards are two videos, as inside one index.  Every shard holds fewer than 2^31 rows; their total may exceed it.
+    `annotate` takes one too (one `tan_label_topk` per shard); its `Annotation` needs fewer than 2^31 rows in all for `segments`.
       vids                      every shard's, in shard order
       v_off [n_videos + 1]      int64, global: each video's first row
       row_base / video_base     int64 [S + 1]: the rows / videos before shard s; the last entry is the total
@@ -863,10 +870,128 @@ def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, 
     return hits
 
 
+class Annotation:
+    """What `annotate` returns: the k best labels of every second of an index.
+      label / score   int32 / f32 [N, k] on the index's device, rows in the index's order (a `ShardedIndex`: shard after shard);
+                      row n holds its k best labels by descending score, equal scores by ascending label number
+      labels          the label texts; label[n, j] numbers them
+      v_off / vids    the index's: int64 [n_videos + 1], each video's first row, and the videos' names
+    `segments` and `label_seconds` read column 0 only: the best label of every second."""
+
+    def __init__(self, label, score, labels, v_off, vids):
+        self.label, self.score, self.labels = label, score, list(labels)
+        self.v_off, self.vids = np.asarray(v_off, dtype=np.int64), list(vids)
+        self._v_off_dev = None
+
+    def __len__(self):
+        return int(self.label.shape[0])
+
+    @property
+    def k(self):
+        return int(self.label.shape[1])
+
+    def _v_off_device(self):
+        if self._v_off_dev is None:
+            self._v_off_dev = torch.from_numpy(self.v_off.astype(np.int32)).to(self.label.device)
+        return self._v_off_dev
+
+    def _check(self, threshold, min_len=1):
+        if threshold != threshold:
+            raise ValueError("Annotation: threshold must not be NaN")
+        if int(min_len) < 1:
+            raise ValueError("Annotation: min_len must be >= 1")
+        if len(self) >= 2 ** 31:
+            raise ValueError("Annotation: 2^31 rows or more; annotate the shards one by one")
+
+    def runs_to_segments(self, runs, peak_score):
+        """`ops.label_runs`' kept runs on the host (runs int [5, n]: ops.RUN_FIELDS, global rows; peak_score [n]) ->
+        [(vid, start_second, end_second, label_text, peak_second, peak_score)]"""
+        video, start, end, label, peak_row = (np.asarray(c, dtype=np.int64) for c in runs)
+        first = self.v_off[video]
+        return [(self.vids[video[i]], int(start[i] - first[i]), int(end[i] - first[i]), self.labels[label[i]],
+                 int(peak_row[i] - first[i]), float(peak_score[i])) for i in range(len(video))]
+
+    def segments(self, threshold, min_len=1):
+        """[(vid, start_second, end_second, label_text, peak_second, peak_score)] in index order: the maximal runs of seconds of one
+        video whose best label is the same and scores >= threshold (a second below it, or with a NaN score, is background), at
+        least min_len seconds long; seconds are the video's own, inclusive; the peak is the run's largest score and the first
+        second that attains it.  Neighbouring runs are not bridged.  One `tan_label_runs` launch and one read-back."""
+        self._check(threshold, min_len)
+        cap = max(len(self) // int(min_len), 1)                        # a kept run holds at least min_len rows
+        n_runs, runs, peak, _ = ops.label_runs(self.score, self.label, len(self.labels), self._v_off_device(), threshold, min_len, cap=cap)
+        back = torch.cat((n_runs[:1], runs.reshape(-1), peak.view(torch.int32))).cpu().numpy()
+        n = int(back[0])
+        return self.runs_to_segments(back[1:1 + 5 * cap].reshape(5, cap)[:, :n], back[1 + 5 * cap:].view(np.float32)[:n])
+
+    def label_seconds(self, threshold):
+        """{label_text: seconds}: how many seconds of the corpus show each label as their best one with a score >= threshold
+        (labels nobody shows included, equal texts added up).  One `tan_label_runs` launch and one read-back."""
+        self._check(threshold)
+        counts = ops.label_runs(self.score, self.label, len(self.labels), self._v_off_device(), threshold, 1, cap=0, label_rows=True)[3]
+        out = {}
+        for text, c in zip(self.labels, counts.cpu().numpy()):
+            out[text] = out.get(text, 0) + int(c)
+        return out
+
+
+@torch.no_grad()
+def annotate(index, model, embed_text, labels, k=1):
+    """The transposed search: for a fixed vocabulary `labels` (step descriptions, tags), the k best labels of EVERY second of the
+    index -- an `Annotation`.  score = <index row, unit label feature>, `search`'s score; the label features come from
+    `query_features`, so an e4m3 index gets e4m3 labels.  One `tan_label_topk` launch: every index row is read once, the label
+    matrix is streamed per 128 rows, and no [N, L] score matrix is stored.  1 <= k <= min(32, len(labels)).
+    `index`: a `VideoIndex`, or a `ShardedIndex` -- one launch per shard into the shard's slice of the outputs (host-resident
+    shards stream through the two slots), exactly what `VideoIndex.concat` of the shards gives.  The outputs stay on the device:
+    k * 8 bytes per row.  There is no `restrict=` here."""
+    labels = list(labels)
+    if not labels:
+        raise ValueError("annotate: no labels")
+    k = int(k)
+    if not 1 <= k <= min(32, len(labels)):
+        raise ValueError("annotate: k must lie in [1, min(32, len(labels))]")
+    N, dev = len(index), index.device
+    tl = query_features(index, model, embed_text, labels)
+    score = torch.empty(N, k, dtype=torch.float32, device=dev)
+    label = torch.empty(N, k, dtype=torch.int32, device=dev)
+    if isinstance(index, ShardedIndex):
+        for s, feat, scale, _ in index.shard_views():
+            out = tuple(t[int(index.row_base[s]):int(index.row_base[s + 1])] for t in (score, label))
+            if index.e4m3:
+                ops.label_topk_e4m3(*tl, feat, scale, k, out=out)
+            else:
+                ops.label_topk(tl, feat, k, out=out)
+    elif index.e4m3:
+        ops.label_topk_e4m3(*tl, index.feat, index.scale, k, out=(score, label))
+    else:
+        ops.label_topk(tl, index.feat, k, out=(score, label))
+    return Annotation(label, score, labels, index.v_off, index.vids)
+
+
+def write_segments_csv(f, segments):
+    """`Annotation.segments`' tuples -> csv rows vid,start,end,label,peak,score under that header"""
+    import csv
+    w = csv.writer(f, lineterminator="\n")
+    w.writerow(("vid", "start", "end", "label", "peak", "score"))
+    for vid, start, end, label, peak, score in segments:
+        w.writerow((vid, start, end, label, peak, f"{score:.6f}"))
+
+
+def write_per_second_csv(f, ann):
+    """An `Annotation` -> csv rows vid,second,label,score under that header: k rows per second, best label first"""
+    import csv
+    w = csv.writer(f, lineterminator="\n")
+    w.writerow(("vid", "second", "label", "score"))
+    label, score = ann.label.cpu().numpy(), ann.score.cpu().numpy()
+    for v, vid in enumerate(ann.vids):
+        for n in range(int(ann.v_off[v]), int(ann.v_off[v + 1])):
+            for j in range(label.shape[1]):
+                w.writerow((vid, n - int(ann.v_off[v]), ann.labels[label[n, j]], f"{score[n, j]:.6f}"))
+
+
 def _parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("index", "query"):
+    for name in ("index", "query", "annotate"):
         p = sub.add_parser(name)
         p.add_argument("--checkpoint", required=True)
         p.add_argument("--vocab", required=True, help="s3d_dict.npy (the Word2Vec vocabulary)")
@@ -883,8 +1008,22 @@ def _parser():
                    help="also keep video_pre_proj of every second (what `query --rerank` needs): + 1 KiB per second in bf16")
     p.add_argument("--worker-id", type=int, default=0)
     p.add_argument("--num-workers", type=int, default=1)
+    for name in ("query", "annotate"):
+        p = sub.choices[name]
+        p.add_argument("--index", required=True)
+        p.add_argument("--shard", action="append", default=None, metavar="PATH",
+                       help="a further index file searched together with --index, in the order given (repeatable)")
+        p.add_argument("--host-resident", action="store_true",
+                       help="keep the rows in pinned host memory and stream them through the card: for an index larger than the card")
+    p = sub.choices["annotate"]
+    p.add_argument("--labels", required=True, metavar="FILE", help="the vocabulary: one label text per line, blank lines skipped")
+    p.add_argument("-k", type=int, default=1, help="labels kept per second, 1 to 32 (segments use the best one)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="a second whose best score is below this is background (default: none is)")
+    p.add_argument("--min-len", type=int, default=None, help="drop segments shorter than this many seconds (default 1)")
+    p.add_argument("--per-second", action="store_true", help="write vid,second,label,score for the k labels of every second instead")
+    p.add_argument("--out", required=True, metavar="CSV", help="vid,start,end,label,peak,score: one row per segment")
     p = sub.choices["query"]
-    p.add_argument("--index", required=True)
     p.add_argument("-k", type=int, default=10)
     p.add_argument("--moments", action="store_true",
                    help="the k best distinct videos, each as `sentence vid start end second score` (seconds of the video)")
@@ -897,10 +1036,6 @@ def _parser():
                    help="two stages: the --pool best distinct videos of the dual sweep rescored by the joint encoder, the k best as "
                         "`sentence vid second score confidence alignability dual_second dual_score` (needs index --keep-stem)")
     p.add_argument("--pool", type=int, default=None, help="with --rerank: candidates per sentence, 1 to 32 (default 32)")
-    p.add_argument("--shard", action="append", default=None, metavar="PATH",
-                   help="a further index file searched together with --index, in the order given (repeatable)")
-    p.add_argument("--host-resident", action="store_true",
-                   help="keep the rows in pinned host memory and stream them through the card: for an index larger than the card")
     p.add_argument("--only", action="append", default=None, metavar="VID", help="search only this video (repeatable)")
     p.add_argument("--only-file", default=None, metavar="PATH", help="search only the videos listed here, one vid per line")
     p.add_argument("--exclude", action="append", default=None, metavar="VID", help="leave this video out (repeatable)")
@@ -935,6 +1070,15 @@ def parse_args(argv=None):
         ap.error("--width must be >= 0")
     if a.cmd == "index" and not 0 <= a.worker_id < a.num_workers:
         ap.error("--worker-id must lie in [0, --num-workers)")
+    if a.cmd == "annotate":
+        if not 1 <= a.k <= 32:
+            ap.error("-k must lie in [1, 32]")
+        if a.per_second and (a.threshold is not None or a.min_len is not None):
+            ap.error("--per-second does not go with --threshold / --min-len")
+        if a.threshold is not None and a.threshold != a.threshold:
+            ap.error("--threshold must not be NaN")
+        if a.min_len is not None and a.min_len < 1:
+            ap.error("--min-len must be >= 1")
     if a.cmd == "query":
         filtered = any(x is not None for x in (a.only, a.only_file, a.exclude, a.exclude_file, a.within))
         if filtered and a.sequence:
@@ -994,6 +1138,15 @@ def main(argv=None):
         idx = ShardedIndex.load([a.index] + (a.shard or []), resident="host" if a.host_resident else "device")
     else:
         idx = VideoIndex.load(a.index)
+    if a.cmd == "annotate":
+        ann = annotate(idx, model, embed, _read_vids(a.labels), a.k)
+        with open(a.out, "w", newline="") as f:
+            if a.per_second:
+                write_per_second_csv(f, ann)
+            else:
+                write_segments_csv(f, ann.segments(float("-inf") if a.threshold is None else a.threshold, a.min_len or 1))
+        print(f"{a.out}: {len(ann)} seconds of {len(ann.vids)} videos against {len(ann.labels)} labels", file=sys.stderr)
+        return 0
     if a.sequence:
         for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
             print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))

@@ -1064,108 +1064,56 @@ inline int n_splits(long Q, long N, int splits, long* tiles_per_split) {
     return (int)((n_tiles + *tiles_per_split - 1) / *tiles_per_split);
 }
 
-template <typename T>
-int rank_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair, int k, int splits, int* higher, int* ties,
-                float* top_s, int* top_n, void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
+// a sweep's scratch: VIDEO: tvid [tiles rounded up to 2] int2, otherwise dscore [Q rounded up to 4] f32; then the splits' lists
+// (score, row[, video]), 4 bytes per entry each
+inline long sweep_ws_head(bool video, long Q, long N) { return video ? (n_index_tiles(N) + 1) / 2 * 2 * 8 : (Q + 3) / 4 * 4 * 4; }
+
+// The four sweeps (tan_rank_topk / _video / _filtered / _video_filtered).  `pair`: FILTER: the filter image, which rides in the
+// kernel's `pair` argument; otherwise the paired rows or nullptr (VIDEO: always nullptr).  The pair launch belongs to the plain
+// sweep alone; higher / ties are its, v_off / n_videos / top_v the VIDEO sweeps'.  The grid is sized from (Q, N, splits) whatever the
+// filter lists.
+template <typename T, bool VIDEO, bool FILTER>
+int sweep_launch(const void* Tq, const void* Vn, long Q, long N, const int* pair, const int* v_off, int n_videos, int k, int splits,
+                 int* higher, int* ties, float* top_s, int* top_n, int* top_v, void* ws, hipStream_t st, const float* q_scale,
+                 const float* v_scale) {
     const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
     long tps;
     const int ns = n_splits(Q, N, splits, &tps);
-    float* dscore = (float*)ws;
-    float* part_s = dscore + (Q + 3) / 4 * 4;
+    float* dscore = VIDEO || FILTER ? nullptr : (float*)ws;
+    int2* tvid = VIDEO ? (int2*)ws : nullptr;
+    float* part_s = (float*)((char*)ws + sweep_ws_head(VIDEO, Q, N));
     int* part_n = (int*)(part_s + (long)ns * Q * k);
-    if (pair) {
-        hipLaunchKernelGGL((rank_kernel<T, true>), dim3((unsigned)q_tiles), dim3(256), tile_bytes<T>(), st, (const T*)Tq, (const T*)Vn, Q, N,
-                           pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr, q_scale, v_scale, (const int2*)nullptr,
-                           (const int*)nullptr, (int*)nullptr);
+    int* part_v = VIDEO ? part_n + (long)ns * Q * k : nullptr;
+    if constexpr (VIDEO && FILTER) {
+        hipLaunchKernelGGL(tile_video_listed_kernel, dim3(cdiv(n_tiles, 256)), dim3(256), 0, st, v_off, n_videos, N, n_tiles, pair, tvid);
         TAN_LAUNCH_CHECK();
+    } else if constexpr (VIDEO) {
+        hipLaunchKernelGGL(tile_video_kernel, dim3(cdiv(n_tiles, 256)), dim3(256), 0, st, v_off, n_videos, N, n_tiles, tvid);
+        TAN_LAUNCH_CHECK();
+    } else if constexpr (!FILTER) {
+        if (pair) {
+            hipLaunchKernelGGL((rank_kernel<T, true>), dim3((unsigned)q_tiles), dim3(256), tile_bytes<T>(), st, (const T*)Tq, (const T*)Vn,
+                               Q, N, pair, 0, 0L, 0L, dscore, higher, ties, (float*)nullptr, (int*)nullptr, q_scale, v_scale,
+                               (const int2*)nullptr, (const int*)nullptr, (int*)nullptr);
+            TAN_LAUNCH_CHECK();
+        }
     }
-    static std::atomic<unsigned long long> lds_done{0};
-    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false>, sweep_lds<T>(), lds_done);
+    static std::atomic<unsigned long long> lds_done{0};            // one per instantiation
+    constexpr int lds = sweep_lds<T, VIDEO>();
+    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, VIDEO, FILTER>, lds, lds_done);
     if (attr != hipSuccess) return (int)attr;
-    hipLaunchKernelGGL((rank_kernel<T, false>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), sweep_lds<T>(), st, (const T*)Tq,
+    hipLaunchKernelGGL((rank_kernel<T, false, VIDEO, FILTER>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), lds, st, (const T*)Tq,
                        (const T*)Vn, Q, N, pair, k, tps, n_tiles, dscore, higher, ties, part_s, part_n, q_scale, v_scale,
-                       (const int2*)nullptr, (const int*)nullptr, (int*)nullptr);
+                       (const int2*)tvid, v_off, part_v);
     TAN_LAUNCH_CHECK();
-    if (k > 0) {
+    if constexpr (VIDEO) {
+        hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, Q, k, ns, top_s,
+                           top_n, top_v);
+        TAN_LAUNCH_CHECK();
+    } else if (k > 0) {
         hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, Q, k, ns, top_s, top_n);
         TAN_LAUNCH_CHECK();
     }
-    return 0;
-}
-
-// ws: tvid [tiles rounded up to 2] int2, then the splits' lists (score, row, video)
-template <typename T>
-int video_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_off, int n_videos, int k, int splits, float* top_s,
-                 int* top_n, int* top_v, void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
-    long tps;
-    const int ns = n_splits(Q, N, splits, &tps);
-    const long n_tiles = n_index_tiles(N);
-    int2* tvid = (int2*)ws;
-    float* part_s = (float*)(tvid + (n_tiles + 1) / 2 * 2);
-    int* part_n = (int*)(part_s + (long)ns * Q * k);
-    int* part_v = part_n + (long)ns * Q * k;
-    hipLaunchKernelGGL(tile_video_kernel, dim3(cdiv(n_tiles, 256)), dim3(256), 0, st, v_off, n_videos, N, n_tiles, tvid);
-    TAN_LAUNCH_CHECK();
-    static std::atomic<unsigned long long> lds_done{0};
-    constexpr int lds = sweep_lds<T, true>();
-    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, true>, lds, lds_done);
-    if (attr != hipSuccess) return (int)attr;
-    hipLaunchKernelGGL((rank_kernel<T, false, true>), dim3((unsigned)((Q + BQ - 1) / BQ), (unsigned)ns), dim3(256), lds, st,
-                       (const T*)Tq, (const T*)Vn, Q, N, (const int*)nullptr, k, tps, n_tiles, (float*)nullptr, (int*)nullptr,
-                       (int*)nullptr, part_s, part_n, q_scale, v_scale, (const int2*)tvid, v_off, part_v);
-    TAN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, Q, k, ns, top_s,
-                       top_n, top_v);
-    TAN_LAUNCH_CHECK();
-    return 0;
-}
-
-// the filtered sweeps: rank_launch / video_launch without the pair launch, the grid sized from (Q, N, splits) as theirs, the filter
-// image in the kernel's `pair` argument.  ws: as the plain launches lay it out.
-template <typename T>
-int rank_filtered_launch(const void* Tq, const void* Vn, long Q, long N, const int* filt, int k, int splits, float* top_s, int* top_n,
-                         void* ws, hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
-    const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
-    long tps;
-    const int ns = n_splits(Q, N, splits, &tps);
-    float* part_s = (float*)ws + (Q + 3) / 4 * 4;
-    int* part_n = (int*)(part_s + (long)ns * Q * k);
-    static std::atomic<unsigned long long> lds_done{0};
-    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, false, true>, sweep_lds<T>(), lds_done);
-    if (attr != hipSuccess) return (int)attr;
-    hipLaunchKernelGGL((rank_kernel<T, false, false, true>), dim3((unsigned)q_tiles, (unsigned)ns), dim3(256), sweep_lds<T>(), st,
-                       (const T*)Tq, (const T*)Vn, Q, N, filt, k, tps, n_tiles, (float*)nullptr, (int*)nullptr, (int*)nullptr, part_s,
-                       part_n, q_scale, v_scale, (const int2*)nullptr, (const int*)nullptr, (int*)nullptr);
-    TAN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, Q, k, ns, top_s, top_n);
-    TAN_LAUNCH_CHECK();
-    return 0;
-}
-
-template <typename T>
-int video_filtered_launch(const void* Tq, const void* Vn, long Q, long N, const int* v_off, int n_videos, const int* filt, int k,
-                          int splits, float* top_s, int* top_n, int* top_v, void* ws, hipStream_t st, const float* q_scale = nullptr,
-                          const float* v_scale = nullptr) {
-    long tps;
-    const int ns = n_splits(Q, N, splits, &tps);
-    const long n_tiles = n_index_tiles(N);
-    int2* tvid = (int2*)ws;
-    float* part_s = (float*)(tvid + (n_tiles + 1) / 2 * 2);
-    int* part_n = (int*)(part_s + (long)ns * Q * k);
-    int* part_v = part_n + (long)ns * Q * k;
-    hipLaunchKernelGGL(tile_video_listed_kernel, dim3(cdiv(n_tiles, 256)), dim3(256), 0, st, v_off, n_videos, N, n_tiles, filt, tvid);
-    TAN_LAUNCH_CHECK();
-    static std::atomic<unsigned long long> lds_done{0};
-    constexpr int lds = sweep_lds<T, true>();
-    const hipError_t attr = ensure_dyn_lds((const void*)rank_kernel<T, false, true, true>, lds, lds_done);
-    if (attr != hipSuccess) return (int)attr;
-    hipLaunchKernelGGL((rank_kernel<T, false, true, true>), dim3((unsigned)((Q + BQ - 1) / BQ), (unsigned)ns), dim3(256), lds, st,
-                       (const T*)Tq, (const T*)Vn, Q, N, filt, k, tps, n_tiles, (float*)nullptr, (int*)nullptr, (int*)nullptr, part_s,
-                       part_n, q_scale, v_scale, (const int2*)tvid, v_off, part_v);
-    TAN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(Q, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, Q, k, ns, top_s,
-                       top_n, top_v);
-    TAN_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1533,63 +1481,86 @@ __global__ void __launch_bounds__(256) runs_emit_kernel(const float* __restrict_
 
 using namespace tal;
 
-extern "C" long tan_rank_topk_ws_bytes(long Q, long N, int k) {
-    if (Q < 1 || N < 1 || N >= (1L << 31) || k < 0 || k > KMAX) return TAN_ERR_BAD_ARG;
-    const long ns = n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS;
-    return ((Q + 3) / 4 * 4) * 4 + ns * Q * k * 8;
+// Every plain / _e4m3 pair of entry points shares ONE body, which takes the row format as `fmt`: the plain twin passes its `dtype`
+// and no scales, the _e4m3 twin FMT_E4M3 and its scales.  rows_ok is the whole check of the format and the two row matrices;
+// by_format calls `launch` with a Rows<T> naming the element type.
+namespace {
+constexpr int FMT_E4M3 = -1;                 // not a TAN_* dtype: a plain entry point handed it has no scales and is refused
+template <typename T> struct Rows { typedef T type; };
+
+inline bool rows_ok(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale) {
+    return Tq && Vn && (uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 &&
+           (fmt == FMT_E4M3 ? q_scale && v_scale : fmt == TAN_F32 || fmt == TAN_BF16);
 }
 
-extern "C" int tan_rank_topk(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* pair, int k, int splits,
-                             int* higher, int* ties, float* top_score, int* top_row, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && Vn && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
+template <typename F> int by_format(int fmt, F launch) {
+    return fmt == TAN_BF16 ? launch(Rows<bf16_t>()) : fmt == TAN_F32 ? launch(Rows<float>()) : launch(Rows<e4m3_t>());
+}
+
+inline long max_splits(long N) { return n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS; }
+
+}  // namespace
+
+extern "C" long tan_rank_topk_ws_bytes(long Q, long N, int k) {
+    if (Q < 1 || N < 1 || N >= (1L << 31) || k < 0 || k > KMAX) return TAN_ERR_BAD_ARG;
+    return sweep_ws_head(false, Q, N) + max_splits(N) * Q * k * 8;
+}
+
+static int rank_topk(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+              const int* pair, int k, int splits, int* higher, int* ties, float* top_score, int* top_row, void* ws, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && ws && (uintptr_t)ws % 16 == 0);
     TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 0 && k <= KMAX && k <= N);
     TAN_REQUIRE(splits >= 0 && (pair || k > 0));
     TAN_REQUIRE(!pair || (higher && ties));
     TAN_REQUIRE(k == 0 || (top_score && top_row));
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16 ? rank_launch<bf16_t>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, st)
-                             : rank_launch<float>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, st);
+    return by_format(fmt, [&](auto r) {
+        return sweep_launch<typename decltype(r)::type, false, false>(Tq, Vn, Q, N, pair, nullptr, 0, k, splits, higher, ties, top_score,
+                                                                      top_row, nullptr, ws, (hipStream_t)stream, q_scale, v_scale);
+    });
+}
+
+extern "C" int tan_rank_topk(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* pair, int k, int splits,
+                             int* higher, int* ties, float* top_score, int* top_row, void* ws, void* stream) {
+    return rank_topk(dtype, Tq, nullptr, Vn, nullptr, Q, N, C, pair, k, splits, higher, ties, top_score, top_row, ws, stream);
 }
 
 extern "C" int tan_rank_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
                                   const int* pair, int k, int splits, int* higher, int* ties, float* top_score, int* top_row, void* ws,
                                   void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && ws);
-    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 0 && k <= KMAX && k <= N);
-    TAN_REQUIRE(splits >= 0 && (pair || k > 0));
-    TAN_REQUIRE(!pair || (higher && ties));
-    TAN_REQUIRE(k == 0 || (top_score && top_row));
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
-    return rank_launch<e4m3_t>(Tq, Vn, Q, N, pair, k, splits, higher, ties, top_score, top_row, ws, (hipStream_t)stream, q_scale,
-                               v_scale);
+    return rank_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Q, N, C, pair, k, splits, higher, ties, top_score, top_row, ws, stream);
 }
 
 extern "C" long tan_rank_topk_video_ws_bytes(long Q, long N, long n_videos, int k) {
     if (!video_sizes_ok(Q, N, RC, n_videos, k)) return TAN_ERR_BAD_ARG;
-    const long ns = n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS;
-    return ((n_index_tiles(N) + 1) / 2 * 2) * 8 + ns * Q * k * 12;
+    return sweep_ws_head(true, Q, N) + max_splits(N) * Q * k * 12;
+}
+
+// FILTER = false: tan_rank_topk_video, filt is nullptr; true: tan_rank_topk_video_filtered
+template <bool FILTER>
+static int rank_topk_video(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                    const int* v_off, long n_videos, const void* filt, int k, int splits, float* top_score, int* top_row,
+                    int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && v_off && top_score && top_row && top_video && ws && (uintptr_t)ws % 16 == 0);
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
+    TAN_REQUIRE(!FILTER || (filt && (uintptr_t)filt % 16 == 0));
+    return by_format(fmt, [&](auto r) {
+        return sweep_launch<typename decltype(r)::type, true, FILTER>(Tq, Vn, Q, N, (const int*)filt, v_off, (int)n_videos, k, splits,
+                                                                      nullptr, nullptr, top_score, top_row, top_video, ws,
+                                                                      (hipStream_t)stream, q_scale, v_scale);
+    });
 }
 
 extern "C" int tan_rank_topk_video(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos,
                                    int k, int splits, float* top_score, int* top_row, int* top_video, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && Vn && v_off && top_score && top_row && top_video && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16
-               ? video_launch<bf16_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, st)
-               : video_launch<float>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, st);
+    return rank_topk_video<false>(dtype, Tq, nullptr, Vn, nullptr, Q, N, C, v_off, n_videos, nullptr, k, splits, top_score, top_row,
+                                  top_video, ws, stream);
 }
 
 extern "C" int tan_rank_topk_video_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
                                         const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_row,
                                         int* top_video, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && v_off && top_score && top_row && top_video && ws);
-    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
-    return video_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, splits, top_score, top_row, top_video, ws, (hipStream_t)stream,
-                                q_scale, v_scale);
+    return rank_topk_video<false>(FMT_E4M3, Tq, q_scale, Vn, v_scale, Q, N, C, v_off, n_videos, nullptr, k, splits, top_score, top_row,
+                                  top_video, ws, stream);
 }
 
 extern "C" long tan_row_filter_bytes(long N) {
@@ -1611,136 +1582,138 @@ extern "C" int tan_row_filter_build(const int* spans, long n_spans, long N, void
     return 0;
 }
 
+static int rank_topk_filtered(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                       const void* filt, int k, int splits, float* top_score, int* top_row, void* ws, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && filt && top_score && top_row && ws);
+    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= N && splits >= 0);
+    TAN_REQUIRE((uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
+    return by_format(fmt, [&](auto r) {
+        return sweep_launch<typename decltype(r)::type, false, true>(Tq, Vn, Q, N, (const int*)filt, nullptr, 0, k, splits, nullptr,
+                                                                     nullptr, top_score, top_row, nullptr, ws, (hipStream_t)stream,
+                                                                     q_scale, v_scale);
+    });
+}
+
 extern "C" int tan_rank_topk_filtered(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const void* filt, int k,
                                       int splits, float* top_score, int* top_row, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && Vn && filt && top_score && top_row && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= N && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16 ? rank_filtered_launch<bf16_t>(Tq, Vn, Q, N, (const int*)filt, k, splits, top_score, top_row, ws, st)
-                             : rank_filtered_launch<float>(Tq, Vn, Q, N, (const int*)filt, k, splits, top_score, top_row, ws, st);
+    return rank_topk_filtered(dtype, Tq, nullptr, Vn, nullptr, Q, N, C, filt, k, splits, top_score, top_row, ws, stream);
 }
 
 extern "C" int tan_rank_topk_filtered_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N,
                                            int C, const void* filt, int k, int splits, float* top_score, int* top_row, void* ws,
                                            void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && filt && top_score && top_row && ws);
-    TAN_REQUIRE(C == RC && Q >= 1 && Q < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= N && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
-    return rank_filtered_launch<e4m3_t>(Tq, Vn, Q, N, (const int*)filt, k, splits, top_score, top_row, ws, (hipStream_t)stream, q_scale,
-                                        v_scale);
+    return rank_topk_filtered(FMT_E4M3, Tq, q_scale, Vn, v_scale, Q, N, C, filt, k, splits, top_score, top_row, ws, stream);
 }
 
 extern "C" int tan_rank_topk_video_filtered(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off,
                                             long n_videos, const void* filt, int k, int splits, float* top_score, int* top_row,
                                             int* top_video, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && Vn && v_off && filt && top_score && top_row && top_video && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16 ? video_filtered_launch<bf16_t>(Tq, Vn, Q, N, v_off, (int)n_videos, (const int*)filt, k, splits, top_score,
-                                                             top_row, top_video, ws, st)
-                             : video_filtered_launch<float>(Tq, Vn, Q, N, v_off, (int)n_videos, (const int*)filt, k, splits, top_score,
-                                                            top_row, top_video, ws, st);
+    return rank_topk_video<true>(dtype, Tq, nullptr, Vn, nullptr, Q, N, C, v_off, n_videos, filt, k, splits, top_score, top_row,
+                                 top_video, ws, stream);
 }
 
 extern "C" int tan_rank_topk_video_filtered_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q,
                                                  long N, int C, const int* v_off, long n_videos, const void* filt, int k, int splits,
                                                  float* top_score, int* top_row, int* top_video, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && v_off && filt && top_score && top_row && top_video && ws);
-    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0 && (uintptr_t)filt % 16 == 0);
-    return video_filtered_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, (const int*)filt, k, splits, top_score, top_row, top_video,
-                                         ws, (hipStream_t)stream, q_scale, v_scale);
+    return rank_topk_video<true>(FMT_E4M3, Tq, q_scale, Vn, v_scale, Q, N, C, v_off, n_videos, filt, k, splits, top_score, top_row,
+                                 top_video, ws, stream);
+}
+
+static int moment_extent(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
+                  const int* v_off, long n_videos, int k, const float* top_score, const int* top_row, const int* top_video, float width,
+                  int* start, int* end, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && v_off && top_score && top_row && top_video && start && end);
+    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && width >= 0.0f);
+    return by_format(fmt, [&](auto r) {
+        return extent_launch<typename decltype(r)::type>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width,
+                                                         start, end, (hipStream_t)stream, q_scale, v_scale);
+    });
 }
 
 extern "C" int tan_moment_extent(const void* Tq, const void* Vn, int dtype, long Q, long N, int C, const int* v_off, long n_videos, int k,
                                  const float* top_score, const int* top_row, const int* top_video, float width, int* start, int* end,
                                  void* stream) {
-    TAN_REQUIRE(Tq && Vn && v_off && top_score && top_row && top_video && start && end && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && width >= 0.0f);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16
-               ? extent_launch<bf16_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end, st)
-               : extent_launch<float>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end, st);
+    return moment_extent(dtype, Tq, nullptr, Vn, nullptr, Q, N, C, v_off, n_videos, k, top_score, top_row, top_video, width, start, end,
+                         stream);
 }
 
 extern "C" int tan_moment_extent_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
                                       const int* v_off, long n_videos, int k, const float* top_score, const int* top_row,
                                       const int* top_video, float width, int* start, int* end, void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && v_off && top_score && top_row && top_video && start && end);
-    TAN_REQUIRE(video_sizes_ok(Q, N, C, n_videos, k) && width >= 0.0f);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0);
-    return extent_launch<e4m3_t>(Tq, Vn, Q, N, v_off, (int)n_videos, k, top_score, top_row, top_video, width, start, end,
-                                 (hipStream_t)stream, q_scale, v_scale);
+    return moment_extent(FMT_E4M3, Tq, q_scale, Vn, v_scale, Q, N, C, v_off, n_videos, k, top_score, top_row, top_video, width, start,
+                         end, stream);
 }
 
 extern "C" long tan_sequence_topk_ws_bytes(long n_seq, long N, int k) {
     if (n_seq < 1 || n_seq >= (1L << 29) || N < 1 || N >= (1L << 31) || k < 1 || k > KMAX) return TAN_ERR_BAD_ARG;
-    const long ns = n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS;
-    return ns * n_seq * k * 8;
+    return max_splits(N) * n_seq * k * 8;
+}
+
+static int sequence_topk(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                  const int* s_off, long n_seq, const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_video,
+                  void* ws, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && s_off && v_off && top_score && top_video && ws && (uintptr_t)ws % 16 == 0);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0);
+    return by_format(fmt, [&](auto r) {
+        return seq_topk_launch<typename decltype(r)::type>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score,
+                                                           top_video, ws, (hipStream_t)stream, q_scale, v_scale);
+    });
 }
 
 extern "C" int tan_sequence_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* s_off, long n_seq,
                                  const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_video, void* ws,
                                  void* stream) {
-    TAN_REQUIRE(Tq && Vn && s_off && v_off && top_score && top_video && ws && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16
-               ? seq_topk_launch<bf16_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score, top_video, ws, st)
-               : seq_topk_launch<float>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score, top_video, ws, st);
+    return sequence_topk(dtype, Tq, nullptr, Vn, nullptr, Qt, N, C, s_off, n_seq, v_off, n_videos, k, splits, top_score, top_video, ws,
+                         stream);
 }
 
 extern "C" int tan_sequence_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
                                       const int* s_off, long n_seq, const int* v_off, long n_videos, int k, int splits,
                                       float* top_score, int* top_video, void* ws, void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && s_off && v_off && top_score && top_video && ws);
-    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)ws % 16 == 0);
-    return seq_topk_launch<e4m3_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, k, splits, top_score, top_video, ws,
-                                   (hipStream_t)stream, q_scale, v_scale);
+    return sequence_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, s_off, n_seq, v_off, n_videos, k, splits, top_score, top_video,
+                         ws, stream);
+}
+
+static int sequence_scores(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                    const int* s_off, long n_seq, const int* v_off, long n_videos, const int* hits, const long* x_off, long P, float* x,
+                    long n_x, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && s_off && v_off && hits && x_off && x && (uintptr_t)x_off % 8 == 0);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && P >= 1 && P < (1L << 31) && n_x >= 1);
+    return by_format(fmt, [&](auto r) {
+        return seq_scores_launch<typename decltype(r)::type>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x,
+                                                             (hipStream_t)stream, q_scale, v_scale);
+    });
 }
 
 extern "C" int tan_sequence_scores(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* s_off, long n_seq,
                                    const int* v_off, long n_videos, const int* hits, const long* x_off, long P, float* x, long n_x,
                                    void* stream) {
-    TAN_REQUIRE(Tq && Vn && s_off && v_off && hits && x_off && x && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && P >= 1 && P < (1L << 31) && n_x >= 1);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)x_off % 8 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16 ? seq_scores_launch<bf16_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, st)
-                             : seq_scores_launch<float>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, st);
+    return sequence_scores(dtype, Tq, nullptr, Vn, nullptr, Qt, N, C, s_off, n_seq, v_off, n_videos, hits, x_off, P, x, n_x, stream);
 }
 
 extern "C" int tan_sequence_scores_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N,
                                         int C, const int* s_off, long n_seq, const int* v_off, long n_videos, const int* hits,
                                         const long* x_off, long P, float* x, long n_x, void* stream) {
-    TAN_REQUIRE(Tq && q_scale && Vn && v_scale && s_off && v_off && hits && x_off && x);
-    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_seq, n_videos) && P >= 1 && P < (1L << 31) && n_x >= 1);
-    TAN_REQUIRE((uintptr_t)Tq % 16 == 0 && (uintptr_t)Vn % 16 == 0 && (uintptr_t)x_off % 8 == 0);
-    return seq_scores_launch<e4m3_t>(Tq, Vn, Qt, N, s_off, n_seq, v_off, (int)n_videos, hits, x_off, P, x, n_x, (hipStream_t)stream,
-                                     q_scale, v_scale);
+    return sequence_scores(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, s_off, n_seq, v_off, n_videos, hits, x_off, P, x, n_x, stream);
+}
+
+static int label_topk(int fmt, const void* Tl, const float* l_scale, const void* Vn, const float* v_scale, long L, long N, int C, int k,
+               float* top_score, int* top_label, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tl, l_scale, Vn, v_scale) && top_score && top_label);
+    TAN_REQUIRE(C == RC && L >= 1 && L < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= L);
+    return by_format(fmt, [&](auto r) {
+        return label_launch<typename decltype(r)::type>(Tl, Vn, L, N, k, top_score, top_label, (hipStream_t)stream, l_scale, v_scale);
+    });
 }
 
 extern "C" int tan_label_topk(const void* Tl, const void* Vn, int dtype, long L, long N, int C, int k, float* top_score, int* top_label,
                               void* stream) {
-    TAN_REQUIRE(Tl && Vn && top_score && top_label && (dtype == TAN_F32 || dtype == TAN_BF16));
-    TAN_REQUIRE(C == RC && L >= 1 && L < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= L);
-    TAN_REQUIRE((uintptr_t)Tl % 16 == 0 && (uintptr_t)Vn % 16 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == TAN_BF16 ? label_launch<bf16_t>(Tl, Vn, L, N, k, top_score, top_label, st)
-                             : label_launch<float>(Tl, Vn, L, N, k, top_score, top_label, st);
+    return label_topk(dtype, Tl, nullptr, Vn, nullptr, L, N, C, k, top_score, top_label, stream);
 }
 
 extern "C" int tan_label_topk_e4m3(const void* Tl, const float* l_scale, const void* Vn, const float* v_scale, long L, long N, int C,
                                    int k, float* top_score, int* top_label, void* stream) {
-    TAN_REQUIRE(Tl && l_scale && Vn && v_scale && top_score && top_label);
-    TAN_REQUIRE(C == RC && L >= 1 && L < (1L << 31) && N >= 1 && N < (1L << 31) && k >= 1 && k <= KMAX && k <= L);
-    TAN_REQUIRE((uintptr_t)Tl % 16 == 0 && (uintptr_t)Vn % 16 == 0);
-    return label_launch<e4m3_t>(Tl, Vn, L, N, k, top_score, top_label, (hipStream_t)stream, l_scale, v_scale);
+    return label_topk(FMT_E4M3, Tl, l_scale, Vn, v_scale, L, N, C, k, top_score, top_label, stream);
 }
 
 extern "C" long tan_label_runs_ws_bytes(long N) {

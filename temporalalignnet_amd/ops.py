@@ -321,34 +321,67 @@ def rank_topk_ws_bytes(Q, N, k):
     return n
 
 
+def _rows_args(what, tq, vn, q_scale, v_scale):
+    """The one check of a wrapper's row arguments: tq [Q, 512] / vn [N, 512] contiguous and of one dtype; uint8 rows are e4m3 codes
+    and come with their f32 scales q_scale [Q] / v_scale [N], any other rows without.  Returns whether the rows are e4m3."""
+    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype
+    e4m3 = tq.dtype == torch.uint8
+    if (q_scale is not None) != e4m3 or (v_scale is not None) != e4m3:
+        raise TypeError(f"{what}: q_scale / v_scale go with uint8 e4m3 codes, and only with them")
+    if e4m3:
+        assert q_scale.shape == (tq.shape[0],) and v_scale.shape == (vn.shape[0],) and q_scale.is_contiguous() and v_scale.is_contiguous()
+    return e4m3
+
+
+def _call(name, tq, q_scale, vn, v_scale, *tail):
+    """tan_<name>(tq, vn, dtype, *tail, stream) or, with scales, its twin tan_<name>_e4m3(tq, q_scale, vn, v_scale, *tail, stream)"""
+    L = _lib.lib()
+    if q_scale is not None:
+        _lib.check(getattr(L, f"tan_{name}_e4m3")(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), *tail, _stream()), f"tan_{name}_e4m3")
+    else:
+        _lib.check(getattr(L, f"tan_{name}")(_ptr(tq), _ptr(vn), _dt(tq), *tail, _stream()), f"tan_{name}")
+
+
+def _scratch(ws, need, dev):
+    """`ws`, or fresh scratch of `need` bytes (a tan_*_ws_bytes answer); need < 0: invalid sizes, which the entry point itself refuses"""
+    if need >= 0:
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
+    return ws
+
+
+def _lists(n, k, dev, video=False):
+    """fresh top-k outputs: (score f32, row int32[, video int32]), [n, k] each"""
+    return (torch.empty(n, k, dtype=torch.float32, device=dev),) + tuple(torch.empty(n, k, dtype=torch.int32, device=dev)
+                                                                         for _ in range(2 if video else 1))
+
+
+def _rank_topk(what, tq, q_scale, vn, v_scale, pair, k, splits, check_pair, out, ws):
+    _rows_args(what, tq, vn, q_scale, v_scale)
+    Q, N, dev = tq.shape[0], vn.shape[0], tq.device
+    if pair is not None:
+        assert pair.dtype == torch.int32 and pair.shape == (Q,) and pair.is_contiguous()
+        if check_pair and Q and (int(pair.min()) < 0 or int(pair.max()) >= N):
+            raise ValueError(f"{what}: pair outside [0, N)")
+    if out is None:
+        higher, ties = (torch.empty(Q, dtype=torch.int32, device=dev) for _ in range(2)) if pair is not None else (None, None)
+        top_s, top_r = _lists(Q, k, dev) if k > 0 else (None, None)
+    else:
+        higher, ties, top_s, top_r = out
+    ws = _scratch(ws, _lib.lib().tan_rank_topk_ws_bytes(Q, N, k), dev)
+    _call("rank_topk", tq, q_scale, vn, v_scale, Q, N, tq.shape[1], _ptr(pair), k, splits, _ptr(higher), _ptr(ties), _ptr(top_s),
+          _ptr(top_r), _ptr(ws))
+    return higher, ties, top_s, top_r
+
+
 def rank_topk(tq, vn, pair=None, k=0, *, splits=0, check_pair=False, out=None, ws=None):
     """Matrix-free rank / top-k of scores = tq @ vn.T (tan_rank_topk): tq [Q, 512], vn [N, 512], both bf16 or both f32, contiguous.
     pair [Q] int32 (device) or None.  Returns (higher [Q] int32, ties [Q] int32, top_score [Q, k] f32, top_row [Q, k] int32); the
     pieces that were not asked for (no pair / k == 0) are None.  splits: 0 = automatic; the result does not depend on it.
     check_pair: verify pair in [0, N) on the host (one synchronisation); otherwise that is the caller's contract.
     out / ws: caller-owned outputs (the same 4-tuple) and scratch (uint8, >= rank_topk_ws_bytes) instead of fresh ones."""
-    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and _dt(tq) == _dt(vn)
-    Q, N, dev = tq.shape[0], vn.shape[0], tq.device
-    if pair is not None:
-        assert pair.dtype == torch.int32 and pair.shape == (Q,) and pair.is_contiguous()
-        if check_pair and Q and (int(pair.min()) < 0 or int(pair.max()) >= N):
-            raise ValueError("rank_topk: pair outside [0, N)")
-    if out is None:
-        higher = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
-        ties = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
-        top_s = torch.empty(Q, k, dtype=torch.float32, device=dev) if k > 0 else None
-        top_r = torch.empty(Q, k, dtype=torch.int32, device=dev) if k > 0 else None
-    else:
-        higher, ties, top_s, top_r = out
-    L = _lib.lib()
-    need = L.tan_rank_topk_ws_bytes(Q, N, k)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
-    _lib.check(L.tan_rank_topk(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(pair), k, splits, _ptr(higher), _ptr(ties),
-                               _ptr(top_s), _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk")
-    return higher, ties, top_s, top_r
+    return _rank_topk("rank_topk", tq, None, vn, None, pair, k, splits, check_pair, out, ws)
 
 
 def quantize_rows_e4m3(x, codes=None, scale=None):
@@ -367,29 +400,8 @@ def quantize_rows_e4m3(x, codes=None, scale=None):
 def rank_topk_e4m3(tq, q_scale, vn, v_scale, pair=None, k=0, *, splits=0, check_pair=False, out=None, ws=None):
     """`rank_topk` over e4m3 rows (tan_rank_topk_e4m3): tq [Q, 512] / vn [N, 512] uint8 codes with their f32 row scales q_scale [Q] /
     v_scale [N], as `quantize_rows_e4m3` makes them; score = (acc * v_scale[n]) * q_scale[q].  Everything else as `rank_topk`."""
-    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype == torch.uint8
-    Q, N, dev = tq.shape[0], vn.shape[0], tq.device
-    assert q_scale.shape == (Q,) and v_scale.shape == (N,) and q_scale.is_contiguous() and v_scale.is_contiguous()
-    if pair is not None:
-        assert pair.dtype == torch.int32 and pair.shape == (Q,) and pair.is_contiguous()
-        if check_pair and Q and (int(pair.min()) < 0 or int(pair.max()) >= N):
-            raise ValueError("rank_topk_e4m3: pair outside [0, N)")
-    if out is None:
-        higher = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
-        ties = torch.empty(Q, dtype=torch.int32, device=dev) if pair is not None else None
-        top_s = torch.empty(Q, k, dtype=torch.float32, device=dev) if k > 0 else None
-        top_r = torch.empty(Q, k, dtype=torch.int32, device=dev) if k > 0 else None
-    else:
-        higher, ties, top_s, top_r = out
-    L = _lib.lib()
-    need = L.tan_rank_topk_ws_bytes(Q, N, k)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
-    _lib.check(L.tan_rank_topk_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(pair), k, splits,
-                                    _ptr(higher), _ptr(ties), _ptr(top_s), _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk_e4m3")
-    return higher, ties, top_s, top_r
+    assert tq.dtype == torch.uint8
+    return _rank_topk("rank_topk_e4m3", tq, q_scale, vn, v_scale, pair, k, splits, check_pair, out, ws)
 
 
 def rank_topk_video_ws_bytes(Q, N, n_videos, k):
@@ -400,14 +412,8 @@ def rank_topk_video_ws_bytes(Q, N, n_videos, k):
 
 
 def _video_args(what, tq, vn, v_off, q_scale, v_scale):
-    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype
     assert v_off.dtype == torch.int32 and v_off.dim() == 1 and v_off.numel() >= 2 and v_off.is_contiguous()
-    e4m3 = tq.dtype == torch.uint8
-    if (q_scale is not None) != e4m3 or (v_scale is not None) != e4m3:
-        raise TypeError(f"{what}: q_scale / v_scale go with uint8 e4m3 codes, and only with them")
-    if e4m3:
-        assert q_scale.shape == (tq.shape[0],) and v_scale.shape == (vn.shape[0],) and q_scale.is_contiguous() and v_scale.is_contiguous()
-    return e4m3
+    return _rows_args(what, tq, vn, q_scale, v_scale)
 
 
 def rank_topk_video(tq, vn, v_off, k, *, q_scale=None, v_scale=None, splits=0, check_v_off=False, out=None, ws=None):
@@ -418,29 +424,16 @@ def rank_topk_video(tq, vn, v_off, k, *, q_scale=None, v_scale=None, splits=0, c
     on it.  check_v_off: verify on the host (one synchronisation) that v_off starts at 0, ends at N and strictly increases;
     otherwise that is the caller's contract.  out / ws: caller-owned outputs (the same 3-tuple) and scratch (uint8,
     >= rank_topk_video_ws_bytes) instead of fresh ones."""
-    e4m3 = _video_args("rank_topk_video", tq, vn, v_off, q_scale, v_scale)
+    _video_args("rank_topk_video", tq, vn, v_off, q_scale, v_scale)
     Q, N, nv, dev = tq.shape[0], vn.shape[0], v_off.numel() - 1, tq.device
     if check_v_off:
         v = v_off.cpu()
         if int(v[0]) != 0 or int(v[-1]) != N or not bool((v[1:] > v[:-1]).all()):
             raise ValueError("rank_topk_video: v_off must start at 0, end at N and strictly increase")
-    if out is None:
-        out = (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev),
-               torch.empty(Q, k, dtype=torch.int32, device=dev))
-    top_s, top_r, top_v = out
-    L = _lib.lib()
-    need = L.tan_rank_topk_video_ws_bytes(Q, N, nv, k)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
-    if e4m3:
-        _lib.check(L.tan_rank_topk_video_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(v_off), nv, k,
-                                              splits, _f32(top_s), _ptr(top_r), _ptr(top_v), _ptr(ws), _stream()),
-                   "tan_rank_topk_video_e4m3")
-    else:
-        _lib.check(L.tan_rank_topk_video(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(v_off), nv, k, splits, _f32(top_s),
-                                         _ptr(top_r), _ptr(top_v), _ptr(ws), _stream()), "tan_rank_topk_video")
+    top_s, top_r, top_v = _lists(Q, k, dev, video=True) if out is None else out
+    ws = _scratch(ws, _lib.lib().tan_rank_topk_video_ws_bytes(Q, N, nv, k), dev)
+    _call("rank_topk_video", tq, q_scale, vn, v_scale, Q, N, tq.shape[1], _ptr(v_off), nv, k, splits, _f32(top_s), _ptr(top_r),
+          _ptr(top_v), _ptr(ws))
     return top_s, top_r, top_v
 
 
@@ -472,29 +465,13 @@ def rank_topk_filtered(tq, vn, filt, k, *, q_scale=None, v_scale=None, splits=0,
     gathered admitted rows; with fewer than k of them the tail is (-inf, 0x7fffffff).  splits: 0 = automatic; the result does not
     depend on it.  out / ws: caller-owned outputs (the same 2-tuple) and scratch (uint8, >= rank_topk_ws_bytes) instead of fresh
     ones."""
-    assert tq.dim() == 2 and vn.dim() == 2 and tq.is_contiguous() and vn.is_contiguous() and tq.dtype == vn.dtype
-    e4m3 = tq.dtype == torch.uint8
-    if (q_scale is not None) != e4m3 or (v_scale is not None) != e4m3:
-        raise TypeError("rank_topk_filtered: q_scale / v_scale go with uint8 e4m3 codes, and only with them")
+    _rows_args("rank_topk_filtered", tq, vn, q_scale, v_scale)
     Q, N, dev = tq.shape[0], vn.shape[0], tq.device
-    if e4m3:
-        assert q_scale.shape == (Q,) and v_scale.shape == (N,) and q_scale.is_contiguous() and v_scale.is_contiguous()
     L = _lib.lib()
     assert filt.dtype == torch.uint8 and filt.is_contiguous() and filt.numel() >= max(L.tan_row_filter_bytes(N), 0)
-    if out is None:
-        out = (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev))
-    top_s, top_r = out
-    need = L.tan_rank_topk_ws_bytes(Q, N, k)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
-    if e4m3:
-        _lib.check(L.tan_rank_topk_filtered_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(filt), k,
-                                                 splits, _f32(top_s), _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk_filtered_e4m3")
-    else:
-        _lib.check(L.tan_rank_topk_filtered(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(filt), k, splits, _f32(top_s),
-                                            _ptr(top_r), _ptr(ws), _stream()), "tan_rank_topk_filtered")
+    top_s, top_r = _lists(Q, k, dev) if out is None else out
+    ws = _scratch(ws, L.tan_rank_topk_ws_bytes(Q, N, k), dev)
+    _call("rank_topk_filtered", tq, q_scale, vn, v_scale, Q, N, tq.shape[1], _ptr(filt), k, splits, _f32(top_s), _ptr(top_r), _ptr(ws))
     return top_s, top_r
 
 
@@ -502,37 +479,39 @@ def rank_topk_video_filtered(tq, vn, v_off, filt, k, *, q_scale=None, v_scale=No
     """`rank_topk_video` over the admitted rows of filt (`row_filter_build`'s image for N rows; tan_rank_topk_video_filtered /
     _e4m3): a video's entry is its best admitted row, a video without one never appears, and with fewer than k admitted videos the
     tail is (-inf, 0x7fffffff, -1).  Everything else as `rank_topk_video`."""
-    e4m3 = _video_args("rank_topk_video_filtered", tq, vn, v_off, q_scale, v_scale)
+    _video_args("rank_topk_video_filtered", tq, vn, v_off, q_scale, v_scale)
     Q, N, nv, dev = tq.shape[0], vn.shape[0], v_off.numel() - 1, tq.device
     L = _lib.lib()
     assert filt.dtype == torch.uint8 and filt.is_contiguous() and filt.numel() >= max(L.tan_row_filter_bytes(N), 0)
-    if out is None:
-        out = (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev),
-               torch.empty(Q, k, dtype=torch.int32, device=dev))
-    top_s, top_r, top_v = out
-    need = L.tan_rank_topk_video_ws_bytes(Q, N, nv, k)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
-    if e4m3:
-        _lib.check(L.tan_rank_topk_video_filtered_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(v_off),
-                                                       nv, _ptr(filt), k, splits, _f32(top_s), _ptr(top_r), _ptr(top_v), _ptr(ws),
-                                                       _stream()), "tan_rank_topk_video_filtered_e4m3")
-    else:
-        _lib.check(L.tan_rank_topk_video_filtered(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(v_off), nv, _ptr(filt), k, splits,
-                                                  _f32(top_s), _ptr(top_r), _ptr(top_v), _ptr(ws), _stream()),
-                   "tan_rank_topk_video_filtered")
+    top_s, top_r, top_v = _lists(Q, k, dev, video=True) if out is None else out
+    ws = _scratch(ws, L.tan_rank_topk_video_ws_bytes(Q, N, nv, k), dev)
+    _call("rank_topk_video_filtered", tq, q_scale, vn, v_scale, Q, N, tq.shape[1], _ptr(v_off), nv, _ptr(filt), k, splits, _f32(top_s),
+          _ptr(top_r), _ptr(top_v), _ptr(ws))
     return top_s, top_r, top_v
 
 
-def _label_out(what, N, k, dev, out):
+def _label_topk(what, e4m3, tl, l_scale, vn, v_scale, k, out):
+    """The body of `label_topk` (e4m3 = False, no scales) and `label_topk_e4m3`.  Unlike the sweeps' wrappers, this family answers
+    every bad argument with an exception of its own instead of an assertion."""
+    if tl.dim() != 2 or vn.dim() != 2 or not tl.is_contiguous() or not vn.is_contiguous() or (not e4m3 and tl.dtype != vn.dtype):
+        raise ValueError(f"{what}: tl [L, 512] and vn [N, 512] are contiguous" + ("" if e4m3 else " and of one dtype"))
+    if e4m3 and (tl.dtype != torch.uint8 or vn.dtype != torch.uint8):
+        raise TypeError(f"{what}: uint8 e4m3 codes")
+    if not e4m3 and tl.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{what}: bf16 or f32 rows (e4m3 codes go to label_topk_e4m3)")
+    L_, N, k = tl.shape[0], vn.shape[0], int(k)
+    if tl.shape[1] != 512 or vn.shape[1] != 512 or N < 1 or not 1 <= k <= min(32, L_):
+        raise ValueError(f"{what}: width 512, N >= 1 and 1 <= k <= min(32, L)")
+    for s, n in ((l_scale, L_), (v_scale, N)) if e4m3 else ():
+        if s is None or s.dtype != torch.float32 or s.shape != (n,) or not s.is_contiguous():
+            raise ValueError(f"{what}: l_scale [L] and v_scale [N] are contiguous f32")
     if out is None:
-        return torch.empty(N, k, dtype=torch.float32, device=dev), torch.empty(N, k, dtype=torch.int32, device=dev)
+        out = _lists(N, k, vn.device)
     top_s, top_l = out
     if top_s.dtype != torch.float32 or top_l.dtype != torch.int32 or top_s.shape != (N, k) or top_l.shape != (N, k) \
             or not top_s.is_contiguous() or not top_l.is_contiguous():
         raise ValueError(f"{what}: out is (top_score f32 [N, k], top_label int32 [N, k]), contiguous")
+    _call("label_topk", tl, l_scale, vn, v_scale, L_, N, 512, k, _f32(top_s), _ptr(top_l))
     return top_s, top_l
 
 
@@ -541,36 +520,13 @@ def label_topk(tl, vn, k=1, *, out=None):
     f32, contiguous.  Returns (top_score [N, k] f32, top_label [N, k] int32), by descending score, equal scores by ascending label;
     1 <= k <= min(32, L).  One launch without scratch; nothing of size N * L is stored.  out: caller-owned outputs (the same
     2-tuple) instead of fresh ones."""
-    if tl.dim() != 2 or vn.dim() != 2 or not tl.is_contiguous() or not vn.is_contiguous() or tl.dtype != vn.dtype:
-        raise ValueError("label_topk: tl [L, 512] and vn [N, 512] are contiguous and of one dtype")
-    if tl.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("label_topk: bf16 or f32 rows (e4m3 codes go to label_topk_e4m3)")
-    L_, N, dev = tl.shape[0], vn.shape[0], vn.device
-    if tl.shape[1] != 512 or vn.shape[1] != 512 or N < 1 or not 1 <= int(k) <= min(32, L_):
-        raise ValueError("label_topk: width 512, N >= 1 and 1 <= k <= min(32, L)")
-    top_s, top_l = _label_out("label_topk", N, int(k), dev, out)
-    _lib.check(_lib.lib().tan_label_topk(_ptr(tl), _ptr(vn), _dt(tl), L_, N, 512, int(k), _f32(top_s), _ptr(top_l), _stream()),
-               "tan_label_topk")
-    return top_s, top_l
+    return _label_topk("label_topk", False, tl, None, vn, None, k, out)
 
 
 def label_topk_e4m3(tl, l_scale, vn, v_scale, k=1, *, out=None):
     """`label_topk` over e4m3 rows (tan_label_topk_e4m3): tl [L, 512] / vn [N, 512] uint8 codes with their f32 row scales l_scale [L]
     / v_scale [N], as `quantize_rows_e4m3` makes them; score = (acc * v_scale[n]) * l_scale[l].  Everything else as `label_topk`."""
-    if tl.dim() != 2 or vn.dim() != 2 or not tl.is_contiguous() or not vn.is_contiguous():
-        raise ValueError("label_topk_e4m3: tl [L, 512] and vn [N, 512] are contiguous")
-    if tl.dtype != torch.uint8 or vn.dtype != torch.uint8:
-        raise TypeError("label_topk_e4m3: uint8 e4m3 codes")
-    L_, N, dev = tl.shape[0], vn.shape[0], vn.device
-    if tl.shape[1] != 512 or vn.shape[1] != 512 or N < 1 or not 1 <= int(k) <= min(32, L_):
-        raise ValueError("label_topk_e4m3: width 512, N >= 1 and 1 <= k <= min(32, L)")
-    for s, n in ((l_scale, L_), (v_scale, N)):
-        if s is None or s.dtype != torch.float32 or s.shape != (n,) or not s.is_contiguous():
-            raise ValueError("label_topk_e4m3: l_scale [L] and v_scale [N] are contiguous f32")
-    top_s, top_l = _label_out("label_topk_e4m3", N, int(k), dev, out)
-    _lib.check(_lib.lib().tan_label_topk_e4m3(_ptr(tl), _f32(l_scale), _ptr(vn), _f32(v_scale), L_, N, 512, int(k), _f32(top_s),
-                                              _ptr(top_l), _stream()), "tan_label_topk_e4m3")
-    return top_s, top_l
+    return _label_topk("label_topk_e4m3", True, tl, l_scale, vn, v_scale, k, out)
 
 
 def label_runs_ws_bytes(N):
@@ -632,7 +588,7 @@ def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scal
     inside the hit's video, whose score is >= top_score - width -- global rows, inclusive (tan_moment_extent / _e4m3; the exact
     definition is in include/tan_hip.h).  tq / vn / v_off / q_scale / v_scale as for `rank_topk_video`; width >= 0.
     out: caller-owned (start, end) instead of fresh ones."""
-    e4m3 = _video_args("moment_extent", tq, vn, v_off, q_scale, v_scale)
+    _video_args("moment_extent", tq, vn, v_off, q_scale, v_scale)
     Q, N, nv, dev = tq.shape[0], vn.shape[0], v_off.numel() - 1, tq.device
     k = top_row.shape[1]
     for t, dt in ((top_score, torch.float32), (top_row, torch.int32), (top_video, torch.int32)):
@@ -641,15 +597,8 @@ def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scal
         out = (torch.empty(Q, k, dtype=torch.int32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev))
     start, end = out
     assert all(t.dtype == torch.int32 and t.shape == (Q, k) and t.is_contiguous() for t in out)
-    L = _lib.lib()
-    if e4m3:
-        _lib.check(L.tan_moment_extent_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Q, N, tq.shape[1], _ptr(v_off), nv, k,
-                                            _f32(top_score), _ptr(top_row), _ptr(top_video), float(width), _ptr(start), _ptr(end),
-                                            _stream()), "tan_moment_extent_e4m3")
-    else:
-        _lib.check(L.tan_moment_extent(_ptr(tq), _ptr(vn), _dt(tq), Q, N, tq.shape[1], _ptr(v_off), nv, k, _f32(top_score),
-                                       _ptr(top_row), _ptr(top_video), float(width), _ptr(start), _ptr(end), _stream()),
-                   "tan_moment_extent")
+    _call("moment_extent", tq, q_scale, vn, v_scale, Q, N, tq.shape[1], _ptr(v_off), nv, k, _f32(top_score), _ptr(top_row),
+          _ptr(top_video), float(width), _ptr(start), _ptr(end))
     return start, end
 
 
@@ -680,24 +629,12 @@ def sequence_topk(tq, vn, s_off, v_off, k, *, q_scale=None, v_scale=None, splits
     video.  splits: 0 = automatic; the result does not depend on it.  check_offsets: verify s_off and v_off on the host (one
     synchronisation); otherwise they are the caller's contract.  out / ws: caller-owned outputs (the same 2-tuple) and scratch
     (uint8, >= sequence_topk_ws_bytes) instead of fresh ones."""
-    e4m3 = _sequence_args("sequence_topk", tq, vn, s_off, v_off, q_scale, v_scale, check_offsets)
+    _sequence_args("sequence_topk", tq, vn, s_off, v_off, q_scale, v_scale, check_offsets)
     Qt, N, ns, nv, dev = tq.shape[0], vn.shape[0], s_off.numel() - 1, v_off.numel() - 1, tq.device
-    if out is None:
-        out = (torch.empty(ns, k, dtype=torch.float32, device=dev), torch.empty(ns, k, dtype=torch.int32, device=dev))
-    top_s, top_v = out
-    L = _lib.lib()
-    need = L.tan_sequence_topk_ws_bytes(ns, N, k)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
-    if e4m3:
-        _lib.check(L.tan_sequence_topk_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Qt, N, tq.shape[1], _ptr(s_off), ns,
-                                            _ptr(v_off), nv, k, splits, _f32(top_s), _ptr(top_v), _ptr(ws), _stream()),
-                   "tan_sequence_topk_e4m3")
-    else:
-        _lib.check(L.tan_sequence_topk(_ptr(tq), _ptr(vn), _dt(tq), Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, k, splits,
-                                       _f32(top_s), _ptr(top_v), _ptr(ws), _stream()), "tan_sequence_topk")
+    top_s, top_v = _lists(ns, k, dev) if out is None else out
+    ws = _scratch(ws, _lib.lib().tan_sequence_topk_ws_bytes(ns, N, k), dev)
+    _call("sequence_topk", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, k, splits, _f32(top_s),
+          _ptr(top_v), _ptr(ws))
     return top_s, top_v
 
 
@@ -705,20 +642,14 @@ def sequence_scores(tq, vn, s_off, v_off, hits, x_off, x, *, q_scale=None, v_sca
     """x [n_x] f32 (caller-owned, returned): for every hit h of hits [P, 2] int32 = (sequence, video), the [m, V] block of step x
     second scores at x[x_off[h]:], x_off [P] int64 -- the scores `sequence_topk` ranked by, bit for bit (tan_sequence_scores /
     _e4m3).  Everything else as `sequence_topk`."""
-    e4m3 = _sequence_args("sequence_scores", tq, vn, s_off, v_off, q_scale, v_scale, check_offsets)
+    _sequence_args("sequence_scores", tq, vn, s_off, v_off, q_scale, v_scale, check_offsets)
     Qt, N, ns, nv = tq.shape[0], vn.shape[0], s_off.numel() - 1, v_off.numel() - 1
     P = hits.shape[0]
     assert hits.dtype == torch.int32 and hits.shape == (P, 2) and hits.is_contiguous()
     assert x_off.dtype == torch.int64 and x_off.shape == (P,) and x_off.is_contiguous()
     assert x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()
-    L = _lib.lib()
-    if e4m3:
-        _lib.check(L.tan_sequence_scores_e4m3(_ptr(tq), _f32(q_scale), _ptr(vn), _f32(v_scale), Qt, N, tq.shape[1], _ptr(s_off), ns,
-                                              _ptr(v_off), nv, _ptr(hits), _ptr(x_off), P, _f32(x), x.numel(), _stream()),
-                   "tan_sequence_scores_e4m3")
-    else:
-        _lib.check(L.tan_sequence_scores(_ptr(tq), _ptr(vn), _dt(tq), Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, _ptr(hits),
-                                         _ptr(x_off), P, _f32(x), x.numel(), _stream()), "tan_sequence_scores")
+    _call("sequence_scores", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, _ptr(hits), _ptr(x_off), P,
+          _f32(x), x.numel())
     return x
 
 

@@ -189,9 +189,7 @@ class RowFilter:
         self.n_rows = int((spans[:, 1] - spans[:, 0]).sum())
         if self.n_rows == 0:
             raise ValueError("restrict: the filter admits no row")
-        sharded = isinstance(index, ShardedIndex)
-        row_base = index.row_base if sharded else np.array([0, len(index)], dtype=np.int64)
-        shard_v_off = [sh.v_off for sh in index.shards] if sharded else [index.v_off]
+        row_base, shard_v_off = index.row_base, [sh.v_off for sh in index.shards]
         self._parts, self._images = {}, {}
         for s in range(len(row_base) - 1):
             lo, hi = np.maximum(spans[:, 0], row_base[s]), np.minimum(spans[:, 1], row_base[s + 1])
@@ -224,10 +222,8 @@ class RowFilter:
 
     def image(self, s=0):
         if s not in self._images:
-            sharded = isinstance(self._index, ShardedIndex)
-            n = len(self._index.shards[s]) if sharded else len(self._index)
             spans = torch.from_numpy(self.shard_spans(s).astype(np.int32)).to(self._index.device)
-            self._images[s] = ops.row_filter_build(spans, n)
+            self._images[s] = ops.row_filter_build(spans, len(self._index.shards[s]))
         return self._images[s]
 
     def clip(self, row, start, end):
@@ -239,6 +235,13 @@ class RowFilter:
 def _restrict(index, videos, exclude, windows):
     spans, n_videos = restrict_spans(index.v_off, index.vids, videos, exclude, windows)
     return RowFilter(index, spans, n_videos, windows is not None)
+
+
+def _locate(index, shard, row):
+    """(shard, shard-local row) of either kind of index -> (global video number, second)"""
+    g = index.row_base[np.asarray(shard, dtype=np.int64)] + np.asarray(row, dtype=np.int64)
+    v = np.searchsorted(index.v_off, g, side="right") - 1
+    return v, g - index.v_off[v]
 
 
 _RESTRICT_DOC = """The `RowFilter` that admits only some of this index's rows, for `search`, `search_moments` and `search_rerank`
@@ -262,6 +265,8 @@ class VideoIndex:
         assert (scale is not None) == (feat.dtype == torch.uint8)
         assert stem is None or (stem.shape == (feat.shape[0], 512) and stem.dtype in (torch.bfloat16, torch.float32))
         self._v_off_dev = None
+        # to the searches this is a `ShardedIndex` of one shard, itself (`shards`, `shard_views`): its rows and videos are the global ones
+        self.row_base, self.video_base = (np.array([0, n], dtype=np.int64) for n in (feat.shape[0], len(self.vids)))
 
     @property
     def v_off_device(self):
@@ -323,9 +328,16 @@ class VideoIndex:
 
     def locate(self, rows):
         """index rows -> (video number, second)"""
-        rows = np.asarray(rows, dtype=np.int64)
-        v = np.searchsorted(self.v_off, rows, side="right") - 1
-        return v, rows - self.v_off[v]
+        return _locate(self, 0, rows)
+
+    @property
+    def shards(self):
+        return [self]
+
+    def shard_views(self, order=None):
+        """`ShardedIndex.shard_views` of the one shard: yields (0, feat, scale, v_off_device), once unless `order` is empty"""
+        for s in ([0] if order is None else order):
+            yield s, self.feat, self.scale, self.v_off_device
 
     def save(self, path):
         """One .npz of plain arrays (bf16 rows as their uint16 bit patterns; e4m3 rows as uint8 codes plus `scale`; `stem`, bf16 as
@@ -426,10 +438,7 @@ class ShardedIndex:
 
     def locate(self, shard, row):
         """(shard, shard-local row) -> (global video number, second)"""
-        shard, row = np.asarray(shard, dtype=np.int64), np.asarray(row, dtype=np.int64)
-        g = self.row_base[shard] + row
-        v = np.searchsorted(self.v_off, g, side="right") - 1
-        return v, g - self.v_off[v]
+        return _locate(self, shard, row)
 
     def shard_views(self, order=None):
         """Yields (s, feat, scale, v_off) -- device tensors of shard s, v_off its int32 offsets -- for s in `order` (default: every
@@ -542,19 +551,68 @@ def query_features(index, model, embed_text, queries, text_batch=1024):
     return t if index.row_dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.row_dtype, device=dev))
 
 
-def _run_lists(Q, k, n_aux, dev):
-    """`ops.topk_fold`'s running lists for Q queries, uninitialised: the first fold resets them"""
-    return (torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.int32, device=dev),
-            torch.empty(Q, k, dtype=torch.int32, device=dev), torch.empty(n_aux, Q, k, dtype=torch.int32, device=dev) if n_aux else None)
+class _Sweep:
+    """The query side of one search call, made once from `query_features`' result (for an e4m3 index: codes and scales), and the
+    ONE place that chooses the sweep of a shard view from (e4m3, restrict)."""
+
+    def __init__(self, index, tq, restrict=None, splits=0):
+        self.e4m3, self.restrict, self.splits = index.e4m3, restrict, splits
+        self.tq, self.q_scale = tq if index.e4m3 else (tq, None)
+
+    def scales(self, v_scale):
+        """the scale keywords of an `ops` call over a view whose row scales are v_scale"""
+        return dict(q_scale=self.q_scale, v_scale=v_scale) if self.e4m3 else {}
+
+    def rows(self, s, feat, scale, k):
+        """(score, row): the k best rows of shard s's view -- of its admitted rows under a filter; k is clamped to them"""
+        if self.restrict is not None:
+            return ops.rank_topk_filtered(self.tq, feat, self.restrict.image(s), min(k, self.restrict.shard_rows(s)), splits=self.splits,
+                                          **self.scales(scale))
+        if self.e4m3:
+            return ops.rank_topk_e4m3(self.tq, self.q_scale, feat, scale, None, min(k, feat.shape[0]), splits=self.splits)[2:]
+        return ops.rank_topk(self.tq, feat, None, min(k, feat.shape[0]), splits=self.splits)[2:]
+
+    def videos(self, s, feat, scale, v_off, k):
+        """(score, row, video): the k best distinct videos of shard s's view, each by its best (admitted) row; k is clamped"""
+        if self.restrict is not None:
+            return ops.rank_topk_video_filtered(self.tq, feat, v_off, self.restrict.image(s), min(k, self.restrict.shard_videos(s)),
+                                                splits=self.splits, **self.scales(scale))
+        return ops.rank_topk_video(self.tq, feat, v_off, min(k, v_off.numel() - 1), splits=self.splits, **self.scales(scale))
 
 
-def _read_lists(run):
-    """One read-back of the folded lists: score [Q, k] f32 (travelling as its bit pattern) and int32 [2 + n_aux, Q, k] = shard, row,
-    then the payload columns."""
-    score, shard, row, aux = run
-    ints = torch.stack((shard, row)) if aux is None else torch.cat((torch.stack((shard, row)), aux))
-    back = torch.cat((score.view(torch.int32)[None], ints)).cpu().numpy()
-    return back[0].view(np.float32), back[1:]
+class _TopLists:
+    """The k best of a search over the views of an index.  A `ShardedIndex`: every shard's lists are folded into running ones on
+    the device (`ops.topk_fold`, once per shard).  A `VideoIndex`: its one view's lists ARE the result, and no fold is launched.
+    lists: (score f32, shard int32 -- None for a `VideoIndex`: all 0 --, row, *payload int32), [Q, k] each, on the device."""
+
+    def __init__(self, index, Q, k, n_aux):
+        self.run = self.lists = None
+        if isinstance(index, ShardedIndex):        # `ops.topk_fold`'s running lists, uninitialised: the first fold resets them
+            i32 = dict(dtype=torch.int32, device=index.device)
+            self.run = (torch.empty(Q, k, dtype=torch.float32, device=index.device), torch.empty(Q, k, **i32), torch.empty(Q, k, **i32),
+                        torch.empty(n_aux, Q, k, **i32) if n_aux else None)
+
+    def add(self, s, lists):
+        """lists = (score, row, *payload) of shard s, shard-local"""
+        if self.run is None:
+            self.lists = (lists[0], None, *lists[1:])
+        else:
+            ops.topk_fold(self.run, lists, s, reset=self.lists is None)
+            self.lists = (*self.run[:3], *(() if self.run[3] is None else self.run[3]))
+
+    def winners(self):
+        """A read-back of (shard, row) alone, flat int64: `search_sequences` sizes its score blocks from them"""
+        if self.run is None:
+            row = self.lists[2].cpu().numpy().reshape(-1).astype(np.int64)
+            return np.zeros_like(row), row
+        return tuple(a.reshape(-1).astype(np.int64) for a in torch.stack(self.lists[1:3]).cpu().numpy())
+
+    def read(self):
+        """The one read-back: (score [Q, k] f32, which travels as its bit pattern, shard [Q, k], (row, *payload) int32 [Q, k])"""
+        ints = torch.stack(self.lists[2 if self.run is None else 1:])
+        back = torch.cat((self.lists[0].view(torch.int32)[None], ints)).cpu().numpy()
+        shard, ints = (np.zeros_like(back[1]), back[1:]) if self.run is None else (back[1], back[2:])
+        return back[0].view(np.float32), shard, ints
 
 
 @torch.no_grad()
@@ -562,7 +620,7 @@ def search(index, model, embed_text, queries, k=10, splits=0, restrict=None):
     """Per query the k best seconds of the corpus: [[(vid, second, score)] * k] * len(queries), by descending score (equal scores
     by index row).  score = <index row, unit text feature>: the stitched dual cosine; / 0.07 gives the evaluation's logit.
     `index`: a `VideoIndex`, or a `ShardedIndex` -- then exactly what `VideoIndex.concat` of its shards gives (as for
-    `search_moments` and `search_sequences`): one sweep and one `tan_topk_fold` per shard, one read-back at the end.
+    `search_moments` and `search_sequences`): one sweep and one `tan_topk_fold` per shard.  One read-back at the end for either.
     restrict: a `RowFilter` of this index (`index.restrict(...)`): only its rows are swept (`tan_rank_topk_filtered`) and returned,
     with the scores and the order the unrestricted call gives them; k is clamped to the admitted rows."""
     queries = list(queries)
@@ -573,30 +631,12 @@ def search(index, model, embed_text, queries, k=10, splits=0, restrict=None):
     k = min(int(k), len(index) if restrict is None else restrict.n_rows)
     if not 1 <= k <= 32:
         raise ValueError("search: k must lie in [1, 32]")
-    tq = query_features(index, model, embed_text, queries)
-    if isinstance(index, ShardedIndex):
-        run = _run_lists(len(queries), k, 0, index.device)
-        for i, (s, feat, scale, _) in enumerate(index.shard_views(None if restrict is None else restrict.ready())):
-            if restrict is not None:
-                tq_, scales = (tq[0], dict(q_scale=tq[1], v_scale=scale)) if index.e4m3 else (tq, {})
-                score, row = ops.rank_topk_filtered(tq_, feat, restrict.image(s), min(k, restrict.shard_rows(s)), splits=splits, **scales)
-            elif index.e4m3:
-                _, _, score, row = ops.rank_topk_e4m3(*tq, feat, scale, None, min(k, feat.shape[0]), splits=splits)
-            else:
-                _, _, score, row = ops.rank_topk(tq, feat, None, min(k, feat.shape[0]), splits=splits)
-            ops.topk_fold(run, (score, row), s, reset=i == 0)
-        score, (shard, row) = _read_lists(run)
-        v, sec = index.locate(shard, row)
-        return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
-    if restrict is not None:
-        tq_, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
-        score, row = ops.rank_topk_filtered(tq_, index.feat, restrict.image(), k, splits=splits, **scales)
-    elif index.e4m3:
-        _, _, score, row = ops.rank_topk_e4m3(*tq, index.feat, index.scale, None, k, splits=splits)
-    else:
-        _, _, score, row = ops.rank_topk(tq, index.feat, None, k, splits=splits)
-    score, row = score.cpu().numpy(), row.cpu().numpy()
-    v, sec = index.locate(row)
+    sweep = _Sweep(index, query_features(index, model, embed_text, queries), restrict, splits)
+    top = _TopLists(index, len(queries), k, 0)
+    for s, feat, scale, _ in index.shard_views(None if restrict is None else restrict.ready()):
+        top.add(s, sweep.rows(s, feat, scale, k))
+    score, shard, (row,) = top.read()
+    v, sec = _locate(index, shard, row)
     return [[(index.vids[v[q, i]], int(sec[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
 
 
@@ -621,44 +661,23 @@ def search_moments(index, model, embed_text, queries, k=10, width=TEMPERATURE, s
         raise ValueError("search_moments: k must lie in [1, 32]")
     if not width >= 0:
         raise ValueError("search_moments: width must be >= 0")
-    tq = query_features(index, model, embed_text, queries)
-    if isinstance(index, ShardedIndex):
-        tq, q_scale = tq if index.e4m3 else (tq, None)
-        run = _run_lists(len(queries), k, 3, index.device)
-        for i, (s, feat, scale, v_off) in enumerate(index.shard_views(None if restrict is None else restrict.ready())):
-            scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
-            if restrict is not None:
-                score, row, video = ops.rank_topk_video_filtered(tq, feat, v_off, restrict.image(s), min(k, restrict.shard_videos(s)),
-                                                                 splits=splits, **scales)
-            else:
-                score, row, video = ops.rank_topk_video(tq, feat, v_off, min(k, v_off.numel() - 1), splits=splits, **scales)
-            # the extents of the shard's OWN list, before the fold: the shard's rows are passed over once (and are gone afterwards
-            # when they are streamed), at the price of extents for hits the fold drops
-            start, end = ops.moment_extent(tq, feat, v_off, score, row, video, width, **scales)
-            ops.topk_fold(run, (score, row, video, start, end), s, reset=i == 0)
-        score, (shard, row, video, start, end) = _read_lists(run)              # all shard-local
-        first = np.zeros_like(row)
-        for s in np.unique(shard):
-            first[shard == s] = index.shards[s].v_off[video[shard == s]]
-        gv = index.video_base[shard] + video
-        if restrict is not None:
-            base = index.row_base[shard]
-            start, end = (a - base for a in restrict.clip(base + row, base + start, base + end))
-        return [[Moment(index.vids[gv[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
-                        int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
-    tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
-    v_off = index.v_off_device
+    sweep = _Sweep(index, query_features(index, model, embed_text, queries), restrict, splits)
+    top = _TopLists(index, len(queries), k, 3)
+    for s, feat, scale, v_off in index.shard_views(None if restrict is None else restrict.ready()):
+        score, row, video = sweep.videos(s, feat, scale, v_off, k)
+        # the extents of the shard's OWN list, before the fold: the shard's rows are passed over once (and are gone afterwards
+        # when they are streamed), at the price of extents for hits the fold drops
+        start, end = ops.moment_extent(sweep.tq, feat, v_off, score, row, video, width, **sweep.scales(scale))
+        top.add(s, (score, row, video, start, end))
+    score, shard, (row, video, start, end) = top.read()                    # all shard-local
+    first = np.zeros_like(row)
+    for s in np.unique(shard):
+        first[shard == s] = index.shards[s].v_off[video[shard == s]]
+    gv = index.video_base[shard] + video
     if restrict is not None:
-        score, row, video = ops.rank_topk_video_filtered(tq, index.feat, v_off, restrict.image(), k, splits=splits, **scales)
-    else:
-        score, row, video = ops.rank_topk_video(tq, index.feat, v_off, k, splits=splits, **scales)
-    start, end = ops.moment_extent(tq, index.feat, v_off, score, row, video, width, **scales)
-    score = score.cpu().numpy()                                    # the one read-back: the int32 results travel together
-    row, video, start, end = torch.stack((row, video, start, end)).cpu().numpy()
-    if restrict is not None:
-        start, end = restrict.clip(row, start, end)
-    first = index.v_off[video]
-    return [[Moment(index.vids[video[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
+        base = index.row_base[shard]
+        start, end = (a - base for a in restrict.clip(base + row, base + start, base + end))
+    return [[Moment(index.vids[gv[q, i]], int(start[q, i] - first[q, i]), int(end[q, i] - first[q, i]),
                     int(row[q, i] - first[q, i]), float(score[q, i])) for i in range(k)] for q in range(len(queries))]
 
 
@@ -683,44 +702,30 @@ def search_sequences(index, model, embed_text, sequences, k=10, splits=0):
     dev = index.device
     m = np.array([len(seq) for seq in sequences], dtype=np.int64)
     s_off = torch.from_numpy(np.concatenate([[0], np.cumsum(m)]).astype(np.int32)).to(dev)
-    tq = query_features(index, model, embed_text, [sentence for seq in sequences for sentence in seq])
+    sweep = _Sweep(index, query_features(index, model, embed_text, [sentence for seq in sequences for sentence in seq]), splits=splits)
     n_seq = len(sequences)
-    if isinstance(index, ShardedIndex):
-        tq, q_scale = tq if index.e4m3 else (tq, None)
-        # phase 1: every shard's best videos, folded with row = the shard-local video number
-        run = _run_lists(n_seq, k, 0, dev)
-        for i, (s, feat, scale, v_off) in enumerate(index.shard_views()):
-            scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
-            ops.topk_fold(run, ops.sequence_topk(tq, feat, s_off, v_off, min(k, v_off.numel() - 1), splits=splits, **scales), s,
-                          reset=i == 0)
-        shard, video = (a.reshape(-1).astype(np.int64) for a in torch.stack(run[1:3]).cpu().numpy())   # read-back 1: the winners
-        # phase 2: the seconds, shard by shard over the shards that hold winners, each over its own hits
-        seq_of_hit = np.repeat(np.arange(n_seq), k)
-        parts = []
-        holders = [int(s) for s in np.unique(shard)]
-        for s, feat, scale, v_off in index.shard_views(holders):
-            scales = dict(q_scale=q_scale, v_scale=scale) if index.e4m3 else {}
-            at = np.flatnonzero(shard == s)
-            parts.append((at, *_sequence_seconds(tq, feat, s_off, v_off, index.shards[s].v_off, m, seq_of_hit[at], video[at], scales)))
-        back = torch.cat([run[0].reshape(-1).view(torch.int32)] + [ts for _, ts, _ in parts]).cpu().numpy()   # read-back 2
-        score, a0 = back[:n_seq * k].view(np.float32), n_seq * k
-        seconds = [None] * (n_seq * k)
-        for at, ts, first in parts:
-            for j, h in enumerate(at):
-                seconds[h] = tuple(int(t) for t in back[a0 + first[j]:a0 + first[j + 1]])
-            a0 += int(first[-1])
-        gv = index.video_base[shard] + video
-        return [[SequenceHit(index.vids[gv[p * k + i]], seconds[p * k + i], float(score[p * k + i])) for i in range(k)]
-                for p in range(n_seq)]
-    tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
-    v_off = index.v_off_device
-    top_s, top_v = ops.sequence_topk(tq, index.feat, s_off, v_off, k, splits=splits, **scales)
-    video = top_v.cpu().numpy().astype(np.int64)                   # read-back 1: [n_seq, k] winners
-    ts, first = _sequence_seconds(tq, index.feat, s_off, v_off, index.v_off, m, np.repeat(np.arange(n_seq), k), video.reshape(-1), scales)
-    back = torch.cat((top_s.reshape(-1).view(torch.int32), ts)).cpu().numpy()                  # read-back 2: scores and seconds
-    score, ts = back[:n_seq * k].view(np.float32), back[n_seq * k:]
-    return [[SequenceHit(index.vids[video[p, i]], tuple(int(t) for t in ts[first[p * k + i]:first[p * k + i + 1]]),
-                         float(score[p * k + i])) for i in range(k)] for p in range(n_seq)]
+    # phase 1: every shard's best videos, with row = the shard-local video number
+    top = _TopLists(index, n_seq, k, 0)
+    for s, feat, scale, v_off in index.shard_views():
+        top.add(s, ops.sequence_topk(sweep.tq, feat, s_off, v_off, min(k, v_off.numel() - 1), splits=splits, **sweep.scales(scale)))
+    shard, video = top.winners()                                           # read-back 1
+    # phase 2: the seconds, shard by shard over the shards that hold winners (a `VideoIndex`: all in shard 0), each over its own hits
+    seq_of_hit = np.repeat(np.arange(n_seq), k)
+    parts = []
+    for s, feat, scale, v_off in index.shard_views([int(s) for s in np.unique(shard)]):
+        at = np.flatnonzero(shard == s)
+        parts.append((at, *_sequence_seconds(sweep.tq, feat, s_off, v_off, index.shards[s].v_off, m, seq_of_hit[at], video[at],
+                                             sweep.scales(scale))))
+    back = torch.cat([top.lists[0].reshape(-1).view(torch.int32)] + [ts for _, ts, _ in parts]).cpu().numpy()   # read-back 2
+    score, a0 = back[:n_seq * k].view(np.float32), n_seq * k
+    seconds = [None] * (n_seq * k)
+    for at, ts, first in parts:
+        for j, h in enumerate(at):
+            seconds[h] = tuple(int(t) for t in back[a0 + first[j]:a0 + first[j + 1]])
+        a0 += int(first[-1])
+    gv = index.video_base[shard] + video
+    return [[SequenceHit(index.vids[gv[p * k + i]], seconds[p * k + i], float(score[p * k + i])) for i in range(k)]
+            for p in range(n_seq)]
 
 
 def _sequence_seconds(tq, feat, s_off, v_off_dev, v_off, m, seq, video, scales):
@@ -821,13 +826,9 @@ def search_rerank(index, model, embed_text, queries, k=10, pool=32, seq_len=64, 
         raise ValueError("search_rerank: windows_per_pass must be >= 1")
     dev, Q = index.feat.device, len(queries)
     # stage 1: the dual sweep, exactly as search_moments runs it
-    tq = query_features(index, model, embed_text, queries)
-    tq, scales = (tq[0], dict(q_scale=tq[1], v_scale=index.scale)) if index.e4m3 else (tq, {})
     v_off = index.v_off_device
-    if restrict is not None:
-        d_score, d_row, d_video = ops.rank_topk_video_filtered(tq, index.feat, v_off, restrict.image(), pool, splits=splits, **scales)
-    else:
-        d_score, d_row, d_video = ops.rank_topk_video(tq, index.feat, v_off, pool, splits=splits, **scales)
+    d_score, d_row, d_video = _Sweep(index, query_features(index, model, embed_text, queries), restrict, splits).videos(
+        0, index.feat, index.scale, v_off, pool)
     table = _rerank_table(v_off, d_row, d_video, T)
     # stage 2: the joint stack over the stem windows, reduced per pass
     emb = embed_text(queries).to(dev).float().reshape(Q, -1).contiguous()
@@ -953,17 +954,12 @@ def annotate(index, model, embed_text, labels, k=1):
     tl = query_features(index, model, embed_text, labels)
     score = torch.empty(N, k, dtype=torch.float32, device=dev)
     label = torch.empty(N, k, dtype=torch.int32, device=dev)
-    if isinstance(index, ShardedIndex):
-        for s, feat, scale, _ in index.shard_views():
-            out = tuple(t[int(index.row_base[s]):int(index.row_base[s + 1])] for t in (score, label))
-            if index.e4m3:
-                ops.label_topk_e4m3(*tl, feat, scale, k, out=out)
-            else:
-                ops.label_topk(tl, feat, k, out=out)
-    elif index.e4m3:
-        ops.label_topk_e4m3(*tl, index.feat, index.scale, k, out=(score, label))
-    else:
-        ops.label_topk(tl, index.feat, k, out=(score, label))
+    for s, feat, scale, _ in index.shard_views():
+        out = tuple(t[int(index.row_base[s]):int(index.row_base[s + 1])] for t in (score, label))      # the view's slice of the outputs
+        if index.e4m3:
+            ops.label_topk_e4m3(*tl, feat, scale, k, out=out)
+        else:
+            ops.label_topk(tl, feat, k, out=out)
     return Annotation(label, score, labels, index.v_off, index.vids)
 
 

@@ -198,6 +198,39 @@ def test_k_is_clamped_to_the_total(fmt):
         assert [len(res[0]) for res in got] == [min(k, 6), min(k, 3), min(k, 3)]
 
 
+def _bits(hits):
+    """A search's result with every score as its f32 bit pattern: 0.0 and -0.0 differ here"""
+    if isinstance(hits, float):
+        return int(np.float32(hits).view(np.int32))
+    if isinstance(hits, (list, tuple)):
+        items = [_bits(h) for h in hits]
+        return type(hits)(*items) if hasattr(hits, "_fields") else type(hits)(items)       # a namedtuple takes its fields one by one
+    return hits
+
+
+@pytest.mark.parametrize("fmt", ("bf16", "e4m3"))
+def test_one_shard_is_the_index_itself_bit_for_bit(fmt):
+    """A `ShardedIndex` of ONE shard against that `VideoIndex`: the fold of a single list against no fold, shard-local against global
+    numbering.  Videos of 1, 63, 64, 65 and 130 rows: the 64-row tile edge after row 63 is a video boundary, the later ones lie inside
+    videos.  Exact rows (small integers over 16), so equal scores occur and the order among them is compared too."""
+    srch, m = _srch(), _the_model()
+    vlens = (1, 63, 64, 65, 130)
+    feat, scale, _ = _exact_shard(fmt, sum(vlens), 700)
+    index = srch.VideoIndex(feat, np.concatenate([[0], np.cumsum(vlens)]), [f"v{j}" for j in range(len(vlens))], scale)
+    one = srch.ShardedIndex([index])
+    queries, sequences, k = QUERIES[:5], [QUERIES[:1], QUERIES[:3]], 3
+    for name, call in (("search", srch.search), ("search_moments", srch.search_moments)):
+        got, want = call(one, m, _embed, queries, k=k), call(index, m, _embed, queries, k=k)
+        assert _bits(got) == _bits(want) and [len(h) for h in got] == [k] * 5, name
+    got, want = (srch.search_sequences(ix, m, _embed, sequences, k=k) for ix in (one, index))
+    assert _bits(got) == _bits(want) and [len(h.seconds) for h in got[1]] == [3] * k
+    got, want = (srch.annotate(ix, m, _embed, QUERIES[:7], k=2) for ix in (one, index))
+    assert got.label.shape == (sum(vlens), 2) and torch.equal(got.label, want.label)
+    assert torch.equal(got.score.view(torch.int32), want.score.view(torch.int32))
+    assert got.vids == want.vids and got.v_off.tolist() == want.v_off.tolist() and got.labels == want.labels
+    torch.cuda.synchronize()
+
+
 # ---------------------------------------------------------------------------------------------- 3. an independent reference
 class _Identity:
     """A model whose text feature is the embedding itself: exact queries reach the sweeps"""

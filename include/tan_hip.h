@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);
+int tan_version(void);          /* 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -885,6 +885,40 @@ int tan_sequence_scores(const void* Tq, const void* Vn, int dtype, long Qt, long
 int tan_sequence_scores_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
                              const int* s_off, long n_seq, const int* v_off, long n_videos, const int* hits, const long* x_off,
                              long P, float* x, long n_x, void* stream);
+/* ---- clip search: the k videos in which a piece of video appears, second for second, and where ----
+ * A CLIP is 1 to 32 consecutive rows of Tq [Qt, C] (its seconds, in order): c_off [n_clip + 1] int32 on the device, c_off[0] == 0,
+ * c_off[n_clip] == Qt, strictly increasing, every difference in [1, 32] -- the contract of s_off.  A VIDEO v is the index rows
+ * [v_off[v], v_off[v + 1]) -- the v_off contract of tan_rank_topk_video.  For clip p with rows q_0 .. q_{m-1} and video v with V rows,
+ * let x_i[t] = score(q_i, v_off[v] + t), the row sweep's score: the MFMA chain of tan_rank_topk in the same K order (e4m3:
+ * (acc * v_scale[n]) * q_scale[q]).  Then
+ *     S(t)        = (((x_0[t] + x_1[t + 1]) + x_2[t + 2]) + ... ) + x_{m-1}[t + m - 1]        for 0 <= t <= V - m
+ *     match(p, v) = max_t S(t);   start(p, v) = the smallest t attaining it
+ * -- the clip laid over the video second for second, not tan_sequence_topk's non-decreasing seconds.  Every + is one f32 add, round
+ * to nearest, never contracted, in ascending i; the maximum is exact and the add order is fixed, so given the bits of x the bits of
+ * S do not depend on tiling, splits or shards.  A video with V < m has no start and is not a candidate.  Inputs are finite.
+ * tan_sequence_scores with c_off as its s_off returns x with the bits this sweep uses (videos are tiled from their own first row by
+ * the same routine).
+ * tan_clip_topk (Tq, Vn, dtype, C == 512, alignment as tan_rank_topk):
+ *   top_score (f32) / top_row / top_video (int32) [n_clip, k], 1 <= k <= min(32, n_videos): per clip the k videos with the largest
+ *     match(p, v), by descending match, equal matches by ascending row.  top_score is the SUM S (not the mean), top_row =
+ *     v_off[v] + start(p, v) -- a global index row -- and top_video is v.  When fewer than k videos hold m rows, the remaining
+ *     slots are (-inf, 0x7fffffff, -1): the empty slots of the filtered sweeps, which tan_topk_fold sorts last.
+ *   splits: as tan_sequence_topk: a split takes WHOLE videos (those whose first row falls into its row range), 0 = chosen from
+ *     n_clip and N, at most 256.  Results are bit-identical from run to run and for every `splits`; no float atomics.  Nothing of
+ *     size Qt x N, n_clip x N or n_clip x n_videos is stored.
+ *   ws: tan_clip_topk_ws_bytes(n_clip, N, k) bytes of scratch, 16-byte aligned: the splits' lists of (score, row, video) only (at
+ *     most 256 * n_clip * k * 12 bytes); it does not depend on `splits`; -1 for invalid sizes.
+ * Another width, k outside [1, min(32, n_videos)], an unknown dtype, a NULL pointer, misalignment, negative splits, n_clip < 1, Qt
+ * outside [n_clip, 32 * n_clip], n_videos outside [1, N], N outside [1, 2^31): TAN_ERR_BAD_ARG, nothing launched.
+ * A c_off or v_off that breaks its contract is the CALLER's error: every lookup is clamped (a clip of more than 32 rows is cut to
+ * 32), nothing is read or written out of bounds, and the lists are unspecified.  The Python wrapper checks on request.
+ * tan_clip_topk_e4m3 takes the codes and scales of tan_rank_topk_e4m3.                                                            */
+long tan_clip_topk_ws_bytes(long n_clip, long N, int k);
+int tan_clip_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* c_off, long n_clip, const int* v_off,
+                  long n_videos, int k, int splits, float* top_score, int* top_row, int* top_video, void* ws, void* stream);
+int tan_clip_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                       const int* c_off, long n_clip, const int* v_off, long n_videos, int k, int splits, float* top_score,
+                       int* top_row, int* top_video, void* ws, void* stream);
 /* Clip pooling of test_retrieval_yc2 (:197-214).  stage: one stage of the video stack's output, window w's frame f at
  * stage + w * win_stride + f * 512 elements of `dtype` (win_stride >= T * 512, a multiple of 8); table [W, 3] int32 = (clip,
  * first_frame, n_frames) per window.  normalize != 0: every selected frame is L2-normalised (sim = 'cos').  sum [n_clips, 512] /

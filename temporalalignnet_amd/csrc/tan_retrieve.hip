@@ -25,6 +25,9 @@
 // tan_sequence_topk ranks videos by the best ORDER-PRESERVING path of a sequence of up to 32 query rows (tan_decode.hip's recurrence
 // fused into the sweep: seq_kernel, which shares the load / MFMA routine tile_scores with rank_kernel), and tan_sequence_scores
 // writes the winners' step x second scores, with the sweep's bits, for tan_monotonic_decode to backtrack.
+// tan_clip_topk ranks videos by the best SECOND-FOR-SECOND match of a run of up to 32 query rows -- a diagonal sum over the same
+// matrix-free score tile (clip_kernel: seq_kernel's frame with two add chains per lane instead of the scan) -- and returns each
+// video's best start; rank_merge_video_kernel folds its splits.
 // tan_rank_topk_filtered / tan_rank_topk_video_filtered sweep only the rows a FILTER admits (rank_kernel's FILTER mode): the image
 // tan_row_filter_build makes from row spans lists the 64-row tiles that hold an admitted row, with a row mask each; a split walks a
 // range of that list and masks the other rows, so the lists are the plain sweep's over the gathered admitted rows, bit for bit.
@@ -820,6 +823,163 @@ __global__ void __launch_bounds__(256) seq_kernel(const T* __restrict__ Tq, cons
     }
 }
 
+// ---- clip search: videos ranked by the best second-for-second match of a run of query rows (include/tan_hip.h) ----
+// seq_kernel<T, false>'s frame with another epilogue: a wave owns ONE clip (its up to 32 rows are the wave's resident query columns,
+// padded columns are computed and ignored), a workgroup four clips, a split the videos whose first row falls into its row range,
+// every video is tiled from its own first row by tile_scores (rows past its end load as zero) and the wave's accumulators go to its
+// [32][65] LDS block.  Then lanes stand over START seconds.  A diagonal of m <= 32 <= 64 cells crosses at most one tile edge, so a
+// lane keeps two partial sums: `cur` for start 64 tile + lane and `prev` for start 64 (tile - 1) + lane.  Step i adds
+// xw[i][lane + i] to cur while lane + i < 64 and xw[i][lane + i - 64] to prev afterwards: prev's earlier terms were added in the
+// previous tile, so every S(t) is the definition's chain of f32 adds in ascending i whatever the tiling -- and the two chains of a
+// lane are independent: no cross-lane scan.  The read address 65 i + lane + i (mod 64 past the edge) is a rotation of the lanes:
+// conflict-free.  After the loop exactly one start per lane is complete (prev's where lane + m > 64, cur's otherwise); it feeds the
+// lane's running (best, start) under strict >, and a lane meets its starts in ascending order, so the smallest start survives.
+// No start is pending after a video's last tile: such a start would end beyond the video.  A finished video gives ONE candidate
+// (S, v_off[v] + start, v) by a wave reduction (max score, then min start); the 64 candidates of a clip live one per lane in
+// registers, sort64v keeps the k best when they are full and raises the threshold.  rank_merge_video_kernel folds the splits' lists
+// (videos are distinct across splits: distinct64 only sorts).
+template <typename T>
+__global__ void __launch_bounds__(256) clip_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Qt, long N,
+                                                   const int* __restrict__ c_off, int n_clip, const int* __restrict__ v_off,
+                                                   int n_videos, int k, long rows_per_split, const float* __restrict__ q_scale,
+                                                   const float* __restrict__ v_scale, float* __restrict__ part_s,
+                                                   int* __restrict__ part_n, int* __restrict__ part_v) {
+#pragma clang fp contract(off)
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, NCH = RC / KC, NFR = RC / M::KS;
+    constexpr long ROWB = (long)RC * sizeof(T);
+    constexpr bool F8 = sizeof(T) == 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* tile = reinterpret_cast<T*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + 2 * BN * LD * sizeof(T));
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
+    float* xw = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16) + wave * XS_WAVE;
+
+    // the wave's clip and the workgroup's videos [va, vb); every lookup is clamped
+    int p = blockIdx.x * 4 + wave;
+    const long r0 = (long)blockIdx.y * rows_per_split, r1 = r0 + rows_per_split;
+    const int va = r0 <= 0 ? 0 : videos_below(v_off, r0, n_videos);
+    const int vb = r1 >= N ? n_videos : videos_below(v_off, r1, n_videos);
+    const bool pok = p < n_clip;
+    p = p >= n_clip ? n_clip - 1 : p;
+    long q0 = c_off[p];
+    q0 = q0 < 0 ? 0 : (q0 >= Qt ? Qt - 1 : q0);
+    long m_l = (long)c_off[p + 1] - q0;
+    m_l = m_l > Qt - q0 ? Qt - q0 : m_l;
+    const int m = m_l < 1 ? 1 : (m_l > 32 ? 32 : (int)m_l);        // wave-uniform
+
+    frag_t qf[NFR];                                                // the clip's rows, resident; columns >= m repeat the last row
+    const long qme = q0 + (col < m ? col : m - 1);
+    {
+        const T* qrow = Tq + qme * RC;
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(qrow, j, lane);
+    }
+    float qs = 1.0f, psc = 0.0f;
+    if constexpr (F8) qs = q_scale[qme];
+
+    // the tile under the MFMAs: video v, its rows [lo, hi) cut to the index, tile t of it
+    struct Cur { int v; long lo, hi, t; };
+    auto open = [&](int v) {
+        Cur c{v, 0, 0, 0};
+        if (v < vb) {
+            c.lo = v_off[v];
+            c.hi = v_off[v + 1];
+            c.lo = c.lo < 0 ? 0 : (c.lo > N ? N : c.lo);
+            c.hi = c.hi < c.lo ? c.lo : (c.hi > N ? N : c.hi);
+        }
+        return c;
+    };
+    uint4 pre[4];
+    auto issue = [&](const Cur& c, int kc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
+            const long n = c.lo + c.t * BN + row;
+            pre[i] = n < c.hi ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Vn) + n * ROWB + kc * 256 + c16 * 16)
+                              : make_uint4(0, 0, 0, 0);
+        }
+        if constexpr (F8) {
+            if (kc == NCH - 1 && tid < BN) {
+                const long n = c.lo + c.t * BN + tid;
+                psc = n < c.hi ? v_scale[n] : 0.0f;
+            }
+        }
+    };
+
+    float cs = -INFINITY, thr = -INFINITY;                         // the candidate registers: (score, row, video), one per lane
+    int cn = SENT_ROW, cv = -1, fill = 0;                          // fill, thr: wave-uniform
+    float prev = 0.0f, best = -INFINITY;                           // the video under way: the lane's open diagonal and its best start
+    int bstart = SENT_ROW;
+
+    Cur cur = open(va);
+    if (cur.v < vb) issue(cur, 0);
+    while (cur.v < vb) {                                           // block-uniform
+        Cur nxt = cur;
+        if ((cur.t + 1) * BN < cur.hi - cur.lo) ++nxt.t; else nxt = open(cur.v + 1);
+        f32x16 acc[2];
+        tile_scores<T>(tile, sc, tid, lane, pre, psc, qf, qs, acc, [&](int kc) {
+            if (kc + 1 < NCH) issue(cur, kc + 1);
+            else if (nxt.v < vb) issue(nxt, 0);
+        });
+        // the wave's tile -> LDS as [clip row][second]; only this wave reads it back
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) xw[col * XS_LD + rt * 32 + acc_row(r, lane)] = acc[rt][r];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        const long V = cur.hi - cur.lo;
+        float sum = xw[lane];                                      // i = 0: the start 64 t + lane opens
+#pragma unroll 4
+        for (int i = 1; i < m; ++i) {
+            const int j = lane + i;
+            const bool here = j < BN;
+            const float xi = xw[i * XS_LD + (here ? j : j - BN)];
+            const float a = (here ? sum : prev) + xi;              // one add per cell, not contracted
+            sum = here ? a : sum;
+            prev = here ? prev : a;
+        }
+        {
+            const bool done_here = lane + m <= BN;                 // else: the start of the previous tile is complete now
+            const long t = (done_here ? cur.t : cur.t - 1) * BN + lane;
+            const float s = done_here ? sum : prev;
+            if (t >= 0 && t + m <= V && s > best) { best = s; bstart = (int)t; }
+        }
+        prev = sum;
+        if (nxt.v != cur.v) {                                      // the video is finished: one candidate
+            float ms = best;
+            int mt = bstart;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float os = __shfl_xor(ms, o, 64);
+                const int ot = __shfl_xor(mt, o, 64);
+                if (better(os, ot, ms, mt)) { ms = os; mt = ot; }
+            }
+            best = -INFINITY;
+            bstart = SENT_ROW;
+            if (mt != SENT_ROW && ms >= thr) {                     // wave-uniform; a video shorter than the clip has no start
+                if (lane == fill) { cs = ms; cn = (int)(cur.lo + mt); cv = cur.v; }
+                if (++fill == CAP) {
+                    sort64v(cs, cn, cv, lane);
+                    thr = __shfl(cs, k - 1, 64);
+                    if (lane >= k) { cs = -INFINITY; cn = SENT_ROW; cv = -1; }
+                    fill = k;
+                }
+            }
+        }
+        cur = nxt;
+    }
+    sort64v(cs, cn, cv, lane);
+    if (pok && lane < k) {
+        const long o = ((long)blockIdx.y * n_clip + p) * k + lane;
+        part_s[o] = cs;
+        part_n[o] = cn;
+        part_v[o] = cv;
+    }
+}
+
 // ---- one wave per frame row: 64 lanes x 8 channels
 template <typename T> __device__ __forceinline__ f8 ld_row8(const T* p) {
     if constexpr (sizeof(T) == 2) return ld8(p); else return ld8f(p);
@@ -1164,6 +1324,28 @@ int seq_topk_launch(const void* Tq, const void* Vn, long Qt, long N, const int* 
                        (const int*)nullptr, 0, (const long*)nullptr, (float*)nullptr, 0L);
     TAN_LAUNCH_CHECK();
     hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(n_seq, 4)), dim3(256), 0, st, part_s, part_n, n_seq, k, ns, top_s, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ws: the splits' lists (score, row, video); the splits are the sequence sweep's
+template <typename T>
+int clip_topk_launch(const void* Tq, const void* Vn, long Qt, long N, const int* c_off, long n_clip, const int* v_off, int n_videos, int k,
+                     int splits, float* top_s, int* top_n, int* top_v, void* ws, hipStream_t st, const float* q_scale = nullptr,
+                     const float* v_scale = nullptr) {
+    long rps;
+    const int ns = n_seq_splits(n_clip, N, splits, &rps);
+    float* part_s = (float*)ws;
+    int* part_n = (int*)(part_s + (long)ns * n_clip * k);
+    int* part_v = part_n + (long)ns * n_clip * k;
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)clip_kernel<T>, seq_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((clip_kernel<T>), dim3(cdiv(n_clip, 4), (unsigned)ns), dim3(256), seq_lds<T>(), st, (const T*)Tq, (const T*)Vn, Qt,
+                       N, c_off, (int)n_clip, v_off, n_videos, k, rps, q_scale, v_scale, part_s, part_n, part_v);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(n_clip, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, n_clip, k, ns,
+                       top_s, top_n, top_v);
     TAN_LAUNCH_CHECK();
     return 0;
 }
@@ -1695,6 +1877,37 @@ extern "C" int tan_sequence_scores_e4m3(const void* Tq, const float* q_scale, co
                                         int C, const int* s_off, long n_seq, const int* v_off, long n_videos, const int* hits,
                                         const long* x_off, long P, float* x, long n_x, void* stream) {
     return sequence_scores(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, s_off, n_seq, v_off, n_videos, hits, x_off, P, x, n_x, stream);
+}
+
+extern "C" long tan_clip_topk_ws_bytes(long n_clip, long N, int k) {
+    if (n_clip < 1 || n_clip >= (1L << 29) || N < 1 || N >= (1L << 31) || k < 1 || k > KMAX) return TAN_ERR_BAD_ARG;
+    return max_splits(N) * n_clip * k * 12;
+}
+
+static int clip_topk(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+              const int* c_off, long n_clip, const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_row,
+              int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && c_off && v_off && top_score && top_row && top_video && ws &&
+                (uintptr_t)ws % 16 == 0);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_clip, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0);
+    return by_format(fmt, [&](auto r) {
+        return clip_topk_launch<typename decltype(r)::type>(Tq, Vn, Qt, N, c_off, n_clip, v_off, (int)n_videos, k, splits, top_score,
+                                                            top_row, top_video, ws, (hipStream_t)stream, q_scale, v_scale);
+    });
+}
+
+extern "C" int tan_clip_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* c_off, long n_clip,
+                             const int* v_off, long n_videos, int k, int splits, float* top_score, int* top_row, int* top_video,
+                             void* ws, void* stream) {
+    return clip_topk(dtype, Tq, nullptr, Vn, nullptr, Qt, N, C, c_off, n_clip, v_off, n_videos, k, splits, top_score, top_row, top_video,
+                     ws, stream);
+}
+
+extern "C" int tan_clip_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                                  const int* c_off, long n_clip, const int* v_off, long n_videos, int k, int splits, float* top_score,
+                                  int* top_row, int* top_video, void* ws, void* stream) {
+    return clip_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, c_off, n_clip, v_off, n_videos, k, splits, top_score, top_row,
+                     top_video, ws, stream);
 }
 
 static int label_topk(int fmt, const void* Tl, const float* l_scale, const void* Vn, const float* v_scale, long L, long N, int C, int k,

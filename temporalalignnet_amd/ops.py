@@ -653,6 +653,31 @@ def sequence_scores(tq, vn, s_off, v_off, hits, x_off, x, *, q_scale=None, v_sca
     return x
 
 
+def clip_topk_ws_bytes(n_clip, N, k):
+    n = _lib.lib().tan_clip_topk_ws_bytes(n_clip, N, k)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_clip_topk_ws_bytes({n_clip}, {N}, {k}): bad argument")
+    return n
+
+
+def clip_topk(tq, vn, c_off, v_off, k, *, q_scale=None, v_scale=None, splits=0, check_offsets=False, out=None, ws=None):
+    """The k videos in which each CLIP appears best second for second (tan_clip_topk / _e4m3; the match is defined in
+    include/tan_hip.h): tq [Qt, 512] holds the clips' rows one after the other, c_off [n_clip + 1] int32 (device) each clip's first
+    row, then Qt (1 to 32 rows each); vn / v_off / q_scale / v_scale as for `rank_topk_video`.
+    Returns (top_score [n_clip, k] f32: the SUM of the clip's scores along the best diagonal, top_row [n_clip, k] int32: the index
+    row where that diagonal starts, top_video [n_clip, k] int32), by descending score, equal scores by ascending row; when fewer
+    than k videos are as long as the clip, the tail is (-inf, 0x7fffffff, -1).  splits: 0 = automatic; the result does not depend
+    on it.  check_offsets: verify c_off and v_off on the host (one synchronisation); otherwise they are the caller's contract.
+    out / ws: caller-owned outputs (the same 3-tuple) and scratch (uint8, >= clip_topk_ws_bytes) instead of fresh ones."""
+    _sequence_args("clip_topk", tq, vn, c_off, v_off, q_scale, v_scale, check_offsets)
+    Qt, N, nc, nv, dev = tq.shape[0], vn.shape[0], c_off.numel() - 1, v_off.numel() - 1, tq.device
+    top_s, top_r, top_v = _lists(nc, k, dev, video=True) if out is None else out
+    ws = _scratch(ws, _lib.lib().tan_clip_topk_ws_bytes(nc, N, k), dev)
+    _call("clip_topk", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(c_off), nc, _ptr(v_off), nv, k, splits, _f32(top_s),
+          _ptr(top_r), _ptr(top_v), _ptr(ws))
+    return top_s, top_r, top_v
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

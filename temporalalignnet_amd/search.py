@@ -38,6 +38,10 @@ sentence is ranked against all of it:
     of every video show?  `tan_label_topk` keeps a tile of index rows resident and streams the LABEL matrix past it, so every row's
     k best labels come out of one launch without scratch; `Annotation.segments` turns the best labels into (video, start, end,
     label) runs on the device (`tan_label_runs`) and `Annotation.label_seconds` counts the seconds of every label (`annotate`).
+  * `search_clips`: the questions that start from VIDEO -- "where else does this clip appear?" (re-uploads, compilations), "more
+    like these twenty seconds".  A clip is up to 32 index rows (seconds of an indexed video, or rows of a freshly indexed one);
+    `tan_clip_topk` lays it over every video second for second -- a diagonal sum over the same matrix-free score tile -- and keeps
+    per clip the k videos with the best placement and where it starts (`similar`; no model is loaded).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -49,6 +53,7 @@ sentence is ranked against all of it:
     python -m temporalalignnet_amd.search merge --out I.npz I0.npz I1.npz ...
     python -m temporalalignnet_amd.search annotate --checkpoint C --vocab s3d_dict.npy --index I.npz --labels steps.txt [-k K]
         [--threshold X] [--min-len M] [--per-second] --out segments.csv
+    python -m temporalalignnet_amd.search similar --index I.npz [--shard I1.npz ...] [--host-resident] --clip VID:10-29 [-k K] [--keep-source]
 """
 from __future__ import annotations
 
@@ -74,7 +79,12 @@ SequenceHit = namedtuple("SequenceHit", ("vid", "seconds", "score"))
 # one hit of `search_rerank`: the video, the second / cosine / softmax confidence / alignability logit (None without the head) of the
 # joint encoder on the window around the dual encoder's best second, and that second and its dual score
 Reranked = namedtuple("Reranked", ("vid", "second", "score", "confidence", "alignability", "dual_second", "dual_score"))
-RERANK_TEXT_SLOTS = 8           # a rerank window holds one sentence; `align_corpus` pads the text side to multiples of 8
+# one hit of `search_clips`: the video, the first / last second (inclusive) of the clip's best placement in it, and the mean score
+# per second along that placement
+ClipHit = namedtuple("ClipHit", ("vid", "start", "end", "score"))
+MAX_CLIP_SECONDS = 32           # a clip's rows are one wave's 32 resident query columns (tan_clip_topk)
+EMPTY_ROW = 0x7fffffff          # the row of an empty top-k slot (include/tan_hip.h)
+RERANK_TEXT_SLOTS = 8         # a rerank window holds one sentence; `align_corpus` pads the text side to multiples of 8
 
 
 def _is_e4m3(dtype):
@@ -754,6 +764,140 @@ def _sequence_seconds(tq, feat, s_off, v_off_dev, v_off, m, seq, video, scales):
     return ts, first
 
 
+def clip_spans(index, clips):
+    """The host half of `clip_features`: every clip checked, [(m, source)] with source = (global video number, first second) for a
+    (vid, first, last) clip and None for a tensor of rows.  A vid string names the FIRST video that carries it; an int is a video
+    number.  ValueError: an unknown vid, first > last, seconds outside the video, m outside [1, 32], a tensor that is not a float
+    [m, 512].  Needs no device."""
+    by_name = None
+    out = []
+    for c, clip in enumerate(clips):
+        if isinstance(clip, torch.Tensor):
+            if clip.dim() != 2 or clip.shape[1] != 512 or not clip.is_floating_point():
+                raise ValueError(f"clip {c}: a tensor clip holds float index-style rows [m, 512], not {tuple(clip.shape)} {clip.dtype}")
+            m, source = int(clip.shape[0]), None
+        else:
+            try:
+                vid, first, last = clip
+                first, last = int(first), int(last)
+            except (TypeError, ValueError):
+                raise ValueError(f"clip {c}: (vid, first_second, last_second) or a tensor [m, 512]") from None
+            if isinstance(vid, str):
+                if by_name is None:
+                    by_name = {}
+                    for v, s in enumerate(index.vids):
+                        by_name.setdefault(s, v)
+                v = by_name.get(vid)
+            else:
+                v = int(vid) if isinstance(vid, (int, np.integer)) and 0 <= int(vid) < len(index.vids) else None
+            if v is None:
+                raise ValueError(f"clip {c}: no video {vid!r} in the index")
+            vlen = int(index.v_off[v + 1] - index.v_off[v])
+            if first > last:
+                raise ValueError(f"clip {c}: first second {first} > last second {last}")
+            if first < 0 or last >= vlen:
+                raise ValueError(f"clip {c}: seconds {first}..{last} lie outside video {vid!r} of {vlen} seconds")
+            m, source = last - first + 1, (v, first)
+        if not 1 <= m <= MAX_CLIP_SECONDS:
+            raise ValueError(f"clip {c}: {m} seconds; a clip holds 1 to {MAX_CLIP_SECONDS} (cut a longer one into pieces)")
+        out.append((m, source))
+    return out
+
+
+def _index_rows(index, lo, hi, dev):
+    """The global rows [lo, hi) of ONE video of either kind of index as f32 on `dev`, from whichever shard holds them
+    (host-resident included); e4m3 rows dequantised (code value x power-of-two scale: exact)."""
+    s = int(np.searchsorted(index.row_base, lo, side="right")) - 1
+    sh, a, b = index.shards[s], lo - int(index.row_base[s]), hi - int(index.row_base[s])
+    rows = sh.feat[a:b].to(dev)
+    if sh.scale is None:
+        return rows.float()
+    lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(dev)
+    return lut[rows.long()] * sh.scale[a:b].to(dev)[:, None]
+
+
+@torch.no_grad()
+def clip_features(index, clips):
+    """The query side of `search_clips`: (rows, c_off).  Each clip is (vid, first, last) -- the seconds first..last, inclusive, of a
+    video OF THIS INDEX (a `VideoIndex` or a `ShardedIndex`; see `clip_spans` for how a vid is resolved) -- or a float tensor
+    [m, 512] of index-style rows, e.g. `build_index(model, [video]).feat[a:b]`; 1 <= m <= 32.  The rows are L2-normalised in f32 and
+    then cast to the index's row dtype or quantised (`ops.quantize_rows_e4m3`), exactly as `query_features` treats text: rows
+    [Qt, 512] in the index's dtype, for an e4m3 index (codes uint8 [Qt, 512], scale f32 [Qt]).  c_off [n_clip + 1] int32 on the
+    device: each clip's first row, then Qt.  ValueError as `clip_spans` raises it, before anything touches the device."""
+    clips = list(clips)
+    spans = clip_spans(index, clips)
+    if not clips:
+        raise ValueError("clip_features: no clips")
+    dev = index.device
+    parts = []
+    for clip, (m, source) in zip(clips, spans):
+        if source is None:
+            parts.append(clip.to(dev).float())
+        else:
+            lo = int(index.v_off[source[0]]) + source[1]
+            parts.append(_index_rows(index, lo, lo + m, dev))
+    t = torch.cat(parts, 0).contiguous()
+    t = ops.l2norm_fwd(t, torch.empty_like(t), None, t.shape[0], 512)
+    c_off = torch.from_numpy(np.concatenate([[0], np.cumsum([m for m, _ in spans])]).astype(np.int32)).to(dev)
+    if index.e4m3:
+        return ops.quantize_rows_e4m3(t), c_off
+    return (t if index.row_dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.row_dtype, device=dev))), c_off
+
+
+def drop_source(entries, source, k):
+    """`search_clips(exclude_source=True)` on the host: entries = one clip's hits, best first, out of a sweep asked for k + 1, each a
+    tuple whose first element is the hit's global video number; source = the clip's own video number, or None for a tensor clip.
+    The source is removed where it is listed, otherwise the list is cut to k: the order is total, so either way these are the k
+    best of the other videos."""
+    if source is not None:
+        kept = [e for e in entries if e[0] != source]
+        if len(kept) < len(entries):
+            return kept
+    return entries[:k]
+
+
+@torch.no_grad()
+def search_clips(index, clips, k=10, splits=0, exclude_source=False):
+    """Video to video: per CLIP (see `clip_features`: (vid, first, last) of this index, or a tensor [m, 512]; 1 to 32 seconds) the
+    videos of the corpus in which it appears best SECOND FOR SECOND, and where: [[ClipHit(vid, start, end, score)]] per clip, by
+    descending score (equal scores by index row).  [start, end] are seconds of the hit's video, inclusive, end = start + m - 1: the
+    placement of the clip with the largest summed score (`tan_clip_topk`; the smallest such start), and score is that sum / m --
+    the mean stitched dual cosine per second, `search`'s score, so / 0.07 gives the mean logit.  Unlike `search_sequences` the
+    seconds advance in lockstep: a video that merely holds the clip's best second once scores one good second out of m.
+    k is clamped to the number of videos and must lie in [1, 32]; a video shorter than the clip cannot hold it, so a list is SHORTER
+    than k when fewer videos are long enough.  exclude_source: leave out the video a (vid, first, last) clip was cut from (a tensor
+    clip has none); the sweep is asked for k + 1, so k <= 31.
+    `index`: a `VideoIndex`, or a `ShardedIndex` -- one sweep and one `tan_topk_fold` per shard, exactly what `VideoIndex.concat`
+    of its shards gives.  One read-back.  There is no `restrict=` here: a `RowFilter` is not taken by this call (a placement needs
+    consecutive rows of its video, and whole-video filters for this sweep are not built)."""
+    clips = list(clips)
+    if not clips:
+        return []
+    spans = clip_spans(index, clips)
+    k = min(int(k), len(index.vids))
+    kk = min(k + 1, len(index.vids)) if exclude_source else k
+    if not 1 <= k <= kk <= 32:
+        raise ValueError("search_clips: k must lie in [1, 32], and in [1, 31] with exclude_source")
+    tq, c_off = clip_features(index, clips)
+    sweep = _Sweep(index, tq, splits=splits)
+    top = _TopLists(index, len(clips), kk, 1)
+    for s, feat, scale, v_off in index.shard_views():
+        top.add(s, ops.clip_topk(sweep.tq, feat, c_off, v_off, min(kk, v_off.numel() - 1), splits=splits, **sweep.scales(scale)))
+    score, shard, (row, video) = top.read()                                # shard-local; an empty slot has row 0x7fffffff
+    out = []
+    for p, (m, source) in enumerate(spans):
+        entries = []
+        for i in range(kk):
+            if row[p, i] == EMPTY_ROW:
+                break                                                      # empty slots sort last
+            s, v = int(shard[p, i]), int(video[p, i])
+            entries.append((int(index.video_base[s]) + v, int(row[p, i] - index.shards[s].v_off[v]), float(score[p, i])))
+        if exclude_source:
+            entries = drop_source(entries, None if source is None else source[0], k)
+        out.append([ClipHit(index.vids[gv], start, start + m - 1, S / m) for gv, start, S in entries])
+    return out
+
+
 def rerank_window(sec, vlen, seq_len=64):
     """(s0, t): the window `search_rerank` gives a candidate whose best dual second is `sec` in a video of `vlen` seconds -- seq_len
     seconds centred on `sec` (sec - seq_len // 2 first), moved inside the video where it would stick out, the whole video when it is
@@ -1039,6 +1183,16 @@ def _parser():
     p.add_argument("--within", action="append", default=None, metavar="VID:FIRST-LAST",
                    help="search this video only between these seconds, inclusive (repeatable; other videos stay whole)")
     p.add_argument("sentences", nargs="+")
+    p = sub.add_parser("similar", help="where else in the corpus a piece of an indexed video appears (no checkpoint, no model)")
+    p.add_argument("--index", required=True)
+    p.add_argument("--shard", action="append", default=None, metavar="PATH",
+                   help="a further index file searched together with --index, in the order given (repeatable)")
+    p.add_argument("--host-resident", action="store_true",
+                   help="keep the rows in pinned host memory and stream them through the card: for an index larger than the card")
+    p.add_argument("--clip", action="append", required=True, metavar="VID:FIRST-LAST",
+                   help=f"these seconds of this video of the index, inclusive, at most {MAX_CLIP_SECONDS} (repeatable)")
+    p.add_argument("-k", type=int, default=10)
+    p.add_argument("--keep-source", action="store_true", help="also list the video the clip was cut from (left out by default)")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
@@ -1085,15 +1239,28 @@ def parse_args(argv=None):
             a.within = None if a.within is None else [parse_within(w) for w in a.within]
         except ValueError as e:
             ap.error(str(e))
+    if a.cmd == "similar":
+        if not 1 <= a.k <= (32 if a.keep_source else 31):
+            ap.error("-k must lie in [1, 31], or [1, 32] with --keep-source")
+        try:
+            a.clip = [parse_within(c, "--clip") for c in a.clip]
+        except ValueError as e:
+            ap.error(str(e))
+        for vid, first, last in a.clip:
+            if first > last:
+                ap.error(f"--clip {vid}:{first}-{last}: FIRST is after LAST")
+            if last - first + 1 > MAX_CLIP_SECONDS:
+                ap.error(f"--clip {vid}:{first}-{last} holds {last - first + 1} seconds; cut it into clips of at most "
+                         f"{MAX_CLIP_SECONDS} seconds")
     return a
 
 
-def parse_within(text):
+def parse_within(text, option="--within"):
     """'VID:FIRST-LAST' -> (vid, first, last); the vid may hold colons itself"""
     vid, sep, span = text.rpartition(":")
     first, dash, last = span.partition("-")
     if not sep or not vid or not dash or not first.isdigit() or not last.isdigit():
-        raise ValueError(f"--within takes VID:FIRST-LAST (seconds, inclusive), not {text!r}")
+        raise ValueError(f"{option} takes VID:FIRST-LAST (seconds, inclusive), not {text!r}")
     return vid, int(first), int(last)
 
 
@@ -1111,12 +1278,30 @@ def restrict_from_args(index, a):
     return index.restrict(videos=only if (a.only is not None or a.only_file) else None, exclude=exclude or None, windows=a.within)
 
 
+def _load_index(a):
+    """--index [--shard ...] [--host-resident] -> a `VideoIndex` or a `ShardedIndex`"""
+    if a.shard or a.host_resident:
+        return ShardedIndex.load([a.index] + (a.shard or []), resident="host" if a.host_resident else "device")
+    return VideoIndex.load(a.index)
+
+
 def main(argv=None):
     a = parse_args(argv)
     if a.cmd == "merge":
         idx = VideoIndex.concat([VideoIndex.load(p, device="cpu") for p in a.inputs])
         idx.save(a.out)
         print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos from {len(a.inputs)} files", file=sys.stderr)
+        return 0
+    if a.cmd == "similar":
+        idx = _load_index(a)
+        try:
+            found = search_clips(idx, a.clip, a.k, exclude_source=not a.keep_source)
+        except ValueError as e:
+            print(f"similar: {e}", file=sys.stderr)
+            return 2
+        for hits in found:
+            for h in hits:
+                print(f"{h.vid}\t{h.start}\t{h.end}\t{h.score:.6f}")
         return 0
     from .infer_align import build_aligner, make_embed_text, read_corpus
     vocab = np.load(a.vocab)
@@ -1130,10 +1315,7 @@ def main(argv=None):
         return 0
     from .word2vec_model import Word2VecTokenizer
     embed = make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab))
-    if a.shard or a.host_resident:
-        idx = ShardedIndex.load([a.index] + (a.shard or []), resident="host" if a.host_resident else "device")
-    else:
-        idx = VideoIndex.load(a.index)
+    idx = _load_index(a)
     if a.cmd == "annotate":
         ann = annotate(idx, model, embed, _read_vids(a.labels), a.k)
         with open(a.out, "w", newline="") as f:

@@ -4,6 +4,7 @@ process, device events around each call, caller-owned outputs and scratch.  Prin
     python tools/search_bench.py [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE] [--moments]
     python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --rerank [--rows 4194304] [--queries 1 64] [--pool 32] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py --clips [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --shards [8] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --restrict [--parent-lib PARENT.so] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--out FILE]
     python tools/search_bench.py --annotate [--parent-lib PARENT.so] --rows 1048576 [--labels 128 1024 8192] [--out FILE]
@@ -22,6 +23,10 @@ same loads and MFMA loop, so the ratio is what the video epilogue and the row ->
 32 x 32 (random unit steps), bf16 and e4m3.  The yardsticks, in the same run on the same rows with Q = n_seq * m queries, are
 `ops.rank_topk_video` (the video sweep) and `ops.rank_topk` (the row sweep).  `finish_ms` is `ops.sequence_scores` plus
 `ops.monotonic_decode` for the n_seq * k winners (tables made once, outside the timing).
+
+--clips times `ops.clip_topk` INSTEAD, on the same layout and for the same n_clip x m cases (random unit rows as the clips), bf16 and
+e4m3.  The yardsticks, in the same run on the same rows, are `ops.sequence_topk` (the same frame with the scan epilogue) and
+`ops.rank_topk` with Q = n_clip * m queries (the row sweep: the same loads and MFMAs); the three alternate call by call.
 
 --rerank times the stages of `search.search_rerank` INSTEAD, on the "corpus" layout over a bf16 index with a bf16 stem store (random
 rows) and a randomly initialised 6 + 6 layer model with the alignability head, bf16: `dual_ms` (`ops.rank_topk_video`, k = pool),
@@ -170,6 +175,40 @@ def sequences_table(N, k, idx_of, a):
     return rows
 
 
+def clips_table(N, k, idx_of, a):
+    """idx_of(q f32 [Q, 512]) -> {format: (tq, vn, scale keywords)}"""
+    v_off = video_layouts(N)["corpus"]
+    nv = v_off.numel() - 1
+    kk = min(k, nv)
+    rows = []
+    for n_clip, m in SEQ_CASES:
+        Q = n_clip * m
+        c_off = torch.arange(0, Q + 1, m, dtype=torch.int32, device="cuda")
+        for fmt, (tq, vn, kw) in idx_of(unit_rows(Q, (1 << 30) + Q)).items():
+            out = (torch.empty(n_clip, kk, device="cuda"), torch.empty(n_clip, kk, dtype=torch.int32, device="cuda"),
+                   torch.empty(n_clip, kk, dtype=torch.int32, device="cuda"))
+            ws = torch.empty(ops.clip_topk_ws_bytes(n_clip, N, kk), dtype=torch.uint8, device="cuda")
+            sout = (torch.empty(n_clip, kk, device="cuda"), torch.empty(n_clip, kk, dtype=torch.int32, device="cuda"))
+            sws = torch.empty(ops.sequence_topk_ws_bytes(n_clip, N, kk), dtype=torch.uint8, device="cuda")
+            rout = (None, None, torch.empty(Q, kk, device="cuda"), torch.empty(Q, kk, dtype=torch.int32, device="cuda"))
+            rws = torch.empty(ops.rank_topk_ws_bytes(Q, N, kk), dtype=torch.uint8, device="cuda")
+
+            def rows_sweep():
+                if kw:
+                    ops.rank_topk_e4m3(tq, kw["q_scale"], vn, kw["v_scale"], None, kk, out=rout, ws=rws)
+                else:
+                    ops.rank_topk(tq, vn, None, kk, out=rout, ws=rws)
+            tc, ts, tr = timed_round((lambda: ops.clip_topk(tq, vn, c_off, v_off, kk, out=out, ws=ws, **kw),
+                                      lambda: ops.sequence_topk(tq, vn, c_off, v_off, kk, out=sout, ws=sws, **kw), rows_sweep),
+                                     a.warmup, a.reps)
+            # a placement is one of the order-preserving paths and a rounded add is monotone: the j-th best match never exceeds the j-th best path
+            below = bool((out[0] <= sout[0]).all())
+            rows.append({"n_clip": n_clip, "m": m, "fmt": fmt, "Q": Q, "videos": nv, "k": kk, "clip_ms": round(tc, 4),
+                         "sequence_ms": round(ts, 4), "row_sweep_ms": round(tr, 4), "clip_over_seq": round(tc / ts, 3),
+                         "clip_over_rows": round(tc / tr, 3), "match_le_path": below})
+    return rows
+
+
 def shards_table(N, k, v16, v8, s8, a):
     """One row per (format, Q): the single sweep, S device-resident shards, S host-resident shards, the fold alone, a plain pinned
     copy of the same bytes."""
@@ -252,6 +291,23 @@ def timed_pair(fa, fb, warmup, reps):
             b.synchronize()
             acc.append(a.elapsed_time(b))
     return float(np.median(ms[0])), float(np.median(ms[1]))
+
+
+def timed_round(fns, warmup, reps):
+    """`timed_pair` for any number of routines: their median ms, the routines alternating call by call (A B C A B C ...)"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    ms = [[] for _ in fns]
+    for _ in range(reps):
+        for fn, acc in zip(fns, ms):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            acc.append(a.elapsed_time(b))
+    return [float(np.median(x)) for x in ms]
 
 
 def parent_sweep(path):
@@ -494,6 +550,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--moments", action="store_true", help="also time rank_topk_video and moment_extent (see the module docstring)")
     ap.add_argument("--sequences", action="store_true", help="time sequence_topk against the video and row sweeps instead (see the module docstring)")
+    ap.add_argument("--clips", action="store_true", help="time clip_topk against sequence_topk and the row sweep instead (see the module docstring)")
     ap.add_argument("--rerank", action="store_true", help="time the stages of search_rerank instead (see the module docstring)")
     ap.add_argument("--pool", type=int, default=32)
     ap.add_argument("--shards", type=int, nargs="?", const=8, default=0, metavar="S",
@@ -588,6 +645,24 @@ def main():
                 fh.write(" ".join(f"{c:>18}" for c in cols) + "\n")
                 for r in rows:
                     fh.write(" ".join(f"{str(r[c]):>18}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
+    if a.clips:
+        def idx_of(q):
+            q8, qs8 = ops.quantize_rows_e4m3(q)
+            return {"bf16": (q.to(torch.bfloat16), v16, {}), "e4m3": (q8, v8, dict(q_scale=qs8, v_scale=s8))}
+        rows = clips_table(N, k, idx_of, a)
+        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "clips": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --clips --rows {N} -k {k}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
+                fh.write("# clip_topk against sequence_topk (the same clips as sequences) and rank_topk with Q = n_clip * m queries, same run, "
+                         "same rows\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>14}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>14}" for c in cols) + "\n")
         print(json.dumps(res))
         return
     if a.sequences:

@@ -46,7 +46,7 @@ Padding (attn_cases.keypad_sets: a different pattern per video, every pattern th
 scattered keys, the whole leading 32 / 96 / 128 keys (a wave's block, the mid forward's first chunk: m = -inf carries over, the
 long kernels' first block), the whole second 32 / 96 / 128, every key but the last, every key (next to live videos).
 NOT covered: attn_fwd_kernel<bf16_t>, attn_bwd_dq_kernel<bf16_t>, attn_bwd_dkv_kernel<bf16_t> -- long_path() is constant true, so no
-call reaches them.  tan_attnblk.hip has its own file (test_attnblk_gpu.py).
+call reaches them.  tan_attnblk.hip has its own files (test_attnblk_fp64_gpu.py, test_attnblk_gpu.py).
 
 Measured on an MI355X (worst observed / bound over every case; test_report_worst_ratios prints them):
                      f32      short    mid      long

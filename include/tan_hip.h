@@ -493,6 +493,16 @@ typedef struct tan_encoder_desc {
     /* optional, both directions: scratch [8, R, C] f32 -- with it, stacks of few row panels (R / 64 <= TAN_SPLIT_PANELS, default 48)
      * run the MLP branch through tan_mlp_fwd_split / tan_mlp_bwd_split */
     float* split_part;
+    /* forward only, optional: the forward in TWO VIDEO GROUPS.  The stack's forward is row-local per video (one attention workgroup per
+     * video, one MLP workgroup per 64-row panel, the LayerNorms inside both), so videos [0, fwd_group_videos) run the whole layer loop
+     * on the call's stream and videos [fwd_group_videos, B) the same launches -- every per-row / per-video pointer advanced, B and the
+     * row count reduced -- on fwd_group_stream, which is made to wait for the call's stream first and which the call's stream waits for
+     * before tan_encoder_fwd returns: everything is ordered on the call's stream as without groups, and every result is bit-identical.
+     * Two half-size launch chains per stack instead of one: when a launch ends, another chain's next launch takes the CUs (DESIGN.md
+     * section 3.7).  Taken only where the whole-panel launches run (bf16, C = 512, the fused attention branch's L, images bound, not
+     * the split-hidden path), 0 < fwd_group_videos < B and both groups' rows are multiples of 64; anything else -- NULL / 0 included
+     * -- is the ungrouped forward, launch for launch. */
+    void* fwd_group_stream; int fwd_group_videos;
 } tan_encoder_desc;
 int tan_encoder_fwd(const tan_encoder_desc* e, void* stream);
 int tan_encoder_bwd(const tan_encoder_desc* e, void* stream);

@@ -174,8 +174,8 @@ static long split_bwd_panels() {
     return n;
 }
 
-extern "C" int tan_encoder_fwd(const tan_encoder_desc* e, void* st) {
-    TAN_REQUIRE(e && e->layers > 0 && e->params && e->bufs && e->x0);
+// the layer loop of tan_encoder_fwd over all e->B videos on one stream
+static int encoder_fwd_run(const tan_encoder_desc* e, void* st) {
     const int dt = e->dtype, C = e->C, H = e->H;
     const long R = (long)e->B * e->L;
     const void* x_in = e->x0;
@@ -236,6 +236,76 @@ extern "C" int tan_encoder_fwd(const tan_encoder_desc* e, void* st) {
     if (e->post_out && !ln1_done)
         CK(tan_layernorm_fwd(x_in, e->post_g, e->post_b, e->post_out, e->post_mean, e->post_rstd, nullptr, 0, R, C, 1e-5f, dt, st));
     return 0;
+}
+
+// The forward in two video groups (tan_encoder_desc.fwd_group_stream): `e` restricted to the videos [v0, v0 + nb).  Per video: L rows of
+// every [R, n * C] activation and [R] statistic, H * L entries of lse [B, H, L] (tan_attn.hip: ((b * H + h) * L + t)), L mask bytes.
+constexpr int FWD_GROUP_MAX_LAYERS = 16;
+
+static void videos_slice(const tan_encoder_desc& e, int v0, int nb, tan_encoder_desc& out, tan_layer_bufs* bufs) {
+    const long r0 = (long)v0 * e.L, C = e.C;
+    const size_t esz = e.dtype == TAN_F32 ? 4 : 2;
+    auto act = [&](auto* p, long width) { return p ? (decltype(p))((char*)p + (size_t)(r0 * width) * esz) : p; };      // NULL (no_save) stays NULL
+    auto vec = [](float* p, long off) { return p ? p + off : p; };
+    out = e;
+    out.B = nb;
+    out.key_padding_mask = e.key_padding_mask ? e.key_padding_mask + r0 : nullptr;
+    out.x0 = act(e.x0, C);
+    out.post_out = act(e.post_out, C);
+    out.post_mean = vec(e.post_mean, r0); out.post_rstd = vec(e.post_rstd, r0);
+    for (int i = 0; i < e.layers; ++i) {
+        const tan_layer_bufs& b = e.bufs[i];
+        tan_layer_bufs& o = bufs[i];
+        o.xn1 = act(b.xn1, C); o.qkv = act(b.qkv, 3 * C); o.attn_o = act(b.attn_o, C); o.x_mid = act(b.x_mid, C); o.xn2 = act(b.xn2, C);
+        o.h_pre = act(b.h_pre, 4 * C); o.h_act = act(b.h_act, 4 * C); o.x_out = act(b.x_out, C);
+        o.mean1 = vec(b.mean1, r0); o.rstd1 = vec(b.rstd1, r0); o.mean2 = vec(b.mean2, r0); o.rstd2 = vec(b.rstd2, r0);
+        o.lse = vec(b.lse, (long)v0 * e.H * e.L);
+    }
+    out.bufs = bufs;
+    out.split_part = nullptr;                 // (the whole stack is past the split-hidden range: so are its halves)
+    out.fwd_group_stream = nullptr; out.fwd_group_videos = 0;
+}
+
+// whether the forward of `e` may run as the two groups [0, g) and [g, B): only the whole-panel launches (one attention workgroup per
+// video, one MLP workgroup per 64-row panel) are issued, and both groups are whole panels
+static bool fwd_groups_ok(const tan_encoder_desc* e, void* st) {
+    const int g = e->fwd_group_videos;
+    if (!e->fwd_group_stream || e->fwd_group_stream == st || g <= 0 || g >= e->B || e->layers > FWD_GROUP_MAX_LAYERS) return false;
+    const long R = (long)e->B * e->L;
+    const bool panel_ok = panel_enabled() && e->dtype == TAN_BF16 && e->C == 512 && R % 64 == 0;
+    const bool attn_panel_ok = panel_enabled() && tan_attnblk_supported(e->L, e->C, e->H, e->dtype);
+    const bool split = panel_ok && e->split_part && R / 64 <= split_panels();
+    if (!panel_ok || !attn_panel_ok || split) return false;
+    if (((long)g * e->L) % 64 != 0 || ((long)(e->B - g) * e->L) % 64 != 0) return false;
+    for (int i = 0; i < e->layers; ++i) {
+        const tan_layer_params& p = e->params[i];
+        if (!p.wp_qkv || !p.wp_out || !p.wp_fc || !p.wp_proj) return false;
+    }
+    return true;
+}
+
+extern "C" int tan_encoder_fwd(const tan_encoder_desc* e, void* st) {
+    TAN_REQUIRE(e && e->layers > 0 && e->params && e->bufs && e->x0);
+    if (!fwd_groups_ok(e, st)) return encoder_fwd_run(e, st);
+    const hipStream_t s0 = (hipStream_t)st, s1 = (hipStream_t)e->fwd_group_stream;
+    static thread_local hipEvent_t ev_fork = nullptr, ev_join = nullptr;      // (the two stacks are issued from two host threads)
+    if (!ev_fork) {
+        if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return -3;
+        if (hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) != hipSuccess) return -3;
+    }
+    const int g = e->fwd_group_videos;
+    tan_encoder_desc d0, d1;
+    tan_layer_bufs b0[FWD_GROUP_MAX_LAYERS], b1[FWD_GROUP_MAX_LAYERS];
+    videos_slice(*e, 0, g, d0, b0);
+    videos_slice(*e, g, e->B - g, d1, b1);
+    if (hipEventRecord(ev_fork, s0) != hipSuccess) return -3;
+    if (hipStreamWaitEvent(s1, ev_fork, 0) != hipSuccess) return -3;
+    const int rc0 = encoder_fwd_run(&d0, s0);
+    const int rc1 = encoder_fwd_run(&d1, s1);
+    // joined whatever the launches returned: nothing stays on the group stream that the call's stream does not wait for
+    if (hipEventRecord(ev_join, s1) != hipSuccess) return -3;
+    if (hipStreamWaitEvent(s0, ev_join, 0) != hipSuccess) return -3;
+    return rc0 ? rc0 : rc1;
 }
 
 // d_stage[s] (may be NULL = no gradient) is the gradient w.r.t. deep-supervision stage s; parameter gradients are

@@ -95,11 +95,25 @@ class _AlignerEngine(_WorkspaceMixin):
         d.split_part = _vp(getattr(er, "split_part", None))
         return d
 
-    def _encoder_fwd(self, er, x0, keypad, post_name, save=False, xn1_ready=False):
+    def _fwd_group_videos(self, B, L):
+        """Videos in group 0 of a stack's forward in two video groups (tan_encoder_desc.fwd_group_videos), 0 = one group: half the
+        batch, rounded down to whole 64-row panels.  Only from 128 row panels up (`fwd_groups` None; True: the library's own
+        eligibility alone, False: never): below that the two stacks do not oversubscribe the 256 CUs, and streaming each block's
+        4 MiB of weights a second time is pure cost."""
+        mode = getattr(self, "fwd_groups", None)
+        if mode is False or (mode is None and B * L < 128 * 64):
+            return 0
+        gran = 64 // np.gcd(L, 64)               # videos per whole panel boundary
+        return int(B // 2 // gran * gran)
+
+    def _encoder_fwd(self, er, x0, keypad, post_name, save=False, xn1_ready=False, group_stream=None):
         d = self._enc_desc(er, x0, keypad, post_name)
         self._flat.join_images()
         d.no_save = 0 if save else 1         # no backward will follow: the tensors kept only for it are not written
         d.xn1_ready = 1 if xn1_ready else 0  # tan_embed_fwd already wrote the first block's ln_1 output
+        g = self._fwd_group_videos(er.B, er.L) if group_stream is not None else 0
+        if g > 0:                            # videos [g, B) on `group_stream`, forked from and joined to the current stream inside the call
+            d.fwd_group_stream, d.fwd_group_videos = C.c_void_p(group_stream.cuda_stream), g
         _lib.check(_lib.lib().tan_encoder_fwd(C.byref(d), ops._stream()), "tan_encoder_fwd")
 
     def _layer_events(self, prefix, layers):
@@ -397,21 +411,22 @@ class _AlignerEngine(_WorkspaceMixin):
                 return fn()
         return self._issuer.submit(run)
 
-    def _run_video_stack(self, x0, vmask_u8, B, T, save=False, er=None):
-        """`er`: a workspace whose first block's ln_1 output tan_embed_fwd has already written (the fused front-end)."""
+    def _run_video_stack(self, x0, vmask_u8, B, T, save=False, er=None, group_stream=None):
+        """`er`: a workspace whose first block's ln_1 output tan_embed_fwd has already written (the fused front-end).
+        `group_stream`: the stream of the second video group of the forward (`_encoder_fwd`)."""
         ready = er is not None
         if er is None:
             er = self._take_ws("video_temporal_encoder", self.num_encoder_layers, B, T, x0.dtype, x0.device)
-        self._encoder_fwd(er, x0, vmask_u8, "ln_video_post_enc", save, xn1_ready=ready)
+        self._encoder_fwd(er, x0, vmask_u8, "ln_video_post_enc", save, xn1_ready=ready, group_stream=group_stream)
         return er
 
-    def _run_joint_stack(self, x0, text_t, vmask_u8, tmask_u8, B, T, N, save=False, pre=None):
+    def _run_joint_stack(self, x0, text_t, vmask_u8, tmask_u8, B, T, N, save=False, pre=None, group_stream=None):
         """`pre` = (er, xj, keypad) from the fused front-end: the joint input, its key-padding mask and the first ln_1 are done."""
         cd, dev = (x0 if pre is None else pre[1]).dtype, (x0 if pre is None else pre[1]).device
         L = T + N
         if pre is not None:
             er, xj, keypad = pre
-            self._encoder_fwd(er, xj, keypad, "ln_joint_post_enc", save, xn1_ready=True)
+            self._encoder_fwd(er, xj, keypad, "ln_joint_post_enc", save, xn1_ready=True, group_stream=group_stream)
             er.xj, er.keypad = xj, keypad
             return er
         xj = torch.empty(B * L, WIDTH, dtype=cd, device=dev)
@@ -424,7 +439,7 @@ class _AlignerEngine(_WorkspaceMixin):
             tm = tmask_u8 if tmask_u8 is not None else torch.zeros(B, N, dtype=torch.uint8, device=dev)
             keypad = torch.cat([vm, tm], dim=1).contiguous()
         er = self._take_ws("joint_temporal_encoder", self.num_decoder_layers, B, L, cd, dev)
-        self._encoder_fwd(er, xj, keypad, "ln_joint_post_enc", save)
+        self._encoder_fwd(er, xj, keypad, "ln_joint_post_enc", save, group_stream=group_stream)
         er.xj, er.keypad = xj, keypad
         return er
 
@@ -750,6 +765,13 @@ class _AlignerEngine(_WorkspaceMixin):
         # so the weight gradients stay on the chains; the bucket all-reduces are issued by the hook, from THIS thread, video first
         hook = self._grad_ready_hook
         dw_j, dw_v = (None, None) if hook is not None else (aux_j, aux_v)
+        # Each stack's forward runs as two video groups (`_fwd_group_videos`, tan_encoder_desc.fwd_group_stream): four chains of half-size
+        # launches instead of two, so that a launch that ends hands its CUs to another chain's next launch.  The second groups ride the
+        # same two role streams -- the process has four hardware queues, a fifth stream would share one with a chain -- which at this point
+        # hold what the stack's forward has to be behind anyway (the previous step's last weight gradients and the optimizer launch of
+        # the stack's matrices) and the loss's mask preparation.  Stage 1 only: stage 2 issues its agreement targets on the loss stream
+        # from the other host thread while the joint stack's forward is being enqueued (`chain_step.Stage2Step.targets`).
+        grp_j, grp_v = (None, None) if (serial or pre is not None) else (aux_j, aux_v)
         # (Measured in round 5 and not kept: the optimizer launch of a stack's UPPER layers -- whose weight gradients ride the chain -- on a
         #  third stream as soon as the lowest of them is differentiated.  The step's boundary shrinks by 0.07 ms and the backward grows by
         #  as much: 4.290 vs 4.271 ms, ABBA x2 of 60 steps.  HBM-bound launches next to the stacks' kernels cost what they save.)
@@ -765,7 +787,8 @@ class _AlignerEngine(_WorkspaceMixin):
                     torch.cuda.current_stream().wait_event(prev["joint"])
                 if pre is not None:
                     pre["joint"]()
-                ej = self._run_joint_stack(None, None, vmask_u8, tmask_u8, B, T, N, True, pre=(fe["ej"], fe["xj"], fe["keypad"]))
+                ej = self._run_joint_stack(None, None, vmask_u8, tmask_u8, B, T, N, True, pre=(fe["ej"], fe["xj"], fe["keypad"]),
+                                           group_stream=grp_j)
                 stages = [ej.stage(s) for s in range(Sd)]
                 dj = [dst_j[s] for s in range(Sd)]
                 if zero_ev is not None:            # (the gradient fill: over long before; a family may add to parameter gradients itself)
@@ -783,7 +806,7 @@ class _AlignerEngine(_WorkspaceMixin):
                 main.wait_event(prev["video"])
             if pre is not None:
                 pre["video"]()
-            ev = self._run_video_stack(fe["x0"], vmask_u8, B, T, True, er=fe["ev"])
+            ev = self._run_video_stack(fe["x0"], vmask_u8, B, T, True, er=fe["ev"], group_stream=grp_v)
             dv = [dst_v[s] for s in range(Se)]
             if zero_ev is not None:
                 main.wait_event(zero_ev)

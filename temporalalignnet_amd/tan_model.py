@@ -107,6 +107,7 @@ class TemporalAligner(_AlignerEngine, nn.Module):
         self._ws_lock = threading.Lock()
         self.overlap_stacks = True        # run the video and joint stacks on two HIP streams
         self.serialize_streams = False    # measurement: the two-chain step with every stream collapsed onto the current one
+        self.fwd_groups = None            # the two-chain step's stack forwards in two video groups: None = from 128 row panels up, True / False = always / never
         self._side = None
         self._issuer = None               # helper thread issuing the side-stream stack (see _on_side)
         self._lp_cache = {}

@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -1088,6 +1088,35 @@ long tan_label_runs_ws_bytes(long N);
 int tan_label_runs(const float* top_score, const int* top_label, int stride, long N, long L, const int* v_off, long n_videos,
                    float threshold, int min_len, long cap, int* n_runs, int* run_video, int* run_start, int* run_end, int* run_label,
                    int* run_peak_row, float* run_peak_score, int* label_rows, void* ws, void* stream);
+
+/* ---- temporally consistent labels: a per-video Viterbi decode over tan_label_topk's lists (`Annotation.decode`) ----
+ * tan_label_decode: top_score f32 / top_label int32 [N, k] as tan_label_topk writes them, 1 <= k <= 32, 1 <= N < 2^31; v_off
+ *   [n_videos + 1] as in tan_label_runs; threshold finite; switch_penalty in [0, +inf], not NaN.
+ *   STATES of row t: j = 0 .. k-1 is list position j, with lab(t, j) = top_label[t, j] and gain(t, j) = top_score[t, j] - threshold
+ *   (one f32 subtract), or -inf if the score is not finite (NaN, +-inf); state k is BACKGROUND, lab = -1 and gain = 0.
+ *   OBJECTIVE, per video: over the paths s_t, maximise  sum_t gain(t, s_t) - switch_penalty * #{t >= 1 : lab(t, s_t) != lab(t-1,
+ *   s_{t-1})}.  Staying on a label across a second where it scores below the threshold costs that second's negative gain; leaving
+ *   and coming back costs two penalties.  A label that is not in a row's list is NOT AVAILABLE at that row -- a path cannot stay
+ *   on it there -- so decode lists of k >= 5: with k = 1 only the best label or background can be chosen and nothing is bridged
+ *   through a second whose best label is another one.
+ *   ARITHMETIC, in this order, every operation one f32 add, subtract, max or compare (nothing to contract), so the result is
+ *   defined bit for bit:   d[0][j] = gain(0, j).   For t >= 1:  m = max_i d[t-1][i],  a = the smallest i attaining it,
+ *   rel[i] = d[t-1][i] - m;  for state j, i* = the smallest i with lab(t-1, i) == lab(t, j) (background always has one: k);
+ *   if i* exists and rel[i*] >= -switch_penalty:  c = rel[i*], bp[t][j] = i*;  otherwise  c = -switch_penalty, bp[t][j] = a;
+ *   d[t][j] = c + gain(t, j).   Subtracting m every step keeps d within a few units of 0 whatever the video's length.  The last
+ *   row's state is the smallest j attaining max_j d; the walk back follows bp.  Videos do not interact.
+ *   OUTPUTS: dec_label int32 [N]: the chosen state's label, -1 for background; dec_score f32 [N]: the chosen list entry's
+ *   top_score, -inf for background.  A bridged second keeps its label with its own score, which is below the threshold.
+ *   ws: tan_label_decode_ws_bytes(N, k) bytes -- N * (k + 1) back-pointer bytes plus alignment; any alignment of ws -- (-1 for
+ *   sizes outside 1 <= N < 2^31, 1 <= k <= 32).  One launch: one wave per video (four per workgroup), sequential in time inside
+ *   a video, so ONE very long video is one wave's serial chain -- the launch takes as long as its longest video.  No atomics:
+ *   bit-identical from run to run and independent of the launch geometry.  Duplicate labels inside one row's list, or a v_off
+ *   that breaks its contract, are the CALLER's error: indices are clamped, nothing is read or written out of bounds, and the
+ *   result is then unspecified (so it is for gains that overflow f32).  A NULL pointer, k or sizes out of range, n_videos outside
+ *   [1, N], a threshold that is not finite, a NaN or negative penalty: TAN_ERR_BAD_ARG, nothing launched.                         */
+long tan_label_decode_ws_bytes(long N, int k);
+int tan_label_decode(const float* top_score, const int* top_label, int k, long N, const int* v_off, long n_videos, float threshold,
+                     float switch_penalty, int* dec_label, float* dec_score, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ hand-written HIP kernel in libtan_hip.so.  All wrappers require CUDA(HIP) tensor
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -581,6 +582,47 @@ def label_runs(top_score, top_label, L, v_off, threshold, min_len=1, *, cap=None
     _lib.check(lib.tan_label_runs(_f32(top_score), _ptr(top_label), stride, N, int(L), _ptr(v_off), nv, threshold, min_len, cap,
                                   _ptr(n_runs), *col, _ptr(counts), _ptr(ws), _stream()), "tan_label_runs")
     return n_runs, runs, peak, counts
+
+
+def label_decode_ws_bytes(N, k):
+    n = _lib.lib().tan_label_decode_ws_bytes(N, k)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_label_decode_ws_bytes({N}, {k}): bad argument")
+    return n
+
+
+def label_decode(top_score, top_label, v_off, threshold, switch, *, out=None, ws=None):
+    """Temporally consistent labels from `label_topk`'s lists: a Viterbi decode per video (tan_label_decode; the exact definition
+    is in include/tan_hip.h).  top_score f32 / top_label int32 [N, k], 1 <= k <= 32; v_off [n_videos + 1] int32 (device).  A path
+    gains score - threshold per second on a list entry, 0 on background, and pays `switch` (in [0, +inf]) wherever its label
+    changes; threshold is finite.  Returns (dec_label int32 [N]: the chosen label or -1 for background, dec_score f32 [N]: its
+    list score or -inf), on the device, nothing read back.  out: caller-owned (dec_label, dec_score) instead of fresh ones;
+    ws: scratch (uint8, >= label_decode_ws_bytes(N, k))."""
+    if top_score.dim() != 2 or top_score.shape != top_label.shape or top_score.dtype != torch.float32 \
+            or top_label.dtype != torch.int32 or not top_score.is_contiguous() or not top_label.is_contiguous():
+        raise ValueError("label_decode: top_score f32 and top_label int32 are contiguous [N, k]")
+    N, k = top_score.shape
+    if v_off.dtype != torch.int32 or v_off.dim() != 1 or v_off.numel() < 2 or not v_off.is_contiguous():
+        raise ValueError("label_decode: v_off is int32 [n_videos + 1], contiguous")
+    nv, dev = v_off.numel() - 1, top_score.device
+    threshold, switch = float(threshold), float(switch)
+    if N < 1 or not 1 <= k <= 32 or not 1 <= nv <= N or not math.isfinite(threshold) or not switch >= 0:
+        raise ValueError("label_decode: N >= 1, 1 <= k <= 32, 1 <= n_videos <= N, threshold finite, switch in [0, +inf]")
+    if out is None:
+        out = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.float32, device=dev))
+    dec_l, dec_s = out
+    if dec_l.dtype != torch.int32 or dec_s.dtype != torch.float32 or dec_l.shape != (N,) or dec_s.shape != (N,) \
+            or not dec_l.is_contiguous() or not dec_s.is_contiguous():
+        raise ValueError("label_decode: out is (dec_label int32 [N], dec_score f32 [N]), contiguous")
+    lib = _lib.lib()
+    need = lib.tan_label_decode_ws_bytes(N, k)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("label_decode: ws is uint8 of at least label_decode_ws_bytes(N, k) bytes")
+    _lib.check(lib.tan_label_decode(_f32(top_score), _ptr(top_label), k, N, _ptr(v_off), nv, threshold, switch, _ptr(dec_l), _f32(dec_s),
+                                    _ptr(ws), _stream()), "tan_label_decode")
+    return dec_l, dec_s
 
 
 def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scale=None, v_scale=None, out=None):

@@ -38,6 +38,9 @@ sentence is ranked against all of it:
     of every video show?  `tan_label_topk` keeps a tile of index rows resident and streams the LABEL matrix past it, so every row's
     k best labels come out of one launch without scratch; `Annotation.segments` turns the best labels into (video, start, end,
     label) runs on the device (`tan_label_runs`) and `Annotation.label_seconds` counts the seconds of every label (`annotate`).
+    Neighbouring seconds score almost alike, so the best label flickers; `Annotation.decode` (`tan_label_decode`) is a per-video
+    Viterbi decode over the kept lists that pays a penalty per label change, and `segments(..., switch=)` builds its runs from
+    the decoded labels (`annotate --smooth PENALTY`).
   * `search_clips`: the questions that start from VIDEO -- "where else does this clip appear?" (re-uploads, compilations), "more
     like these twenty seconds".  A clip is up to 32 index rows (seconds of an indexed video, or rows of a freshly indexed one);
     `tan_clip_topk` lays it over every video second for second -- a diagonal sum over the same matrix-free score tile -- and keeps
@@ -52,7 +55,7 @@ sentence is ranked against all of it:
     python -m temporalalignnet_amd.search query ... --only VID --only-file vids.txt --exclude VID --within VID:30-90 "crack two eggs" ...
     python -m temporalalignnet_amd.search merge --out I.npz I0.npz I1.npz ...
     python -m temporalalignnet_amd.search annotate --checkpoint C --vocab s3d_dict.npy --index I.npz --labels steps.txt [-k K]
-        [--threshold X] [--min-len M] [--per-second] --out segments.csv
+        [--threshold X] [--min-len M] [--smooth PENALTY] [--per-second] --out segments.csv
     python -m temporalalignnet_amd.search similar --index I.npz [--shard I1.npz ...] [--host-resident] --clip VID:10-29 [-k K] [--keep-source]
 """
 from __future__ import annotations
@@ -1021,7 +1024,8 @@ class Annotation:
                       row n holds its k best labels by descending score, equal scores by ascending label number
       labels          the label texts; label[n, j] numbers them
       v_off / vids    the index's: int64 [n_videos + 1], each video's first row, and the videos' names
-    `segments` and `label_seconds` read column 0 only: the best label of every second."""
+    `segments` and `label_seconds` read column 0 only: the best label of every second -- or, with `switch=`, the labels of
+    `decode`, which may be any of a second's k labels: annotate with k >= 5 when decoding."""
 
     def __init__(self, label, score, labels, v_off, vids):
         self.label, self.score, self.labels = label, score, list(labels)
@@ -1056,23 +1060,55 @@ class Annotation:
         return [(self.vids[video[i]], int(start[i] - first[i]), int(end[i] - first[i]), self.labels[label[i]],
                  int(peak_row[i] - first[i]), float(peak_score[i])) for i in range(len(video))]
 
-    def segments(self, threshold, min_len=1):
+    def _check_switch(self, threshold, switch):
+        if not np.isfinite(threshold):
+            raise ValueError("Annotation: decoding needs a finite threshold")
+        if not float(switch) >= 0:
+            raise ValueError("Annotation: switch must lie in [0, +inf]")
+        if len(self) >= 2 ** 31:
+            raise ValueError("Annotation: 2^31 rows or more; annotate the shards one by one")
+
+    def decode(self, threshold, switch):
+        """(label int32 [N], score f32 [N]) on the device: per video, the sequence of labels -- each one of its second's k kept
+        labels, or -1 for background -- that maximises the sum of (score - threshold) over the labelled seconds minus `switch`
+        per change of label (`tan_label_decode`; the exact definition is in include/tan_hip.h).  score is the chosen label's own
+        score at that second (below the threshold where the path bridges a dip), -inf for background.  switch = 0 is the per-second
+        choice; switch = +inf gives one label, or background, per video.  A label outside a second's list cannot be chosen
+        there.  One launch, nothing read back."""
+        self._check_switch(threshold, switch)
+        return ops.label_decode(self.score, self.label, self._v_off_device(), threshold, switch)
+
+    def _decoded_lists(self, threshold, switch):
+        """`decode`'s columns as [N, 1] lists for `tan_label_runs`, with the threshold that makes exactly the -inf rows background"""
+        label, score = self.decode(threshold, switch)
+        return score[:, None], label[:, None], float(np.finfo(np.float32).min)
+
+    def segments(self, threshold, min_len=1, switch=None):
         """[(vid, start_second, end_second, label_text, peak_second, peak_score)] in index order: the maximal runs of seconds of one
         video whose best label is the same and scores >= threshold (a second below it, or with a NaN score, is background), at
         least min_len seconds long; seconds are the video's own, inclusive; the peak is the run's largest score and the first
-        second that attains it.  Neighbouring runs are not bridged.  One `tan_label_runs` launch and one read-back."""
+        second that attains it.  Neighbouring runs are not bridged.  One `tan_label_runs` launch and one read-back.
+        switch (a penalty in [0, +inf]; threshold finite): the runs of `decode`'s labels instead -- a run then keeps the seconds
+        the path bridged, which score below the threshold, and may hold labels that were not a second's best one."""
         self._check(threshold, min_len)
         cap = max(len(self) // int(min_len), 1)                        # a kept run holds at least min_len rows
-        n_runs, runs, peak, _ = ops.label_runs(self.score, self.label, len(self.labels), self._v_off_device(), threshold, min_len, cap=cap)
+        score, label = self.score, self.label
+        if switch is not None:
+            score, label, threshold = self._decoded_lists(threshold, switch)
+        n_runs, runs, peak, _ = ops.label_runs(score, label, len(self.labels), self._v_off_device(), threshold, min_len, cap=cap)
         back = torch.cat((n_runs[:1], runs.reshape(-1), peak.view(torch.int32))).cpu().numpy()
         n = int(back[0])
         return self.runs_to_segments(back[1:1 + 5 * cap].reshape(5, cap)[:, :n], back[1 + 5 * cap:].view(np.float32)[:n])
 
-    def label_seconds(self, threshold):
+    def label_seconds(self, threshold, switch=None):
         """{label_text: seconds}: how many seconds of the corpus show each label as their best one with a score >= threshold
-        (labels nobody shows included, equal texts added up).  One `tan_label_runs` launch and one read-back."""
+        (labels nobody shows included, equal texts added up).  One `tan_label_runs` launch and one read-back.
+        switch: count the seconds of `decode`'s labels instead (threshold finite)."""
         self._check(threshold)
-        counts = ops.label_runs(self.score, self.label, len(self.labels), self._v_off_device(), threshold, 1, cap=0, label_rows=True)[3]
+        score, label = self.score, self.label
+        if switch is not None:
+            score, label, threshold = self._decoded_lists(threshold, switch)
+        counts = ops.label_runs(score, label, len(self.labels), self._v_off_device(), threshold, 1, cap=0, label_rows=True)[3]
         out = {}
         for text, c in zip(self.labels, counts.cpu().numpy()):
             out[text] = out.get(text, 0) + int(c)
@@ -1161,6 +1197,9 @@ def _parser():
     p.add_argument("--threshold", type=float, default=None,
                    help="a second whose best score is below this is background (default: none is)")
     p.add_argument("--min-len", type=int, default=None, help="drop segments shorter than this many seconds (default 1)")
+    p.add_argument("--smooth", type=float, default=None, metavar="PENALTY",
+                   help="decode every video's labels with this penalty per label change (>= 0; needs a finite --threshold, "
+                        "use -k 5 or more): segments bridge short dips and flickers")
     p.add_argument("--per-second", action="store_true", help="write vid,second,label,score for the k labels of every second instead")
     p.add_argument("--out", required=True, metavar="CSV", help="vid,start,end,label,peak,score: one row per segment")
     p = sub.choices["query"]
@@ -1229,6 +1268,13 @@ def parse_args(argv=None):
             ap.error("--threshold must not be NaN")
         if a.min_len is not None and a.min_len < 1:
             ap.error("--min-len must be >= 1")
+        if a.smooth is not None:
+            if a.per_second:
+                ap.error("--smooth does not go with --per-second")
+            if not a.smooth >= 0:
+                ap.error("--smooth must be >= 0")
+            if a.threshold is None or not np.isfinite(a.threshold):
+                ap.error("--smooth needs a finite --threshold")
     if a.cmd == "query":
         filtered = any(x is not None for x in (a.only, a.only_file, a.exclude, a.exclude_file, a.within))
         if filtered and a.sequence:
@@ -1322,7 +1368,7 @@ def main(argv=None):
             if a.per_second:
                 write_per_second_csv(f, ann)
             else:
-                write_segments_csv(f, ann.segments(float("-inf") if a.threshold is None else a.threshold, a.min_len or 1))
+                write_segments_csv(f, ann.segments(float("-inf") if a.threshold is None else a.threshold, a.min_len or 1, switch=a.smooth))
         print(f"{a.out}: {len(ann)} seconds of {len(ann.vids)} videos against {len(ann.labels)} labels", file=sys.stderr)
         return 0
     if a.sequence:

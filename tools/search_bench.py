@@ -51,12 +51,14 @@ the feature: `index_select` of the admitted rows, then the plain sweep over them
 lists have the gathered sweep's scores (bit patterns) and rows.
 
 --annotate times corpus annotation INSTEAD (`ops.label_topk` / `ops.label_topk_e4m3`, then `ops.label_runs` over its lists), bf16 and
-e4m3, for L in --labels and k in 1, 5 (use --rows 1048576): `label_topk_ms` beside `swapped_rank_ms`, what a caller has without the
+e4m3, for L in --labels and k in --annotate-k (default 1, 5; use --rows 1048576): `label_topk_ms` beside `swapped_rank_ms`, what a caller has without the
 entry point -- `ops.rank_topk` with the rows as queries and the labels as the index, over chunks of rows small enough for its scratch
 -- the two alternating call by call; `self_pair_spread`, the same alternation of `label_topk` with itself; `torch_ms` (bf16: `matmul`
 + `topk` over the same chunks); `equals_swapped` / `within_eps`: the lists have route (a)'s bits / scores within 2e-5;
 `swapped_equals_parent`: this build's `rank_topk` gives what --parent-lib's gives on the first chunk; the achieved FLOP rate and the
-label-stream rate it implies; `runs_ms`: `ops.label_runs` at the median best score."""
+label-stream rate it implies; `runs_ms`: `ops.label_runs` at the median best score; `decode_ms`: `ops.label_decode` over the same
+lists at that threshold and a penalty of DECODE_SWITCH, timed after `label_topk` in the same run, beside `decode_stream_ms`, the time
+its own bytes (N k 8 read, N (k + 1) written and read, N 8 written) would take at HBM_COPY_TBS."""
 import argparse
 import json
 import os
@@ -387,6 +389,7 @@ def restrict_table(N, k, v16, v8, s8, a):
 
 ANNOTATE_KS = (1, 5)
 ANNOTATE_CHUNK = 65536            # route (a): rows per roles-swapped rank_topk call; its scratch is (label tiles, at most 256) x chunk x k x 8 bytes
+DECODE_SWITCH, HBM_COPY_TBS = 0.02, 6.29   # the decode's penalty per label change; the measured float4 copy rate (MI355X_MICROARCH)
 BF16_MFMA_PEAK_TF, L2_SHARED_TBS, INF_CACHE_TBS = 2500.0, (16.8, 18.8), 8.6      # MI355X_MICROARCH figures, not measurements of this kernel
 
 
@@ -401,7 +404,7 @@ def annotate_table(N, v16, v8, s8, a):
         for L in a.labels:
             lab = unit_rows(L, (1 << 29) + L)
             tl, ls = (lab.to(torch.bfloat16), None) if vs is None else ops.quantize_rows_e4m3(lab)
-            for k in ANNOTATE_KS:
+            for k in [k for k in a.annotate_k if k <= L]:
                 out = (torch.empty(N, k, device="cuda"), torch.empty(N, k, dtype=torch.int32, device="cuda"))
                 ref = (torch.empty(N, k, device="cuda"), torch.empty(N, k, dtype=torch.int32, device="cuda"))
                 chunk = min(ANNOTATE_CHUNK, N)
@@ -442,6 +445,10 @@ def annotate_table(N, v16, v8, s8, a):
                         torch.empty(cap, device="cuda"), torch.empty(L, dtype=torch.int32, device="cuda"))
                 rws = torch.empty(ops.label_runs_ws_bytes(N), dtype=torch.uint8, device="cuda")
                 t_runs, _ = timed(lambda: ops.label_runs(out[0], out[1], L, v_off, thr, 1, cap=cap, out=runs, ws=rws), a.warmup, a.reps)
+                dec = (torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty(N, device="cuda"))
+                dws = torch.empty(ops.label_decode_ws_bytes(N, k), dtype=torch.uint8, device="cuda")
+                t_dec, _ = timed(lambda: ops.label_decode(out[0], out[1], v_off, thr, DECODE_SWITCH, out=dec, ws=dws), a.warmup, a.reps)
+                dec_bytes = N * k * 8 + 2 * N * (k + 1) + N * 8
                 tflops = 2.0 * N * L * 512 / t_new * 1e-9
                 stream = -(-N // 128) * L * row_bytes / t_new * 1e-9                         # TB/s: every workgroup of 128 rows reads every label once
                 rows.append({"fmt": fmt, "L": L, "k": k, "label_topk_ms": round(t_new, 4), "swapped_rank_ms": round(t_a, 4),
@@ -450,9 +457,10 @@ def annotate_table(N, v16, v8, s8, a):
                              "of_bf16_mfma_peak": round(tflops / BF16_MFMA_PEAK_TF, 4) if vs is None else None,
                              "label_stream_TBps": round(stream, 2), "equals_swapped": same, "within_eps": within,
                              "swapped_equals_parent": same_parent, "runs_ms": round(t_runs, 4), "runs": int(runs[0][0]),
-                             "rows_kept": int(runs[3].sum())})
+                             "rows_kept": int(runs[3].sum()), "decode_ms": round(t_dec, 4),
+                             "decode_stream_ms": round(dec_bytes / HBM_COPY_TBS * 1e-9, 4), "decoded_rows": int((dec[0] >= 0).sum())})
                 print(json.dumps(rows[-1]), file=sys.stderr, flush=True)                      # progress: a row takes seconds
-                del out, ref, ws, runs, rws
+                del out, ref, ws, runs, rws, dec, dws
     return rows
 
 
@@ -561,6 +569,7 @@ def main():
                          "with --annotate: its sweep checks that this build's route (a) is the parent's")
     ap.add_argument("--annotate", action="store_true", help="time label_topk and label_runs instead (see the module docstring)")
     ap.add_argument("--labels", type=int, nargs="+", default=[128, 1024, 8192], help="with --annotate: vocabulary sizes")
+    ap.add_argument("--annotate-k", type=int, nargs="+", default=list(ANNOTATE_KS), help="with --annotate: labels kept per row")
     a = ap.parse_args()
     N, k = a.rows, a.k
     if a.rerank:
@@ -608,7 +617,9 @@ def main():
                          f"of_bf16_mfma_peak against {BF16_MFMA_PEAK_TF / 1000} PF (specification); label_stream = ceil(N / 128) x L x row bytes / "
                          f"time, against {L2_SHARED_TBS[0]}-{L2_SHARED_TBS[1]} TB/s (rows shared by an XCD's workgroups, from L2) and "
                          f"{INF_CACHE_TBS} TB/s (Infinity Cache): figures of the microarchitecture notes the design assumed, not measurements of "
-                         "this kernel; runs = ops.label_runs at the median best score (about half the rows kept)\n")
+                         "this kernel; runs = ops.label_runs at the median best score (about half the rows kept); decode = ops.label_decode over "
+                         f"the same lists at that threshold and penalty {DECODE_SWITCH}, videos of 60 to 1 200 rows, one wave per video; "
+                         f"decode_stream = (N k 8 + 2 N (k + 1) + N 8) bytes at {HBM_COPY_TBS} TB/s\n")
                 cols = list(rows[0])
                 fh.write(" ".join(f"{c:>21}" for c in cols) + "\n")
                 for r in rows:

@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -1117,6 +1117,39 @@ int tan_label_runs(const float* top_score, const int* top_label, int stride, lon
 long tan_label_decode_ws_bytes(long N, int k);
 int tan_label_decode(const float* top_score, const int* top_label, int k, long N, const int* v_off, long n_videos, float threshold,
                      float switch_penalty, int* dec_label, float* dec_score, void* ws, void* stream);
+
+/* ---- copy alignment: the best local alignment of a query's seconds with a video's, re-timed or re-cut (`search.align_spans`) ----
+ * A BLOCK is a row-major [m, V] f32 matrix of scores x[i][j], query second i along the rows, video second j along the columns:
+ * what tan_sequence_scores writes for one hit (a query of more than 32 seconds as consecutive 32-row sequences with consecutive
+ * x_off: a score does not depend on its tile position or query column).  With theta finite, skew in [0, +inf) and
+ * H[-1][*] = H[*][-1] = 0:
+ *     g[i][j] = x[i][j] - theta
+ *     diag = H[i-1][j-1];   up = H[i-1][j] - skew;   left = H[i][j-1] - skew
+ *     P    = max(diag, up, left);   pred = the FIRST of (diag, up, left) that attains P
+ *     H[i][j] = max(0, g[i][j] + P)
+ * Every - and + is one f32 operation, round to nearest, never contracted; every max is exact.  Each cell is therefore a fixed
+ * function of three neighbours: given the bits of x, the result does not depend on traversal order, strip height, slab width or
+ * launch shape.  For a cell with H > 0: if pred is diag and that H is 0 (or lies outside the matrix) the path STARTS here, origin =
+ * (i, j), cells = 1; otherwise origin and cells + 1 are inherited from pred (an up or left that attains P ahead of diag has H > 0).
+ * Per block: best = max H; end = the cell attaining best with the smallest i, then the smallest j; score = best and span =
+ * (a_first, a_last, b_first, b_last, cells) = (origin i, end i, origin j, end j, the end's cells): query seconds a_first .. a_last
+ * shown as video seconds b_first .. b_last.  No positive cell: score = 0, span = (-1, -1, -1, -1, 0).  Inputs are finite.
+ * This is Smith-Waterman in its time-warping form: horizontal and vertical steps are matches too (one query second shown for two
+ * video seconds, or the reverse) and cost skew; an unrelated cell costs theta - x, so a short cut or insertion is bridged and a long
+ * one is not.  tan_sequence_topk / tan_monotonic_decode are global and one-sided; tan_clip_topk is a diagonal of slope one.
+ * tan_local_align: x holds n_x elements; x_off [P] `long` element offsets and table [P, 3] int32 = (m, V, first boundary slot) on
+ *   the device, the slot being the running sum of V over the entries before (slots of different entries must not overlap), sum_V
+ *   the sum over all.  1 <= m <= 4096, 1 <= V < 2^20, m * V < 2^31; score f32 [P], span int32 [P, 5].
+ *   ws: tan_local_align_ws_bytes(P, sum_V) bytes, any alignment: two boundary rows of 16 bytes per slot (the last row of a strip of
+ *   64 query seconds, handed to the next strip), 32 * sum_V + 16; -1 for P or sum_V outside [1, 2^31) or sum_V < P.
+ *   One launch: one wave per block (four per workgroup), the strips of a block one after the other, the anti-diagonals of a strip
+ *   in sequence -- so ONE long pair is one wave's serial chain of about (m / 64) * (V + 63) steps.  No atomics: bit-identical from run
+ *   to run.  A NULL pointer, n_x < 1, P or sum_V out of range, a theta that is not finite, a skew that is negative, infinite or NaN:
+ *   TAN_ERR_BAD_ARG, nothing launched.  A table entry outside the limits, whose block leaves [0, n_x) or whose slots leave
+ *   [0, sum_V) is skipped with the empty result, as tan_sequence_scores skips a bad hit; nothing is read or written out of bounds. */
+long tan_local_align_ws_bytes(long P, long sum_V);
+int tan_local_align(const float* x, long n_x, const long* x_off, const int* table, long P, long sum_V, float theta, float skew,
+                    float* score, int* span, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -625,6 +625,60 @@ def label_decode(top_score, top_label, v_off, threshold, switch, *, out=None, ws
     return dec_l, dec_s
 
 
+def local_align_ws_bytes(P, sum_V):
+    n = _lib.lib().tan_local_align_ws_bytes(P, sum_V)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_local_align_ws_bytes({P}, {sum_V}): bad argument")
+    return n
+
+
+def local_align(x, x_off, table, theta, skew, *, sum_V=None, check_table=False, out=None, ws=None):
+    """The best local alignment of every block of `x` (tan_local_align; the exact definition is in include/tan_hip.h): x f32 [n_x]
+    holds row-major [m, V] blocks of query second x video second scores as `sequence_scores` writes them; x_off int64 [P] each
+    block's first element, table int32 [P, 3] = (m, V, first boundary slot = the running sum of V), both on the device; 1 <= m <=
+    4096, 1 <= V < 2^20.  A cell gains x - theta (theta finite), a step along one axis alone pays `skew` (in [0, +inf)).
+    Returns (score f32 [P], span int32 [P, 5] = (a_first, a_last, b_first, b_last, cells): query seconds a_first .. a_last appear
+    as video seconds b_first .. b_last), on the device, nothing read back; a block without a positive cell, or a table entry that
+    breaks the limits, gives (0, (-1, -1, -1, -1, 0)).  sum_V: the number of boundary slots, the sum of the table's V; the caller
+    built the table and knows it -- without it the wrapper reads the table's last entry back (slot + V: one synchronisation).
+    check_table: verify on the host (one synchronisation) that the slots are the running sum of V, so no two entries share one --
+    otherwise that is the caller's contract: overlapping slots stay in bounds but give wrong results for strips beyond the first.
+    out: caller-owned (score, span) instead of fresh ones; ws: scratch (uint8, >= local_align_ws_bytes(P, sum_V))."""
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError("local_align: x is f32 [n_x], contiguous, n_x >= 1")
+    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
+        raise ValueError("local_align: x_off is int64 [P], contiguous, P >= 1")
+    P, dev = x_off.numel(), x.device
+    if table.dtype != torch.int32 or table.shape != (P, 3) or not table.is_contiguous():
+        raise ValueError("local_align: table is int32 [P, 3] = (m, V, first boundary slot), contiguous")
+    theta, skew = float(theta), float(skew)
+    if not math.isfinite(theta) or not (skew >= 0 and math.isfinite(skew)):
+        raise ValueError("local_align: theta finite, skew in [0, +inf)")
+    if check_table or sum_V is None:
+        t = table.cpu().long()
+        if check_table and (int(t[0, 2]) != 0 or bool((t[:, 1] < 1).any()) or not torch.equal(t[1:, 2], torch.cumsum(t[:, 1], 0)[:-1])):
+            raise ValueError("local_align: the table's third column is the running sum of its V (from 0, every V >= 1)")
+        sum_V = int(t[-1, 1] + t[-1, 2]) if sum_V is None else sum_V
+    sum_V = int(sum_V)
+    if not P <= sum_V < 2 ** 31:
+        raise ValueError("local_align: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
+    if out is None:
+        out = (torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, 5, dtype=torch.int32, device=dev))
+    score, span = out
+    if score.dtype != torch.float32 or span.dtype != torch.int32 or score.shape != (P,) or span.shape != (P, 5) \
+            or not score.is_contiguous() or not span.is_contiguous():
+        raise ValueError("local_align: out is (score f32 [P], span int32 [P, 5]), contiguous")
+    lib = _lib.lib()
+    need = lib.tan_local_align_ws_bytes(P, sum_V)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("local_align: ws is uint8 of at least local_align_ws_bytes(P, sum_V) bytes")
+    _lib.check(lib.tan_local_align(_f32(x), x.numel(), _ptr(x_off), _ptr(table), P, sum_V, theta, skew, _f32(score), _ptr(span), _ptr(ws),
+                                   _stream()), "tan_local_align")
+    return score, span
+
+
 def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scale=None, v_scale=None, out=None):
     """(start, end) int32 [Q, k]: for every hit of `rank_topk_video`'s lists, the contiguous run of index rows around top_row,
     inside the hit's video, whose score is >= top_score - width -- global rows, inclusive (tan_moment_extent / _e4m3; the exact

@@ -45,6 +45,11 @@ sentence is ranked against all of it:
     like these twenty seconds".  A clip is up to 32 index rows (seconds of an indexed video, or rows of a freshly indexed one);
     `tan_clip_topk` lays it over every video second for second -- a diagonal sum over the same matrix-free score tile -- and keeps
     per clip the k videos with the best placement and where it starts (`similar`; no model is loaded).
+  * `align_spans` / `search_copies`: the second stage of clip search, for a copy that was re-timed or re-cut.  A query of up to
+    4096 seconds and a video give one [m, V] block of scores (`tan_sequence_scores`, the query as 32-row pieces), and
+    `tan_local_align` finds the best LOCAL alignment in it -- steps along either axis allowed at a price, unrelated cells bridged
+    at a price -- with its extent in both videos.  `search_copies` proposes the candidate videos by one `tan_clip_topk` sweep over
+    the query's pieces and ranks them by that alignment (`similar --align`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -57,6 +62,7 @@ sentence is ranked against all of it:
     python -m temporalalignnet_amd.search annotate --checkpoint C --vocab s3d_dict.npy --index I.npz --labels steps.txt [-k K]
         [--threshold X] [--min-len M] [--smooth PENALTY] [--per-second] --out segments.csv
     python -m temporalalignnet_amd.search similar --index I.npz [--shard I1.npz ...] [--host-resident] --clip VID:10-29 [-k K] [--keep-source]
+    python -m temporalalignnet_amd.search similar --index I.npz --clip VID:0-599 --align --threshold X [--skew Y] [--pool P] [--piece S] [-k K]
 """
 from __future__ import annotations
 
@@ -86,6 +92,12 @@ Reranked = namedtuple("Reranked", ("vid", "second", "score", "confidence", "alig
 # per second along that placement
 ClipHit = namedtuple("ClipHit", ("vid", "start", "end", "score"))
 MAX_CLIP_SECONDS = 32           # a clip's rows are one wave's 32 resident query columns (tan_clip_topk)
+# one hit of `align_spans` / `search_copies`: the video, the first / last second (inclusive) of the copy in it, the first / last
+# second of the QUERY that the copy shows, the alignment's score (the sum of score - threshold over its cells, minus skew per step
+# along one axis alone) and the number of its cells
+CopyHit = namedtuple("CopyHit", ("vid", "start", "end", "q_start", "q_end", "score", "cells"))
+MAX_ALIGN_SECONDS = 4096        # a query of `align_spans`: 12 bits of tan_local_align's packed origin
+PIECE_ROWS = 32                 # `align_spans` hands a query to tan_sequence_scores as sequences of this many rows
 EMPTY_ROW = 0x7fffffff          # the row of an empty top-k slot (include/tan_hip.h)
 RERANK_TEXT_SLOTS = 8         # a rerank window holds one sentence; `align_corpus` pads the text side to multiples of 8
 
@@ -767,12 +779,23 @@ def _sequence_seconds(tq, feat, s_off, v_off_dev, v_off, m, seq, video, scales):
     return ts, first
 
 
-def clip_spans(index, clips):
+def _video_number(index, vid, by_name):
+    """A vid string -> the FIRST video that carries it, an int -> itself; None when the index has no such video.  by_name: a dict the
+    caller keeps between calls (filled on first use)."""
+    if isinstance(vid, str):
+        if not by_name:
+            for v, s in enumerate(index.vids):
+                by_name.setdefault(s, v)
+        return by_name.get(vid)
+    return int(vid) if isinstance(vid, (int, np.integer)) and 0 <= int(vid) < len(index.vids) else None
+
+
+def clip_spans(index, clips, max_seconds=MAX_CLIP_SECONDS):
     """The host half of `clip_features`: every clip checked, [(m, source)] with source = (global video number, first second) for a
     (vid, first, last) clip and None for a tensor of rows.  A vid string names the FIRST video that carries it; an int is a video
-    number.  ValueError: an unknown vid, first > last, seconds outside the video, m outside [1, 32], a tensor that is not a float
-    [m, 512].  Needs no device."""
-    by_name = None
+    number.  ValueError: an unknown vid, first > last, seconds outside the video, m outside [1, max_seconds] (32 for the clip sweep;
+    `align_spans` passes 4096), a tensor that is not a float [m, 512].  Needs no device."""
+    by_name = {}
     out = []
     for c, clip in enumerate(clips):
         if isinstance(clip, torch.Tensor):
@@ -785,14 +808,7 @@ def clip_spans(index, clips):
                 first, last = int(first), int(last)
             except (TypeError, ValueError):
                 raise ValueError(f"clip {c}: (vid, first_second, last_second) or a tensor [m, 512]") from None
-            if isinstance(vid, str):
-                if by_name is None:
-                    by_name = {}
-                    for v, s in enumerate(index.vids):
-                        by_name.setdefault(s, v)
-                v = by_name.get(vid)
-            else:
-                v = int(vid) if isinstance(vid, (int, np.integer)) and 0 <= int(vid) < len(index.vids) else None
+            v = _video_number(index, vid, by_name)
             if v is None:
                 raise ValueError(f"clip {c}: no video {vid!r} in the index")
             vlen = int(index.v_off[v + 1] - index.v_off[v])
@@ -801,8 +817,8 @@ def clip_spans(index, clips):
             if first < 0 or last >= vlen:
                 raise ValueError(f"clip {c}: seconds {first}..{last} lie outside video {vid!r} of {vlen} seconds")
             m, source = last - first + 1, (v, first)
-        if not 1 <= m <= MAX_CLIP_SECONDS:
-            raise ValueError(f"clip {c}: {m} seconds; a clip holds 1 to {MAX_CLIP_SECONDS} (cut a longer one into pieces)")
+        if not 1 <= m <= max_seconds:
+            raise ValueError(f"clip {c}: {m} seconds; a clip holds 1 to {max_seconds} (cut a longer one into pieces)")
         out.append((m, source))
     return out
 
@@ -820,15 +836,16 @@ def _index_rows(index, lo, hi, dev):
 
 
 @torch.no_grad()
-def clip_features(index, clips):
+def clip_features(index, clips, max_seconds=MAX_CLIP_SECONDS):
     """The query side of `search_clips`: (rows, c_off).  Each clip is (vid, first, last) -- the seconds first..last, inclusive, of a
     video OF THIS INDEX (a `VideoIndex` or a `ShardedIndex`; see `clip_spans` for how a vid is resolved) -- or a float tensor
     [m, 512] of index-style rows, e.g. `build_index(model, [video]).feat[a:b]`; 1 <= m <= 32.  The rows are L2-normalised in f32 and
     then cast to the index's row dtype or quantised (`ops.quantize_rows_e4m3`), exactly as `query_features` treats text: rows
     [Qt, 512] in the index's dtype, for an e4m3 index (codes uint8 [Qt, 512], scale f32 [Qt]).  c_off [n_clip + 1] int32 on the
-    device: each clip's first row, then Qt.  ValueError as `clip_spans` raises it, before anything touches the device."""
+    device: each clip's first row, then Qt.  ValueError as `clip_spans` raises it, before anything touches the device.
+    max_seconds: the longest clip taken (`align_spans`: 4096); c_off is tan_clip_topk's only while every clip holds at most 32."""
     clips = list(clips)
-    spans = clip_spans(index, clips)
+    spans = clip_spans(index, clips, max_seconds)
     if not clips:
         raise ValueError("clip_features: no clips")
     dev = index.device
@@ -899,6 +916,173 @@ def search_clips(index, clips, k=10, splits=0, exclude_source=False):
             entries = drop_source(entries, None if source is None else source[0], k)
         out.append([ClipHit(index.vids[gv], start, start + m - 1, S / m) for gv, start, S in entries])
     return out
+
+
+def piece_offsets(ms, piece=PIECE_ROWS):
+    """Queries of ms[q] rows, one after the other, cut into pieces of `piece` rows (each query's last piece shorter): (s_off
+    [n_pieces + 1] int64: every piece's first row, then the total -- tan_sequence_scores' s_off --, first [Q + 1] int64: the number
+    of each query's first piece).  No piece straddles two queries."""
+    ms = np.asarray(ms, dtype=np.int64)
+    n = (ms + piece - 1) // piece
+    first = np.concatenate([[0], np.cumsum(n)])
+    row0 = np.concatenate([[0], np.cumsum(ms)])
+    q_of = np.repeat(np.arange(len(ms)), n)
+    s_off = row0[q_of] + (np.arange(first[-1]) - first[q_of]) * piece
+    return np.concatenate([s_off, row0[-1:]]).astype(np.int64), first.astype(np.int64)
+
+
+def align_tables(ms, Vs, first, videos, piece=PIECE_ROWS):
+    """The tables of P pairs for `ops.sequence_scores` and `ops.local_align`: pair h is a query of ms[h] rows whose pieces are the
+    sequences first[h], first[h] + 1, ... and a video `videos[h]` of Vs[h] rows.  Returns (hits [n, 2] = (sequence, video) per
+    (pair, piece), hit_off [n]: consecutive element offsets, so a pair's pieces fill ONE row-major [m, V] block, x_off [P]: each
+    pair's block, table [P, 3] = (m, V, first boundary slot), n_x, sum_V), all int64."""
+    ms, Vs, first, videos = (np.asarray(a, dtype=np.int64) for a in (ms, Vs, first, videos))
+    x_off = np.concatenate([[0], np.cumsum(ms * Vs)])
+    slot = np.concatenate([[0], np.cumsum(Vs)])
+    n = (ms + piece - 1) // piece
+    pair_of = np.repeat(np.arange(len(ms)), n)
+    a = np.arange(int(n.sum())) - np.concatenate([[0], np.cumsum(n)])[pair_of]           # the piece's number inside its query
+    hits = np.stack((first[pair_of] + a, videos[pair_of]), 1)
+    hit_off = x_off[pair_of] + a * piece * Vs[pair_of]
+    return hits, hit_off, x_off[:-1], np.stack((ms, Vs, slot[:-1]), 1), int(x_off[-1]), int(slot[-1])
+
+
+def _align_prices(what, threshold, skew):
+    threshold, skew = float(threshold), float(skew)
+    if not np.isfinite(threshold) or not (skew >= 0 and np.isfinite(skew)):
+        raise ValueError(f"{what}: threshold must be finite and skew in [0, +inf)")
+    return threshold, skew
+
+
+@torch.no_grad()
+def align_spans(index, pairs, threshold, skew=0.0):
+    """Where, and how much of it, a re-timed or re-cut copy of a query appears in a given video: per pair (query, vid) one
+    CopyHit(vid, start, end, q_start, q_end, score, cells) or None.  `query` is what `clip_features` takes -- (vid, first, last) of
+    this index or a float tensor [m, 512] -- with 1 to 4096 seconds; `vid` a video of this index (a string: the first that carries
+    it; an int: a global video number).  The hit is the best LOCAL alignment of the query's seconds with the video's
+    (`tan_local_align`, defined in include/tan_hip.h): a cell gains score - threshold, with `search`'s score (the stitched dual
+    cosine); a step along one axis alone -- the copy slowed down or sped up -- costs `skew`; a few unrelated seconds are bridged at
+    threshold - score each.  [start, end] are seconds of the video, [q_start, q_end] the seconds OF THE QUERY (0 = its first) they
+    show, both inclusive; cells is the length of the path, score its sum.  None: no second of the pair scores above the threshold.
+    `threshold` has no default: it depends on the features, and nobody has measured it.
+    `index`: a `VideoIndex` or a `ShardedIndex` (host-resident too): the pairs are grouped by the shard that holds their video, a
+    shard without one is not visited, and each visited shard costs one `tan_sequence_scores` and one `tan_local_align`.  One
+    read-back at the end.  The score blocks of a shard's pairs (4 bytes x query seconds x video seconds) are held at once:
+    ValueError from 2^31 elements on -- split the call."""
+    pairs = list(pairs)
+    threshold, skew = _align_prices("align_spans", threshold, skew)
+    if not pairs:
+        return []
+    # every distinct query once: `search_copies` pairs one query with many videos
+    uniq, q_of, seen, by_name, gvs = [], [], {}, {}, []
+    for n, pair in enumerate(pairs):
+        try:
+            query, vid = pair
+        except (TypeError, ValueError):
+            raise ValueError(f"pair {n}: (query, vid)") from None
+        key = id(query) if isinstance(query, torch.Tensor) else query
+        try:
+            at = seen.get(key)
+        except TypeError:                              # an unhashable query: `clip_spans` says what is wrong with it
+            at = None
+        if at is None:
+            at = len(uniq)
+            uniq.append(query)
+            try:
+                seen[key] = at
+            except TypeError:
+                pass
+        q_of.append(at)
+        gv = _video_number(index, vid, by_name)
+        if gv is None:
+            raise ValueError(f"pair {n}: no video {vid!r} in the index")
+        gvs.append(gv)
+    ms = np.array([m for m, _ in clip_spans(index, uniq, MAX_ALIGN_SECONDS)], dtype=np.int64)
+    tq, _ = clip_features(index, uniq, MAX_ALIGN_SECONDS)
+    dev = index.device
+    s_off, first = piece_offsets(ms)
+    s_off_dev = torch.from_numpy(s_off.astype(np.int32)).to(dev)
+    sweep = _Sweep(index, tq)
+    q_of, gvs = np.asarray(q_of, dtype=np.int64), np.asarray(gvs, dtype=np.int64)
+    shard = np.searchsorted(index.video_base, gvs, side="right") - 1
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)          # noqa: E731
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)          # noqa: E731
+    parts = []
+    for s, feat, scale, v_off in index.shard_views([int(s) for s in np.unique(shard)]):
+        at = np.flatnonzero(shard == s)
+        local = gvs[at] - index.video_base[s]
+        sv = index.shards[s].v_off
+        hits, hit_off, x_off, table, n_x, sum_V = align_tables(ms[q_of[at]], sv[local + 1] - sv[local], first[q_of[at]], local)
+        if n_x >= 2 ** 31:
+            raise ValueError("align_spans: the score blocks of one shard's pairs reach 2^31 elements; split the call")
+        x = torch.empty(n_x, dtype=torch.float32, device=dev)
+        ops.sequence_scores(sweep.tq, feat, s_off_dev, v_off, i32(hits), i64(hit_off), x, **sweep.scales(scale))
+        score, span = ops.local_align(x, i64(x_off), i32(table), threshold, skew, sum_V=sum_V)
+        parts.append((at, torch.cat((score.view(torch.int32)[:, None], span), 1)))
+    back = torch.cat([t for _, t in parts]).cpu().numpy()                                      # the one read-back
+    out, a0 = [None] * len(pairs), 0
+    for at, _ in parts:
+        for h, row in zip(at, back[a0:a0 + len(at)]):
+            sc = float(row[:1].view(np.float32)[0])
+            if sc > 0:
+                out[h] = CopyHit(index.vids[gvs[h]], int(row[3]), int(row[4]), int(row[1]), int(row[2]), sc, int(row[5]))
+        a0 += len(at)
+    return out
+
+
+def copy_pieces(m, piece):
+    """A query of m seconds cut into pieces of `piece` seconds, the last one shorter: [(first second, seconds)]"""
+    return [(a, min(piece, m - a)) for a in range(0, m, piece)]
+
+
+@torch.no_grad()
+def search_copies(index, queries, k=10, pool=32, piece=16, *, threshold, skew=0.0, exclude_source=False):
+    """Video to video when the copy was re-timed or re-cut -- slowed down, sped up, seconds cut out or inserted: per QUERY ((vid,
+    first, last) of this index, or a float tensor [m, 512]; 1 to 4096 seconds) the videos that hold the best local alignment with
+    it, [[CopyHit(vid, start, end, q_start, q_end, score, cells)]] by descending score (equal scores by global video number), at
+    most k per query and only hits with a positive score.  See `align_spans` for the hit, `threshold` (no default) and `skew`.
+    Two stages.  Every query is cut into pieces of `piece` seconds (1 to 32, the last piece shorter) and ONE `tan_clip_topk` sweep
+    -- `search_clips`' -- proposes the `pool` (1 to 32) best videos per piece; the union of a query's candidates, without the
+    query's own video when exclude_source is set, goes to `align_spans`.  A copy can only be found if one of its pieces lands in
+    a piece's pool: a shorter piece survives more re-timing but is less specific, a larger pool admits more videos, and both cost
+    sweep time (the sweep grows with the number of pieces) and alignment time (with the candidates).  The defaults piece = 16 and
+    pool = 32 have not been measured on real features.
+    `index`: a `VideoIndex` or a `ShardedIndex`.  Two read-backs: the candidates, then the alignments."""
+    queries = list(queries)
+    threshold, skew = _align_prices("search_copies", threshold, skew)
+    if not queries:
+        return []
+    k, pool, piece = int(k), int(pool), int(piece)
+    if k < 1 or not 1 <= pool <= 32 or not 1 <= piece <= MAX_CLIP_SECONDS:
+        raise ValueError(f"search_copies: k >= 1, pool in [1, 32], piece in [1, {MAX_CLIP_SECONDS}]")
+    spans = clip_spans(index, queries, MAX_ALIGN_SECONDS)
+    clips, q_of = [], []
+    for q, (query, (m, source)) in enumerate(zip(queries, spans)):
+        for a, n in copy_pieces(m, piece):
+            clips.append(query[a:a + n] if source is None else (source[0], source[1] + a, source[1] + a + n - 1))
+            q_of.append(q)
+    kk = min(pool, len(index.vids))
+    tq, c_off = clip_features(index, clips)
+    sweep = _Sweep(index, tq)
+    top = _TopLists(index, len(clips), kk, 1)
+    for s, feat, scale, v_off in index.shard_views():
+        top.add(s, ops.clip_topk(sweep.tq, feat, c_off, v_off, min(kk, v_off.numel() - 1), **sweep.scales(scale)))
+    _, shard, (row, video) = top.read()                                    # read-back 1; an empty slot has row 0x7fffffff
+    cands = [set() for _ in queries]
+    for p, q in enumerate(q_of):
+        held = row[p] != EMPTY_ROW
+        cands[q].update((index.video_base[shard[p][held]] + video[p][held]).tolist())
+    pairs = []
+    for q, (query, (m, source)) in enumerate(zip(queries, spans)):
+        if exclude_source and source is not None:
+            cands[q].discard(source[0])
+        pairs += [(q, gv) for gv in sorted(cands[q])]
+    found = align_spans(index, [(queries[q], gv) for q, gv in pairs], threshold, skew)          # read-back 2
+    out = [[] for _ in queries]
+    for (q, gv), hit in zip(pairs, found):
+        if hit is not None:
+            out[q].append((-hit.score, gv, hit))
+    return [[hit for _, _, hit in sorted(hits, key=lambda e: e[:2])[:k]] for hits in out]
 
 
 def rerank_window(sec, vlen, seq_len=64):
@@ -1232,6 +1416,16 @@ def _parser():
                    help=f"these seconds of this video of the index, inclusive, at most {MAX_CLIP_SECONDS} (repeatable)")
     p.add_argument("-k", type=int, default=10)
     p.add_argument("--keep-source", action="store_true", help="also list the video the clip was cut from (left out by default)")
+    p.add_argument("--align", action="store_true",
+                   help=f"find re-timed or re-cut copies: the best local alignment of the clip (then up to {MAX_ALIGN_SECONDS} seconds) "
+                        "with each candidate video, as `vid start end score q_start q_end cells` (needs --threshold)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="with --align: a second of the alignment gains its score minus this (no default: it depends on the features)")
+    p.add_argument("--skew", type=float, default=None, help="with --align: the price of a step along one video alone, >= 0 (default 0)")
+    p.add_argument("--pool", type=int, default=None, help="with --align: candidate videos per piece, 1 to 32 (default 32)")
+    p.add_argument("--piece", type=int, default=None,
+                   help=f"with --align: the clip is cut into pieces of this many seconds for the candidate sweep, 1 to {MAX_CLIP_SECONDS} "
+                        "(default 16)")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
@@ -1286,7 +1480,20 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error(str(e))
     if a.cmd == "similar":
-        if not 1 <= a.k <= (32 if a.keep_source else 31):
+        if not a.align and any(x is not None for x in (a.threshold, a.skew, a.pool, a.piece)):
+            ap.error("--threshold / --skew / --pool / --piece need --align")
+        if a.align:
+            if a.threshold is None or not np.isfinite(a.threshold):
+                ap.error("--align needs a finite --threshold")
+            if a.skew is not None and not (a.skew >= 0 and np.isfinite(a.skew)):
+                ap.error("--skew must be >= 0 and finite")
+            if a.pool is not None and not 1 <= a.pool <= 32:
+                ap.error("--pool must lie in [1, 32]")
+            if a.piece is not None and not 1 <= a.piece <= MAX_CLIP_SECONDS:
+                ap.error(f"--piece must lie in [1, {MAX_CLIP_SECONDS}]")
+            if a.k < 1:
+                ap.error("-k must be >= 1")
+        elif not 1 <= a.k <= (32 if a.keep_source else 31):
             ap.error("-k must lie in [1, 31], or [1, 32] with --keep-source")
         try:
             a.clip = [parse_within(c, "--clip") for c in a.clip]
@@ -1295,9 +1502,9 @@ def parse_args(argv=None):
         for vid, first, last in a.clip:
             if first > last:
                 ap.error(f"--clip {vid}:{first}-{last}: FIRST is after LAST")
-            if last - first + 1 > MAX_CLIP_SECONDS:
+            if last - first + 1 > (MAX_ALIGN_SECONDS if a.align else MAX_CLIP_SECONDS):
                 ap.error(f"--clip {vid}:{first}-{last} holds {last - first + 1} seconds; cut it into clips of at most "
-                         f"{MAX_CLIP_SECONDS} seconds")
+                         f"{MAX_ALIGN_SECONDS if a.align else MAX_CLIP_SECONDS} seconds")
     return a
 
 
@@ -1341,10 +1548,19 @@ def main(argv=None):
     if a.cmd == "similar":
         idx = _load_index(a)
         try:
-            found = search_clips(idx, a.clip, a.k, exclude_source=not a.keep_source)
+            if a.align:
+                found = search_copies(idx, a.clip, a.k, 32 if a.pool is None else a.pool, 16 if a.piece is None else a.piece,
+                                      threshold=a.threshold, skew=a.skew or 0.0, exclude_source=not a.keep_source)
+            else:
+                found = search_clips(idx, a.clip, a.k, exclude_source=not a.keep_source)
         except ValueError as e:
             print(f"similar: {e}", file=sys.stderr)
             return 2
+        if a.align:
+            for hits in found:
+                for h in hits:
+                    print(f"{h.vid}\t{h.start}\t{h.end}\t{h.score:.6f}\t{h.q_start}\t{h.q_end}\t{h.cells}")
+            return 0
         for hits in found:
             for h in hits:
                 print(f"{h.vid}\t{h.start}\t{h.end}\t{h.score:.6f}")

@@ -5,6 +5,7 @@ process, device events around each call, caller-owned outputs and scratch.  Prin
     python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --rerank [--rows 4194304] [--queries 1 64] [--pool 32] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --clips [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py --copies [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --shards [8] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --restrict [--parent-lib PARENT.so] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--out FILE]
     python tools/search_bench.py --annotate [--parent-lib PARENT.so] --rows 1048576 [--labels 128 1024 8192] [--out FILE]
@@ -27,6 +28,16 @@ same loads and MFMA loop, so the ratio is what the video epilogue and the row ->
 --clips times `ops.clip_topk` INSTEAD, on the same layout and for the same n_clip x m cases (random unit rows as the clips), bf16 and
 e4m3.  The yardsticks, in the same run on the same rows, are `ops.sequence_topk` (the same frame with the scan epilogue) and
 `ops.rank_topk` with Q = n_clip * m queries (the row sweep: the same loads and MFMAs); the three alternate call by call.
+
+--copies times `ops.local_align` INSTEAD: P = 32 and 1024 blocks of 128 x 600 and one block of 1200 x 1200 (scores drawn like the
+cosines of random unit rows, N(0, 1/512), threshold 0.02, skew 0.01), against two yardsticks in the same run, the three alternating
+call by call: `ops.monotonic_decode` over the same blocks (the nearest existing recurrence: global and one-sided) and the host path the
+kernel replaces -- read the blocks back and run the float32 anti-diagonal numpy restatement (imported from tests/align_ref.py, the one
+file of the test tree this tool depends on: the yardstick is the reference the tests pin, not a second copy of it), timed on the host
+clock over the first HOST_BLOCKS blocks and scaled to P where P is larger (`host_scaled`).  `steps` is the kernel's serial chain per
+block, ceil(m / 64) * (V + 63) anti-diagonals, and `ns_per_step` the launch's time over it.  Then, on the 4 Mi-row corpus layout over
+the bf16 index, `search.search_copies` (a 40-second query cut out of the corpus, pool 32, piece 16, threshold 0.4, skew 0.1) beside
+`search.search_clips` (its first 32 seconds), host clock around calls that end in their read-back.
 
 --rerank times the stages of `search.search_rerank` INSTEAD, on the "corpus" layout over a bf16 index with a bf16 stem store (random
 rows) and a randomly initialised 6 + 6 layer model with the alignability head, bf16: `dual_ms` (`ops.rank_topk_video`, k = pool),
@@ -209,6 +220,81 @@ def clips_table(N, k, idx_of, a):
                          "sequence_ms": round(ts, 4), "row_sweep_ms": round(tr, 4), "clip_over_seq": round(tc / ts, 3),
                          "clip_over_rows": round(tc / tr, 3), "match_le_path": below})
     return rows
+
+
+ALIGN_CASES = ((32, 128, 600), (1024, 128, 600), (1, 1200, 1200))
+ALIGN_PRICES = (0.02, 0.01)
+HOST_BLOCKS = 8
+
+
+def copies_table(N, k, v16, a):
+    import time
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import align_ref
+
+    from temporalalignnet_amd import search
+    theta, skew = ALIGN_PRICES
+    i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).cuda()          # noqa: E731
+    rows = []
+    for P, m, V in ALIGN_CASES:
+        x = torch.randn(P * m * V, generator=torch.Generator(device="cuda").manual_seed(P + m), device="cuda") * (512 ** -0.5)
+        x_off = torch.arange(P, dtype=torch.int64, device="cuda") * (m * V)
+        table = i32(np.stack((np.full(P, m), np.full(P, V), np.arange(P) * V), 1))
+        out = (torch.empty(P, device="cuda"), torch.empty(P, 5, dtype=torch.int32, device="cuda"))
+        ws = torch.empty(ops.local_align_ws_bytes(P, P * V), dtype=torch.uint8, device="cuda")
+        # the decode's tables: one "video" per block, its m rows in order
+        hit_of_row = np.repeat(np.arange(P), m)
+        rows_t = i32(np.stack((hit_of_row * m * V + (np.arange(P * m) % m) * V, np.full(P * m, V)), 1))
+        vtab = i32(np.stack((np.arange(P) * m, np.full(P, m), np.arange(P) * V), 1))
+        order = torch.arange(P * m, dtype=torch.int32, device="cuda")
+        bp, run = torch.empty(x.numel(), dtype=torch.int32, device="cuda"), torch.empty(P * V, device="cuda")
+        sec, path = torch.empty(P * m, dtype=torch.int32, device="cuda"), torch.empty(P, device="cuda")
+        n_host = min(P, HOST_BLOCKS)
+        host_ms, host_out = [], []
+
+        def host():
+            t0 = time.perf_counter()
+            back = x.cpu().numpy()
+            t1 = time.perf_counter()
+            host_out[:] = [align_ref.align(back[h * m * V:(h + 1) * m * V].reshape(m, V), theta, skew) for h in range(n_host)]
+            host_ms.append(((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
+        ta, td, _ = timed_round((lambda: ops.local_align(x, x_off, table, theta, skew, sum_V=P * V, out=out, ws=ws),
+                                 lambda: ops.monotonic_decode(x, rows_t, order, vtab, None, bp, run, sec, path), host), a.warmup, a.reps)
+        back_ms, ref_ms = (float(np.median([t[i] for t in host_ms[a.warmup:]])) for i in (0, 1))
+        sc, sp = out[0].cpu().numpy(), out[1].cpu().numpy()
+        same = all(sc[h:h + 1].view(np.int32)[0] == np.array([w[0]]).view(np.int32)[0] and tuple(sp[h].tolist()) == w[1]
+                   for h, w in enumerate(host_out))
+        steps = (m + 63) // 64 * (V + 63)
+        rows.append({"P": P, "m": m, "V": V, "local_align_ms": round(ta, 4), "monotonic_decode_ms": round(td, 4),
+                     "align_over_decode": round(ta / td, 3), "steps": steps, "ns_per_step": round(ta * 1e6 / steps, 1),
+                     "Mcells_per_s": round(P * m * V / ta * 1e-3, 1), "read_back_ms": round(back_ms, 3), "host_blocks": n_host,
+                     "host_ref_ms": round(ref_ms, 1), "host_scaled_ms": round(back_ms + ref_ms * P / n_host, 1),
+                     "host_over_align": round((back_ms + ref_ms * P / n_host) / ta, 1), "equals_host": bool(same)})
+        del x, bp
+    # end to end on the corpus layout: one 40-second query cut out of a video
+    v_off = video_layouts(N)["corpus"].cpu().numpy().astype(np.int64)
+    idx = search.VideoIndex(v16, v_off, [f"v{i:06d}" for i in range(len(v_off) - 1)])
+    src = int(np.argmax(v_off[1:] - v_off[:-1] >= 100))
+    query, clip = (src, 30, 69), (src, 30, 61)
+
+    def host_clock(fn):
+        for _ in range(a.warmup):
+            fn()
+        ms = []
+        for _ in range(a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ms))
+    found = search.search_copies(idx, [query], k=k, threshold=0.4, skew=0.1)[0]
+    t_copies = host_clock(lambda: search.search_copies(idx, [query], k=k, threshold=0.4, skew=0.1))
+    t_clips = host_clock(lambda: search.search_clips(idx, [clip], k=k))
+    e2e = {"videos": len(v_off) - 1, "query_seconds": 40, "pool": 32, "piece": 16, "search_copies_ms": round(t_copies, 3),
+           "search_clips_ms": round(t_clips, 3), "copies_over_clips": round(t_copies / t_clips, 3), "hits": len(found),
+           "finds_its_source": bool(found and found[0][:5] == (idx.vids[src], 30, 69, 0, 39))}
+    return rows, e2e
 
 
 def shards_table(N, k, v16, v8, s8, a):
@@ -559,6 +645,8 @@ def main():
     ap.add_argument("--moments", action="store_true", help="also time rank_topk_video and moment_extent (see the module docstring)")
     ap.add_argument("--sequences", action="store_true", help="time sequence_topk against the video and row sweeps instead (see the module docstring)")
     ap.add_argument("--clips", action="store_true", help="time clip_topk against sequence_topk and the row sweep instead (see the module docstring)")
+    ap.add_argument("--copies", action="store_true",
+                    help="time local_align against monotonic_decode and the host restatement, and search_copies, instead (see the module docstring)")
     ap.add_argument("--rerank", action="store_true", help="time the stages of search_rerank instead (see the module docstring)")
     ap.add_argument("--pool", type=int, default=32)
     ap.add_argument("--shards", type=int, nargs="?", const=8, default=0, metavar="S",
@@ -656,6 +744,28 @@ def main():
                 fh.write(" ".join(f"{c:>18}" for c in cols) + "\n")
                 for r in rows:
                     fh.write(" ".join(f"{str(r[c]):>18}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
+    if a.copies:
+        del v8, s8
+        rows, e2e = copies_table(N, k, v16, a)
+        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "copies": rows, "search": e2e}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --copies --rows {N} -k {k}: median of {a.reps} after {a.warmup} warm-ups, {res['gpu']}\n")
+                fh.write(f"# local_align (threshold {ALIGN_PRICES[0]}, skew {ALIGN_PRICES[1]}, scores N(0, 1/512)) against monotonic_decode over the "
+                         "same blocks (device events) and the host path: read_back = x.cpu(), host_ref = the float32 numpy restatement over "
+                         "host_blocks blocks (host clock), host_scaled = read_back + host_ref * P / host_blocks; the three alternate call by "
+                         "call; steps = ceil(m / 64) * (V + 63) anti-diagonals per block\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>19}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>19}" for c in cols) + "\n")
+                fh.write("# end to end, bf16 index, host clock around calls that end in their read-back: search_copies (40 s query, pool 32, "
+                         "piece 16, threshold 0.4, skew 0.1) beside search_clips (its first 32 s)\n")
+                fh.write(" ".join(f"{c:>19}" for c in e2e) + "\n")
+                fh.write(" ".join(f"{str(v):>19}" for v in e2e.values()) + "\n")
         print(json.dumps(res))
         return
     if a.clips:

@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -1150,6 +1150,31 @@ int tan_label_decode(const float* top_score, const int* top_label, int k, long N
 long tan_local_align_ws_bytes(long P, long sum_V);
 int tan_local_align(const float* x, long n_x, const long* x_off, const int* table, long P, long sum_V, float theta, float skew,
                     float* score, int* span, void* ws, void* stream);
+
+/* ---- copy alignment with the path: the second-to-second time map of the best local alignment (`search.align_paths`) ----
+ * This ADDS to tan_local_align's definition and changes nothing in it.  Each positive cell gets one 2-bit CODE:
+ *     0 start: pred is diag and that H is 0 or lies outside the matrix;   1 diag;   2 up;   3 left
+ * with pred the first of (diag, up, left) attaining P, as above.  The PATH of a block with score > 0 is the chain of cells from
+ * `end` back along the codes to its start cell.  It has exactly `cells` cells and is monotone in i and j, so the cells of query
+ * second i are consecutive video seconds lo_i .. hi_i, and lo_{i+1} is hi_i or hi_i + 1.  The TIME MAP qmap is int32 [m, 2] per
+ * block: row i = (lo_i, hi_i) for a_first <= i <= a_last, (-1, -1) in every other row and in all rows of a block without a
+ * positive cell.  Hence qmap[a_first][0] == b_first, qmap[a_last][1] == b_last, sum (hi - lo + 1) == cells, and the map is a
+ * fixed function of the bits of x whatever the launch shape.
+ * tan_local_align_path: x, n_x, x_off, table, P, sum_V, theta, skew, score, span as for tan_local_align; score and span are
+ *   tan_local_align's bit for bit.  path_off [P, 2] `long` on the device: column 0 the first qmap row of each block -- the running
+ *   sum of m; the block owns m rows of qmap int32 [n_map, 2] --, column 1 its first TRACE entry -- the running sum of
+ *   ceil(m / 64) * (V + 63), n_trace the total.  The trace is one 16-byte entry per (strip of 64 query seconds, anti-diagonal d):
+ *   two 64-bit masks, the low and the high bit of the code of cell (i, j) at bit i & 63 of entry (i >> 6, j + (i & 63)).
+ *   ws: tan_local_align_path_ws_bytes(P, sum_V, n_trace) = 32 * sum_V + 16 * n_trace + 16 bytes, any alignment (-1 for P or sum_V as
+ *   above, n_trace outside [1, 2^35)).  One launch, one wave per block as tan_local_align; the same wave walks the path back
+ *   (about (m + V) / 32 dependent loads of 1 KiB) and writes the block's m map rows.  No atomics: bit-identical from run to run.
+ *   An entry is skipped if tan_local_align would skip it, or if its map rows leave [0, n_map) or its trace entries leave
+ *   [0, n_trace): the empty score and span, and NOTHING of qmap is touched.  A valid entry writes all m of its map rows: the caller
+ *   never clears qmap.  TAN_ERR_BAD_ARG, nothing launched: tan_local_align's cases, a NULL path_off or qmap, n_map outside
+ *   [1, 2^31), n_trace outside [1, 2^35).                                                                                      */
+long tan_local_align_path_ws_bytes(long P, long sum_V, long n_trace);
+int tan_local_align_path(const float* x, long n_x, const long* x_off, const int* table, long P, long sum_V, float theta, float skew,
+                         const long* path_off, long n_map, long n_trace, float* score, int* span, int* qmap, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -679,6 +679,64 @@ def local_align(x, x_off, table, theta, skew, *, sum_V=None, check_table=False, 
     return score, span
 
 
+def local_align_path_ws_bytes(P, sum_V, n_trace):
+    n = _lib.lib().tan_local_align_path_ws_bytes(P, sum_V, n_trace)
+    if n < 0:
+        raise _lib.TanHipError(f"tan_local_align_path_ws_bytes({P}, {sum_V}, {n_trace}): bad argument")
+    return n
+
+
+def local_align_path(x, x_off, table, theta, skew, path_off, *, sum_V=None, n_map, n_trace, out=None, ws=None):
+    """`local_align` with the best path's second-to-second time map (tan_local_align_path; the exact definition is in
+    include/tan_hip.h).  x, x_off, table, theta, skew, sum_V as for `local_align`; path_off int64 [P, 2] on the device = (each
+    block's first map row: the running sum of m, its first trace entry: the running sum of ceil(m / 64) * (V + 63)), n_map and
+    n_trace their totals (`search.path_tables`).  Returns (score f32 [P], span int32 [P, 5], qmap int32 [n_map, 2]) on the device:
+    score and span are `local_align`'s bit for bit; a block's m map rows hold (first, last video second) of query seconds a_first ..
+    a_last and (-1, -1) elsewhere.  A table entry that breaks the limits, or whose map rows or trace entries leave [0, n_map) /
+    [0, n_trace), gives the empty result and its map rows are NOT written.
+    out: caller-owned (score, span, qmap); ws: scratch (uint8, >= local_align_path_ws_bytes(P, sum_V, n_trace))."""
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError("local_align_path: x is f32 [n_x], contiguous, n_x >= 1")
+    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
+        raise ValueError("local_align_path: x_off is int64 [P], contiguous, P >= 1")
+    P, dev = x_off.numel(), x.device
+    if table.dtype != torch.int32 or table.shape != (P, 3) or not table.is_contiguous():
+        raise ValueError("local_align_path: table is int32 [P, 3] = (m, V, first boundary slot), contiguous")
+    if path_off.dtype != torch.int64 or path_off.shape != (P, 2) or not path_off.is_contiguous():
+        raise ValueError("local_align_path: path_off is int64 [P, 2] = (first map row, first trace entry), contiguous")
+    theta, skew = float(theta), float(skew)
+    if not math.isfinite(theta) or not (skew >= 0 and math.isfinite(skew)):
+        raise ValueError("local_align_path: theta finite, skew in [0, +inf)")
+    if sum_V is None:
+        t = table[-1].cpu()
+        sum_V = int(t[1]) + int(t[2])
+    sum_V, n_map, n_trace = int(sum_V), int(n_map), int(n_trace)
+    if not P <= sum_V < 2 ** 31:
+        raise ValueError("local_align_path: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
+    if not 1 <= n_map < 2 ** 31 or n_trace < 1:
+        raise ValueError("local_align_path: 1 <= n_map < 2^31, n_trace >= 1")
+    if out is None:
+        out = (torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, 5, dtype=torch.int32, device=dev),
+               torch.empty(n_map, 2, dtype=torch.int32, device=dev))
+    score, span, qmap = out
+    if score.dtype != torch.float32 or span.dtype != torch.int32 or score.shape != (P,) or span.shape != (P, 5) \
+            or not score.is_contiguous() or not span.is_contiguous():
+        raise ValueError("local_align_path: out is (score f32 [P], span int32 [P, 5], qmap), contiguous")
+    if qmap.dtype != torch.int32 or qmap.shape != (n_map, 2) or not qmap.is_contiguous():
+        raise ValueError("local_align_path: qmap is int32 [n_map, 2], contiguous")
+    lib = _lib.lib()
+    need = lib.tan_local_align_path_ws_bytes(P, sum_V, n_trace)
+    if need < 0:
+        raise ValueError("local_align_path: n_trace out of range")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("local_align_path: ws is uint8 of at least local_align_path_ws_bytes(P, sum_V, n_trace) bytes")
+    _lib.check(lib.tan_local_align_path(_f32(x), x.numel(), _ptr(x_off), _ptr(table), P, sum_V, theta, skew, _ptr(path_off), n_map, n_trace,
+                                        _f32(score), _ptr(span), _ptr(qmap), _ptr(ws), _stream()), "tan_local_align_path")
+    return score, span, qmap
+
+
 def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scale=None, v_scale=None, out=None):
     """(start, end) int32 [Q, k]: for every hit of `rank_topk_video`'s lists, the contiguous run of index rows around top_row,
     inside the hit's video, whose score is >= top_score - width -- global rows, inclusive (tan_moment_extent / _e4m3; the exact

@@ -50,6 +50,10 @@ sentence is ranked against all of it:
     `tan_local_align` finds the best LOCAL alignment in it -- steps along either axis allowed at a price, unrelated cells bridged
     at a price -- with its extent in both videos.  `search_copies` proposes the candidate videos by one `tan_clip_topk` sweep over
     the query's pieces and ranks them by that alignment (`similar --align`).
+  * `align_paths` / `search_copies(paths=True)`: the same alignment with its second-to-second time map -- which seconds of the copy
+    show each second of the query (`tan_local_align_path` records every step's decision and walks the best path back).
+    `copy_interval`, `copy_inverse` and `transfer_segments` carry timestamps, chapter marks or `Annotation.segments` from the
+    original onto the copy (`similar --align --map OUT.csv`).
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -63,6 +67,7 @@ sentence is ranked against all of it:
         [--threshold X] [--min-len M] [--smooth PENALTY] [--per-second] --out segments.csv
     python -m temporalalignnet_amd.search similar --index I.npz [--shard I1.npz ...] [--host-resident] --clip VID:10-29 [-k K] [--keep-source]
     python -m temporalalignnet_amd.search similar --index I.npz --clip VID:0-599 --align --threshold X [--skew Y] [--pool P] [--piece S] [-k K]
+    python -m temporalalignnet_amd.search similar --index I.npz --clip VID:0-599 --align --threshold X --map OUT.csv
 """
 from __future__ import annotations
 
@@ -96,6 +101,9 @@ MAX_CLIP_SECONDS = 32           # a clip's rows are one wave's 32 resident query
 # second of the QUERY that the copy shows, the alignment's score (the sum of score - threshold over its cells, minus skew per step
 # along one axis alone) and the number of its cells
 CopyHit = namedtuple("CopyHit", ("vid", "start", "end", "q_start", "q_end", "score", "cells"))
+# one hit of `align_paths` / `search_copies(paths=True)`: the CopyHit, and int32 [q_end - q_start + 1, 2]: the first / last second of
+# the video shown for each query second from q_start on
+CopyPath = namedtuple("CopyPath", ("hit", "seconds"))
 MAX_ALIGN_SECONDS = 4096        # a query of `align_spans`: 12 bits of tan_local_align's packed origin
 PIECE_ROWS = 32                 # `align_spans` hands a query to tan_sequence_scores as sequences of this many rows
 EMPTY_ROW = 0x7fffffff          # the row of an empty top-k slot (include/tan_hip.h)
@@ -969,8 +977,13 @@ def align_spans(index, pairs, threshold, skew=0.0):
     shard without one is not visited, and each visited shard costs one `tan_sequence_scores` and one `tan_local_align`.  One
     read-back at the end.  The score blocks of a shard's pairs (4 bytes x query seconds x video seconds) are held at once:
     ValueError from 2^31 elements on -- split the call."""
+    return _align_pairs("align_spans", index, pairs, threshold, skew, False)
+
+
+def _align_pairs(what, index, pairs, threshold, skew, paths):
+    """`align_spans` (paths False: CopyHit or None per pair) and `align_paths` (paths True: CopyPath or None)"""
     pairs = list(pairs)
-    threshold, skew = _align_prices("align_spans", threshold, skew)
+    threshold, skew = _align_prices(what, threshold, skew)
     if not pairs:
         return []
     # every distinct query once: `search_copies` pairs one query with many videos
@@ -1007,26 +1020,96 @@ def align_spans(index, pairs, threshold, skew=0.0):
     shard = np.searchsorted(index.video_base, gvs, side="right") - 1
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)          # noqa: E731
     i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)          # noqa: E731
-    parts = []
+    parts, maps = [], []
     for s, feat, scale, v_off in index.shard_views([int(s) for s in np.unique(shard)]):
         at = np.flatnonzero(shard == s)
         local = gvs[at] - index.video_base[s]
         sv = index.shards[s].v_off
         hits, hit_off, x_off, table, n_x, sum_V = align_tables(ms[q_of[at]], sv[local + 1] - sv[local], first[q_of[at]], local)
         if n_x >= 2 ** 31:
-            raise ValueError("align_spans: the score blocks of one shard's pairs reach 2^31 elements; split the call")
+            raise ValueError(f"{what}: the score blocks of one shard's pairs reach 2^31 elements; split the call")
         x = torch.empty(n_x, dtype=torch.float32, device=dev)
         ops.sequence_scores(sweep.tq, feat, s_off_dev, v_off, i32(hits), i64(hit_off), x, **sweep.scales(scale))
-        score, span = ops.local_align(x, i64(x_off), i32(table), threshold, skew, sum_V=sum_V)
+        if paths:
+            path_off, n_map, n_trace = path_tables(table[:, 0], table[:, 1])
+            score, span, qmap = ops.local_align_path(x, i64(x_off), i32(table), threshold, skew, i64(path_off), sum_V=sum_V, n_map=n_map,
+                                                     n_trace=n_trace)
+            maps.append((path_off[:, 0], qmap.view(-1)))
+        else:
+            score, span = ops.local_align(x, i64(x_off), i32(table), threshold, skew, sum_V=sum_V)
         parts.append((at, torch.cat((score.view(torch.int32)[:, None], span), 1)))
-    back = torch.cat([t for _, t in parts]).cpu().numpy()                                      # the one read-back
-    out, a0 = [None] * len(pairs), 0
-    for at, _ in parts:
-        for h, row in zip(at, back[a0:a0 + len(at)]):
+    n_head = 6 * sum(len(at) for at, _ in parts)
+    back = torch.cat([t.view(-1) for _, t in parts] + [q for _, q in maps]).cpu().numpy()       # the one read-back
+    head, tail = back[:n_head].reshape(-1, 6), back[n_head:].reshape(-1, 2)
+    out, a0, r0 = [None] * len(pairs), 0, 0
+    for n, (at, _) in enumerate(parts):
+        for e, (h, row) in enumerate(zip(at, head[a0:a0 + len(at)])):
             sc = float(row[:1].view(np.float32)[0])
             if sc > 0:
                 out[h] = CopyHit(index.vids[gvs[h]], int(row[3]), int(row[4]), int(row[1]), int(row[2]), sc, int(row[5]))
+                if paths:
+                    row0 = r0 + int(maps[n][0][e])                                            # the pair's map rows, then its aligned ones
+                    out[h] = CopyPath(out[h], tail[row0 + int(row[1]):row0 + int(row[2]) + 1].copy())
         a0 += len(at)
+        if paths:
+            r0 += maps[n][1].numel() // 2
+    return out
+
+
+def path_tables(ms, Vs):
+    """What `ops.local_align_path` needs beside `align_tables`: (path_off [P, 2] int64 = (each pair's first map row: the running sum
+    of m, its first trace entry: the running sum of ceil(m / 64) * (V + 63)), n_map, n_trace: the two totals)"""
+    ms, Vs = np.asarray(ms, dtype=np.int64), np.asarray(Vs, dtype=np.int64)
+    rows = np.concatenate([[0], np.cumsum(ms)])
+    entries = np.concatenate([[0], np.cumsum((ms + 63) // 64 * (Vs + 63))])
+    return np.stack((rows[:-1], entries[:-1]), 1), int(rows[-1]), int(entries[-1])
+
+
+@torch.no_grad()
+def align_paths(index, pairs, threshold, skew=0.0):
+    """`align_spans` with the path: per pair (query, vid) one CopyPath(hit, seconds) or None.  `hit` is the CopyHit that
+    `align_spans` returns for the pair; `seconds` is an int32 array [q_end - q_start + 1, 2]: row i = the first and the last
+    second of the video that show query second q_start + i (`tan_local_align_path`, defined in include/tan_hip.h).  A second of
+    the query shown for several seconds of the copy (slowed down, or seconds inserted) has first < last; consecutive query seconds
+    that share one video second (sped up, or seconds dropped) repeat it.  The path is monotone and without jumps: a row's first
+    is the previous row's last or the second after it.  `copy_interval`, `copy_inverse` and `transfer_segments` read the map.
+    Arguments, checks and shard grouping are `align_spans`'.  Each visited shard costs one `tan_sequence_scores` and one
+    `tan_local_align_path`, and the one read-back at the end carries the maps too (8 bytes per query second and pair)."""
+    return _align_pairs("align_paths", index, pairs, threshold, skew, True)
+
+
+def copy_interval(path, q_first, q_last):
+    """The video seconds (first, last), inclusive, that show query seconds q_first .. q_last of a CopyPath, the query seconds
+    clipped to the aligned [q_start, q_end]; None if they do not meet."""
+    a, b = max(int(q_first), path.hit.q_start), min(int(q_last), path.hit.q_end)
+    if a > b:
+        return None
+    return int(path.seconds[a - path.hit.q_start, 0]), int(path.seconds[b - path.hit.q_start, 1])
+
+
+def copy_inverse(path):
+    """The map of a CopyPath read the other way: an int32 array [end - start + 1, 2], row t = the first and the last QUERY second
+    shown at video second start + t.  A step of the path advances the video by at most one second, so every video second of
+    [start, end] is on it and every row is set.  Pure numpy on the host."""
+    hit, sec = path.hit, np.asarray(path.seconds, dtype=np.int64)
+    inv = np.empty((hit.end - hit.start + 1, 2), dtype=np.int32)
+    inv[:, 0], inv[:, 1] = np.iinfo(np.int32).max, -1
+    for i, (lo, hi) in enumerate(sec):
+        rows = slice(lo - hit.start, hi - hit.start + 1)
+        inv[rows, 0] = np.minimum(inv[rows, 0], hit.q_start + i)
+        inv[rows, 1] = np.maximum(inv[rows, 1], hit.q_start + i)
+    return inv
+
+
+def transfer_segments(path, segments):
+    """Segments (start, end, label, ...) on the QUERY's timeline (seconds of the query, 0 = its first, inclusive) carried onto the
+    copy's timeline through `copy_interval`: the same tuples with start and end replaced by video seconds, in their order; a
+    segment that does not meet the aligned span is dropped."""
+    out = []
+    for seg in segments:
+        at = copy_interval(path, seg[0], seg[1])
+        if at is not None:
+            out.append(tuple(at) + tuple(seg[2:]))
     return out
 
 
@@ -1036,7 +1119,7 @@ def copy_pieces(m, piece):
 
 
 @torch.no_grad()
-def search_copies(index, queries, k=10, pool=32, piece=16, *, threshold, skew=0.0, exclude_source=False):
+def search_copies(index, queries, k=10, pool=32, piece=16, *, threshold, skew=0.0, exclude_source=False, paths=False):
     """Video to video when the copy was re-timed or re-cut -- slowed down, sped up, seconds cut out or inserted: per QUERY ((vid,
     first, last) of this index, or a float tensor [m, 512]; 1 to 4096 seconds) the videos that hold the best local alignment with
     it, [[CopyHit(vid, start, end, q_start, q_end, score, cells)]] by descending score (equal scores by global video number), at
@@ -1047,6 +1130,8 @@ def search_copies(index, queries, k=10, pool=32, piece=16, *, threshold, skew=0.
     a piece's pool: a shorter piece survives more re-timing but is less specific, a larger pool admits more videos, and both cost
     sweep time (the sweep grows with the number of pieces) and alignment time (with the candidates).  The defaults piece = 16 and
     pool = 32 have not been measured on real features.
+    paths: the hits are CopyPath(hit, seconds) -- the same CopyHits in the same order, each with its second-to-second time map
+    (`align_paths` in place of `align_spans`).
     `index`: a `VideoIndex` or a `ShardedIndex`.  Two read-backs: the candidates, then the alignments."""
     queries = list(queries)
     threshold, skew = _align_prices("search_copies", threshold, skew)
@@ -1077,11 +1162,11 @@ def search_copies(index, queries, k=10, pool=32, piece=16, *, threshold, skew=0.
         if exclude_source and source is not None:
             cands[q].discard(source[0])
         pairs += [(q, gv) for gv in sorted(cands[q])]
-    found = align_spans(index, [(queries[q], gv) for q, gv in pairs], threshold, skew)          # read-back 2
+    found = (align_paths if paths else align_spans)(index, [(queries[q], gv) for q, gv in pairs], threshold, skew)      # read-back 2
     out = [[] for _ in queries]
     for (q, gv), hit in zip(pairs, found):
         if hit is not None:
-            out[q].append((-hit.score, gv, hit))
+            out[q].append((-(hit.hit if paths else hit).score, gv, hit))
     return [[hit for _, _, hit in sorted(hits, key=lambda e: e[:2])[:k]] for hits in out]
 
 
@@ -1426,6 +1511,9 @@ def _parser():
     p.add_argument("--piece", type=int, default=None,
                    help=f"with --align: the clip is cut into pieces of this many seconds for the candidate sweep, 1 to {MAX_CLIP_SECONDS} "
                         "(default 16)")
+    p.add_argument("--map", default=None, metavar="OUT.csv",
+                   help="with --align: write the time map of every hit, one row `query,vid,query_second,first,last` per aligned second "
+                        "of the clip (query_second on the clip's own video timeline; first..last the seconds of vid that show it)")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
@@ -1482,6 +1570,8 @@ def parse_args(argv=None):
     if a.cmd == "similar":
         if not a.align and any(x is not None for x in (a.threshold, a.skew, a.pool, a.piece)):
             ap.error("--threshold / --skew / --pool / --piece need --align")
+        if a.map is not None and not a.align:
+            ap.error("--map needs --align")
         if a.align:
             if a.threshold is None or not np.isfinite(a.threshold):
                 ap.error("--align needs a finite --threshold")
@@ -1550,13 +1640,22 @@ def main(argv=None):
         try:
             if a.align:
                 found = search_copies(idx, a.clip, a.k, 32 if a.pool is None else a.pool, 16 if a.piece is None else a.piece,
-                                      threshold=a.threshold, skew=a.skew or 0.0, exclude_source=not a.keep_source)
+                                      threshold=a.threshold, skew=a.skew or 0.0, exclude_source=not a.keep_source,
+                                      paths=a.map is not None)
             else:
                 found = search_clips(idx, a.clip, a.k, exclude_source=not a.keep_source)
         except ValueError as e:
             print(f"similar: {e}", file=sys.stderr)
             return 2
         if a.align:
+            if a.map is not None:
+                with open(a.map, "w") as f:
+                    f.write("query,vid,query_second,first,last\n")
+                    for (vid, first, last), hits in zip(a.clip, found):
+                        for h, seconds in hits:
+                            for i, (lo, hi) in enumerate(seconds.tolist()):
+                                f.write(f"{vid}:{first}-{last},{h.vid},{first + h.q_start + i},{lo},{hi}\n")
+                found = [[h for h, _ in hits] for hits in found]
             for hits in found:
                 for h in hits:
                     print(f"{h.vid}\t{h.start}\t{h.end}\t{h.score:.6f}\t{h.q_start}\t{h.q_end}\t{h.cells}")

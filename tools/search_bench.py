@@ -5,7 +5,7 @@ process, device events around each call, caller-owned outputs and scratch.  Prin
     python tools/search_bench.py --sequences [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --rerank [--rows 4194304] [--queries 1 64] [--pool 32] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --clips [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
-    python tools/search_bench.py --copies [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
+    python tools/search_bench.py --copies [--parent-lib PARENT.so] [--rows 4194304] [-k 10] [--reps 10] [--warmup 3] [--out FILE] [--paths-out FILE]
     python tools/search_bench.py --shards [8] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--reps 10] [--warmup 3] [--out FILE]
     python tools/search_bench.py --restrict [--parent-lib PARENT.so] [--rows 4194304] [--queries 1 64 1024] [-k 10] [--out FILE]
     python tools/search_bench.py --annotate [--parent-lib PARENT.so] --rows 1048576 [--labels 128 1024 8192] [--out FILE]
@@ -37,7 +37,11 @@ file of the test tree this tool depends on: the yardstick is the reference the t
 clock over the first HOST_BLOCKS blocks and scaled to P where P is larger (`host_scaled`).  `steps` is the kernel's serial chain per
 block, ceil(m / 64) * (V + 63) anti-diagonals, and `ns_per_step` the launch's time over it.  Then, on the 4 Mi-row corpus layout over
 the bf16 index, `search.search_copies` (a 40-second query cut out of the corpus, pool 32, piece 16, threshold 0.4, skew 0.1) beside
-`search.search_clips` (its first 32 seconds), host clock around calls that end in their read-back.
+`search.search_clips` (its first 32 seconds), host clock around calls that end in their read-back.  A second table (`paths`,
+--paths-out) times `ops.local_align_path` over the same three shapes, alternating call by call with `ops.local_align`:
+`path_over_align`, the trace's size and what a caller reads back with and without the map; with --parent-lib the parent commit's
+`tan_local_align` runs twice in the same round (`parent_align_ms`, `parent_again_ms`; `parent_spread`: how far its own two medians lie
+apart) beside this build's.
 
 --rerank times the stages of `search.search_rerank` INSTEAD, on the "corpus" layout over a bf16 index with a bf16 stem store (random
 rows) and a randomly initialised 6 + 6 layer model with the alignability head, bf16: `dual_ms` (`ops.rank_topk_video`, k = pool),
@@ -236,7 +240,8 @@ def copies_table(N, k, v16, a):
     from temporalalignnet_amd import search
     theta, skew = ALIGN_PRICES
     i32 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).cuda()          # noqa: E731
-    rows = []
+    rows, paths = [], []
+    parent = parent_align(a.parent_lib) if a.parent_lib else None
     for P, m, V in ALIGN_CASES:
         x = torch.randn(P * m * V, generator=torch.Generator(device="cuda").manual_seed(P + m), device="cuda") * (512 ** -0.5)
         x_off = torch.arange(P, dtype=torch.int64, device="cuda") * (m * V)
@@ -271,7 +276,32 @@ def copies_table(N, k, v16, a):
                      "Mcells_per_s": round(P * m * V / ta * 1e-3, 1), "read_back_ms": round(back_ms, 3), "host_blocks": n_host,
                      "host_ref_ms": round(ref_ms, 1), "host_scaled_ms": round(back_ms + ref_ms * P / n_host, 1),
                      "host_over_align": round((back_ms + ref_ms * P / n_host) / ta, 1), "equals_host": bool(same)})
-        del x, bp
+        # the same blocks with the time map: local_align and local_align_path alternate call by call; with --parent-lib the parent
+        # commit's tan_local_align runs TWICE in the same round, and the distance of its two medians is the session's spread
+        path_off, n_map, n_trace = search.path_tables(np.full(P, m), np.full(P, V))
+        po = torch.from_numpy(path_off).cuda()
+        pout = (torch.empty(P, device="cuda"), torch.empty(P, 5, dtype=torch.int32, device="cuda"),
+                torch.empty(n_map, 2, dtype=torch.int32, device="cuda"))
+        pws = torch.empty(ops.local_align_path_ws_bytes(P, P * V, n_trace), dtype=torch.uint8, device="cuda")
+        fns = [lambda: ops.local_align(x, x_off, table, theta, skew, sum_V=P * V, out=out, ws=ws),
+               lambda: ops.local_align_path(x, x_off, table, theta, skew, po, sum_V=P * V, n_map=n_map, n_trace=n_trace, out=pout, ws=pws)]
+        if parent is not None:
+            pout0 = (torch.empty(P, device="cuda"), torch.empty(P, 5, dtype=torch.int32, device="cuda"))
+            fns += [lambda: parent(x, x_off, table, P, P * V, theta, skew, pout0, ws)] * 2
+        t = timed_round(fns, a.warmup, a.reps)
+        aligned = pout[1][:, 4] > 0
+        lo, hi = pout[2].view(P, m, 2)[..., 0], pout[2].view(P, m, 2)[..., 1]
+        prow = {"P": P, "m": m, "V": V, "local_align_ms": round(t[0], 4), "local_align_path_ms": round(t[1], 4),
+                "path_over_align": round(t[1] / t[0], 3), "trace_MB": round(16 * n_trace / 1e6, 2), "align_read_back_bytes": 24 * P,
+                "path_read_back_bytes": 24 * P + 8 * n_map, "mean_cells": round(float(pout[1][:, 4].float().mean()), 1),
+                "same_score_span": bool(torch.equal(pout[0].view(torch.int32), out[0].view(torch.int32)) and torch.equal(pout[1], out[1])),
+                "cells_add_up": bool(torch.equal(((hi - lo + 1) * (lo >= 0)).sum(1)[aligned], pout[1][aligned, 4].long()))}
+        if parent is not None:
+            prow.update({"parent_align_ms": round(t[2], 4), "parent_again_ms": round(t[3], 4),
+                         "parent_spread": round(abs(t[2] - t[3]) / min(t[2], t[3]), 4), "align_over_parent": round(t[0] / min(t[2], t[3]), 4),
+                         "equals_parent": bool(torch.equal(pout0[0].view(torch.int32), out[0].view(torch.int32)) and torch.equal(pout0[1], out[1]))})
+        paths.append(prow)
+        del x, bp, pws
     # end to end on the corpus layout: one 40-second query cut out of a video
     v_off = video_layouts(N)["corpus"].cpu().numpy().astype(np.int64)
     idx = search.VideoIndex(v16, v_off, [f"v{i:06d}" for i in range(len(v_off) - 1)])
@@ -294,7 +324,9 @@ def copies_table(N, k, v16, a):
     e2e = {"videos": len(v_off) - 1, "query_seconds": 40, "pool": 32, "piece": 16, "search_copies_ms": round(t_copies, 3),
            "search_clips_ms": round(t_clips, 3), "copies_over_clips": round(t_copies / t_clips, 3), "hits": len(found),
            "finds_its_source": bool(found and found[0][:5] == (idx.vids[src], 30, 69, 0, 39))}
-    return rows, e2e
+    t_paths = host_clock(lambda: search.search_copies(idx, [query], k=k, threshold=0.4, skew=0.1, paths=True))
+    e2e["search_copies_paths_ms"] = round(t_paths, 3)
+    return rows, e2e, paths
 
 
 def shards_table(N, k, v16, v8, s8, a):
@@ -415,6 +447,21 @@ def parent_sweep(path):
         else:
             rc = L.tan_rank_topk(tq.data_ptr(), vn.data_ptr(), ops.TAN_BF16, Q, N, 512, None, k, 0, None, None, out[0].data_ptr(),
                                  out[1].data_ptr(), ws.data_ptr(), st)
+        assert rc == 0, rc
+    return run
+
+
+def parent_align(path):
+    """tan_local_align of ANOTHER build of the library (the parent commit's), called as `ops.local_align` calls it"""
+    import ctypes as C
+
+    from temporalalignnet_amd import _lib
+    L = C.CDLL(path)
+    L.tan_local_align.restype, L.tan_local_align.argtypes = _lib.declared_prototypes()["tan_local_align"]
+
+    def run(x, x_off, table, P, sum_V, theta, skew, out, ws):
+        rc = L.tan_local_align(x.data_ptr(), x.numel(), x_off.data_ptr(), table.data_ptr(), P, sum_V, theta, skew, out[0].data_ptr(),
+                               out[1].data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
         assert rc == 0, rc
     return run
 
@@ -652,8 +699,10 @@ def main():
     ap.add_argument("--shards", type=int, nargs="?", const=8, default=0, metavar="S",
                     help="time sharded search over S shards (default 8) instead (see the module docstring)")
     ap.add_argument("--restrict", action="store_true", help="time the filtered sweep instead (see the module docstring)")
+    ap.add_argument("--paths-out", default=None, metavar="FILE", help="with --copies: write the local_align_path table here")
     ap.add_argument("--parent-lib", default=None, metavar="PATH",
                     help="with --restrict: libtan_hip.so of the parent commit's build, whose plain sweep is timed in the same run; "
+                         "with --copies: its tan_local_align is timed twice beside this build's; "
                          "with --annotate: its sweep checks that this build's route (a) is the parent's")
     ap.add_argument("--annotate", action="store_true", help="time label_topk and label_runs instead (see the module docstring)")
     ap.add_argument("--labels", type=int, nargs="+", default=[128, 1024, 8192], help="with --annotate: vocabulary sizes")
@@ -748,8 +797,22 @@ def main():
         return
     if a.copies:
         del v8, s8
-        rows, e2e = copies_table(N, k, v16, a)
-        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "copies": rows, "search": e2e}
+        rows, e2e, paths = copies_table(N, k, v16, a)
+        res = {"rows": N, "k": k, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "copies": rows, "search": e2e,
+               "paths": paths}
+        if a.paths_out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.paths_out)), exist_ok=True)
+            with open(a.paths_out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --copies --rows {N}: median of {a.reps} after {a.warmup} warm-ups, device events, caller-owned "
+                         f"outputs and scratch, {res['gpu']}\n")
+                fh.write(f"# local_align_path (the time map) beside local_align over the same blocks (threshold {ALIGN_PRICES[0]}, skew "
+                         f"{ALIGN_PRICES[1]}, scores N(0, 1/512)), alternating call by call; trace = 16 bytes x ceil(m / 64) x (V + 63) per block; "
+                         "read_back = what a caller copies to the host (score, span; + 8 bytes per query second); parent_align / parent_again = "
+                         "--parent-lib's tan_local_align twice in the same round, parent_spread = the distance of its two medians\n")
+                cols = list(paths[0])
+                fh.write(" ".join(f"{c:>21}" for c in cols) + "\n")
+                for r in paths:
+                    fh.write(" ".join(f"{str(r[c]):>21}" for c in cols) + "\n")
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as fh:

@@ -259,6 +259,15 @@ def window_pack(video, text, table, T, Kp, out_video, vmask, out_text, tmask):
                                           _ptr(tmask), _stream()), "tan_window_pack")
 
 
+def window_pack_fresh(video, text, table, T, Kp):
+    """`window_pack` into four fresh outputs on video's device, which it returns: (out_video, vmask, out_text, tmask)"""
+    W, dev = table.shape[0], video.device
+    out = (torch.empty(W, T, video.shape[-1], dtype=video.dtype, device=dev), torch.empty(W, T, dtype=torch.bool, device=dev),
+           torch.empty(W, Kp, text.shape[-1], dtype=text.dtype, device=dev), torch.empty(W, Kp, dtype=torch.bool, device=dev))
+    window_pack(video, text, table, T, Kp, *out)
+    return out
+
+
 def window_stitch_acc(sim_j, sim_d, a_joint, table, acc_j, acc_d, cnt, tcnt, a_sum):
     """acc_j / acc_d / cnt [sum K*vlen], tcnt / a_sum [sum K] += one pass (tan_window_stitch_acc); sim_j / sim_d [W, T, Kp] f32 (one
     stage of eval_windows' output, read in place), a_joint [W, Kp] f32 or None (no alignability head: a_sum is None too)."""
@@ -315,11 +324,26 @@ def segment_decode(sim, rows, order, vtab, keep, bias, bp, run, seg, path):
                "tan_segment_decode")
 
 
-def rank_topk_ws_bytes(Q, N, k):
-    n = _lib.lib().tan_rank_topk_ws_bytes(Q, N, k)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_rank_topk_ws_bytes({Q}, {N}, {k}): bad argument")
-    return n
+def _bytes(name):
+    """ops.<name>(*sizes) = tan_<name>(*sizes): a scratch buffer's or a filter image's bytes; TanHipError for sizes the library refuses"""
+    def ask(*sizes):
+        n = getattr(_lib.lib(), f"tan_{name}")(*sizes)
+        if n < 0:
+            raise _lib.TanHipError(f"tan_{name}({', '.join(str(a) for a in sizes)}): bad argument")
+        return n
+    ask.__name__ = name
+    return ask
+
+
+rank_topk_ws_bytes = _bytes("rank_topk_ws_bytes")                    # (Q, N, k)
+rank_topk_video_ws_bytes = _bytes("rank_topk_video_ws_bytes")        # (Q, N, n_videos, k)
+row_filter_bytes = _bytes("row_filter_bytes")                        # (N)
+label_runs_ws_bytes = _bytes("label_runs_ws_bytes")                  # (N)
+label_decode_ws_bytes = _bytes("label_decode_ws_bytes")              # (N, k)
+local_align_ws_bytes = _bytes("local_align_ws_bytes")                # (P, sum_V)
+local_align_path_ws_bytes = _bytes("local_align_path_ws_bytes")      # (P, sum_V, n_trace)
+sequence_topk_ws_bytes = _bytes("sequence_topk_ws_bytes")            # (n_seq, N, k)
+clip_topk_ws_bytes = _bytes("clip_topk_ws_bytes")                    # (n_clip, N, k)
 
 
 def _rows_args(what, tq, vn, q_scale, v_scale):
@@ -343,12 +367,17 @@ def _call(name, tq, q_scale, vn, v_scale, *tail):
         _lib.check(getattr(L, f"tan_{name}")(_ptr(tq), _ptr(vn), _dt(tq), *tail, _stream()), f"tan_{name}")
 
 
-def _scratch(ws, need, dev):
-    """`ws`, or fresh scratch of `need` bytes (a tan_*_ws_bytes answer); need < 0: invalid sizes, which the entry point itself refuses"""
+def _scratch(ws, need, dev, refuse=None, contiguous=True):
+    """`ws`, or fresh scratch of `need` bytes (a tan_*_ws_bytes answer); need < 0: invalid sizes, which the entry point itself refuses
+    (`ws` stays as it came, None included).  refuse: the ValueError text of the wrappers that answer bad scratch by an exception of
+    their own (contiguous=False: `label_runs` never asked for contiguous scratch); without it the sweeps' assertion."""
     if need >= 0:
         if ws is None:
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.numel() >= need
+        if refuse is None:
+            assert ws.dtype == torch.uint8 and ws.numel() >= need
+        elif ws.dtype != torch.uint8 or ws.numel() < need or (contiguous and not ws.is_contiguous()):
+            raise ValueError(refuse)
     return ws
 
 
@@ -405,13 +434,6 @@ def rank_topk_e4m3(tq, q_scale, vn, v_scale, pair=None, k=0, *, splits=0, check_
     return _rank_topk("rank_topk_e4m3", tq, q_scale, vn, v_scale, pair, k, splits, check_pair, out, ws)
 
 
-def rank_topk_video_ws_bytes(Q, N, n_videos, k):
-    n = _lib.lib().tan_rank_topk_video_ws_bytes(Q, N, n_videos, k)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_rank_topk_video_ws_bytes({Q}, {N}, {n_videos}, {k}): bad argument")
-    return n
-
-
 def _video_args(what, tq, vn, v_off, q_scale, v_scale):
     assert v_off.dtype == torch.int32 and v_off.dim() == 1 and v_off.numel() >= 2 and v_off.is_contiguous()
     return _rows_args(what, tq, vn, q_scale, v_scale)
@@ -438,23 +460,13 @@ def rank_topk_video(tq, vn, v_off, k, *, q_scale=None, v_scale=None, splits=0, c
     return top_s, top_r, top_v
 
 
-def row_filter_bytes(N):
-    n = _lib.lib().tan_row_filter_bytes(N)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_row_filter_bytes({N}): bad argument")
-    return n
-
-
 def row_filter_build(spans, N, out=None):
     """The filter image of row spans over an index of N rows (tan_row_filter_build; layout in include/tan_hip.h): spans [n, 2] int32
     (device, contiguous), [lo, hi) each, ascending, disjoint, non-empty, inside [0, N) -- the caller's contract.  Returns the image,
     uint8 [row_filter_bytes(N)]; out: caller-owned memory instead of a fresh one.  Nothing is read back."""
     assert spans.dtype == torch.int32 and spans.dim() == 2 and spans.shape[1] == 2 and spans.is_contiguous()
-    need = _lib.lib().tan_row_filter_bytes(N)
-    if need >= 0:                                  # invalid sizes: the entry point itself refuses them below
-        if out is None:
-            out = torch.empty(need, dtype=torch.uint8, device=spans.device)
-        assert out.dtype == torch.uint8 and out.numel() >= need and out.is_contiguous()
+    out = _scratch(out, _lib.lib().tan_row_filter_bytes(N), spans.device)
+    assert out is None or out.is_contiguous()
     _lib.check(_lib.lib().tan_row_filter_build(_ptr(spans), spans.shape[0], N, _ptr(out), _stream()), "tan_row_filter_build")
     return out
 
@@ -530,14 +542,17 @@ def label_topk_e4m3(tl, l_scale, vn, v_scale, k=1, *, out=None):
     return _label_topk("label_topk_e4m3", True, tl, l_scale, vn, v_scale, k, out)
 
 
-def label_runs_ws_bytes(N):
-    n = _lib.lib().tan_label_runs_ws_bytes(N)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_label_runs_ws_bytes({N}): bad argument")
-    return n
-
-
 RUN_FIELDS = ("video", "start", "end", "label", "peak_row")             # label_runs' int32 columns, in this order; then peak_score f32
+
+
+def _label_lists(what, top_score, top_label, v_off):
+    """The one check of `label_topk`'s lists and the videos' offsets as `label_runs` and `label_decode` take them: (N, k, n_videos)"""
+    if top_score.dim() != 2 or top_score.shape != top_label.shape or top_score.dtype != torch.float32 \
+            or top_label.dtype != torch.int32 or not top_score.is_contiguous() or not top_label.is_contiguous():
+        raise ValueError(f"{what}: top_score f32 and top_label int32 are contiguous [N, k]")
+    if v_off.dtype != torch.int32 or v_off.dim() != 1 or v_off.numel() < 2 or not v_off.is_contiguous():
+        raise ValueError(f"{what}: v_off is int32 [n_videos + 1], contiguous")
+    return (*top_score.shape, v_off.numel() - 1)
 
 
 def label_runs(top_score, top_label, L, v_off, threshold, min_len=1, *, cap=None, label_rows=False, out=None, ws=None):
@@ -549,13 +564,7 @@ def label_runs(top_score, top_label, L, v_off, threshold, min_len=1, *, cap=None
     back: n_runs[0] is the number of kept runs even above cap (default: N, which always suffices), and only the first
     min(n_runs, cap) columns are written.  label_rows=True: also count the rows of every label (whatever min_len is).
     out: caller-owned (n_runs, runs, peak_score, label_rows) instead of fresh ones; ws: scratch (uint8, >= label_runs_ws_bytes)."""
-    if top_score.dim() != 2 or top_score.shape != top_label.shape or top_score.dtype != torch.float32 \
-            or top_label.dtype != torch.int32 or not top_score.is_contiguous() or not top_label.is_contiguous():
-        raise ValueError("label_runs: top_score f32 and top_label int32 are contiguous [N, k]")
-    N, stride = top_score.shape
-    if v_off.dtype != torch.int32 or v_off.dim() != 1 or v_off.numel() < 2 or not v_off.is_contiguous():
-        raise ValueError("label_runs: v_off is int32 [n_videos + 1], contiguous")
-    nv, dev = v_off.numel() - 1, top_score.device
+    (N, stride, nv), dev = _label_lists("label_runs", top_score, top_label, v_off), top_score.device
     threshold, min_len, cap = float(threshold), int(min_len), N if cap is None else int(cap)
     if N < 1 or stride < 1 or int(L) < 1 or not 1 <= nv <= N or threshold != threshold or min_len < 1 or cap < 0:
         raise ValueError("label_runs: N, k, L >= 1, 1 <= n_videos <= N, threshold not NaN, min_len >= 1, cap >= 0")
@@ -569,11 +578,7 @@ def label_runs(top_score, top_label, L, v_off, threshold, min_len=1, *, cap=None
     if counts is not None and (counts.dtype != torch.int32 or counts.shape != (int(L),) or not counts.is_contiguous()):
         raise ValueError("label_runs: label_rows is int32 [L], contiguous")
     lib = _lib.lib()
-    need = lib.tan_label_runs_ws_bytes(N)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    if ws.dtype != torch.uint8 or ws.numel() < need:
-        raise ValueError("label_runs: ws is uint8 of at least label_runs_ws_bytes(N) bytes")
+    ws = _scratch(ws, lib.tan_label_runs_ws_bytes(N), dev, "label_runs: ws is uint8 of at least label_runs_ws_bytes(N) bytes", False)
     if cap > 0:
         _ptr(runs)
         col = [C.c_void_p(runs.data_ptr() + 4 * cap * j) for j in range(5)] + [_f32(peak)]
@@ -584,13 +589,6 @@ def label_runs(top_score, top_label, L, v_off, threshold, min_len=1, *, cap=None
     return n_runs, runs, peak, counts
 
 
-def label_decode_ws_bytes(N, k):
-    n = _lib.lib().tan_label_decode_ws_bytes(N, k)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_label_decode_ws_bytes({N}, {k}): bad argument")
-    return n
-
-
 def label_decode(top_score, top_label, v_off, threshold, switch, *, out=None, ws=None):
     """Temporally consistent labels from `label_topk`'s lists: a Viterbi decode per video (tan_label_decode; the exact definition
     is in include/tan_hip.h).  top_score f32 / top_label int32 [N, k], 1 <= k <= 32; v_off [n_videos + 1] int32 (device).  A path
@@ -598,13 +596,7 @@ def label_decode(top_score, top_label, v_off, threshold, switch, *, out=None, ws
     changes; threshold is finite.  Returns (dec_label int32 [N]: the chosen label or -1 for background, dec_score f32 [N]: its
     list score or -inf), on the device, nothing read back.  out: caller-owned (dec_label, dec_score) instead of fresh ones;
     ws: scratch (uint8, >= label_decode_ws_bytes(N, k))."""
-    if top_score.dim() != 2 or top_score.shape != top_label.shape or top_score.dtype != torch.float32 \
-            or top_label.dtype != torch.int32 or not top_score.is_contiguous() or not top_label.is_contiguous():
-        raise ValueError("label_decode: top_score f32 and top_label int32 are contiguous [N, k]")
-    N, k = top_score.shape
-    if v_off.dtype != torch.int32 or v_off.dim() != 1 or v_off.numel() < 2 or not v_off.is_contiguous():
-        raise ValueError("label_decode: v_off is int32 [n_videos + 1], contiguous")
-    nv, dev = v_off.numel() - 1, top_score.device
+    (N, k, nv), dev = _label_lists("label_decode", top_score, top_label, v_off), top_score.device
     threshold, switch = float(threshold), float(switch)
     if N < 1 or not 1 <= k <= 32 or not 1 <= nv <= N or not math.isfinite(threshold) or not switch >= 0:
         raise ValueError("label_decode: N >= 1, 1 <= k <= 32, 1 <= n_videos <= N, threshold finite, switch in [0, +inf]")
@@ -615,21 +607,46 @@ def label_decode(top_score, top_label, v_off, threshold, switch, *, out=None, ws
             or not dec_l.is_contiguous() or not dec_s.is_contiguous():
         raise ValueError("label_decode: out is (dec_label int32 [N], dec_score f32 [N]), contiguous")
     lib = _lib.lib()
-    need = lib.tan_label_decode_ws_bytes(N, k)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
-        raise ValueError("label_decode: ws is uint8 of at least label_decode_ws_bytes(N, k) bytes")
+    ws = _scratch(ws, lib.tan_label_decode_ws_bytes(N, k), dev, "label_decode: ws is uint8 of at least label_decode_ws_bytes(N, k) bytes")
     _lib.check(lib.tan_label_decode(_f32(top_score), _ptr(top_label), k, N, _ptr(v_off), nv, threshold, switch, _ptr(dec_l), _f32(dec_s),
                                     _ptr(ws), _stream()), "tan_label_decode")
     return dec_l, dec_s
 
 
-def local_align_ws_bytes(P, sum_V):
-    n = _lib.lib().tan_local_align_ws_bytes(P, sum_V)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_local_align_ws_bytes({P}, {sum_V}): bad argument")
-    return n
+def _align_args(what, x, x_off, table, theta, skew, sum_V, path_off=(), check_table=False):
+    """The checks that `local_align` and `local_align_path` share, in their order: (P, theta, skew, sum_V).  path_off: a 1-tuple from
+    `local_align_path`; check_table: `local_align`'s option.  Without sum_V the table's last entry is read back."""
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError(f"{what}: x is f32 [n_x], contiguous, n_x >= 1")
+    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
+        raise ValueError(f"{what}: x_off is int64 [P], contiguous, P >= 1")
+    P = x_off.numel()
+    if table.dtype != torch.int32 or table.shape != (P, 3) or not table.is_contiguous():
+        raise ValueError(f"{what}: table is int32 [P, 3] = (m, V, first boundary slot), contiguous")
+    for po in path_off:
+        if po.dtype != torch.int64 or po.shape != (P, 2) or not po.is_contiguous():
+            raise ValueError(f"{what}: path_off is int64 [P, 2] = (first map row, first trace entry), contiguous")
+    theta, skew = float(theta), float(skew)
+    if not math.isfinite(theta) or not (skew >= 0 and math.isfinite(skew)):
+        raise ValueError(f"{what}: theta finite, skew in [0, +inf)")
+    if check_table or sum_V is None:
+        t = (table if check_table else table[-1:]).cpu().long()
+        if check_table and (int(t[0, 2]) != 0 or bool((t[:, 1] < 1).any()) or not torch.equal(t[1:, 2], torch.cumsum(t[:, 1], 0)[:-1])):
+            raise ValueError(f"{what}: the table's third column is the running sum of its V (from 0, every V >= 1)")
+        sum_V = int(t[-1, 1] + t[-1, 2]) if sum_V is None else sum_V
+    sum_V = int(sum_V)
+    if not P <= sum_V < 2 ** 31:
+        raise ValueError(f"{what}: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
+    return P, theta, skew, sum_V
+
+
+def _align_out(what, out, P, dev, more=""):
+    """(score f32 [P], span int32 [P, 5]): the pair `out`, checked, or fresh ones; more: what else the caller's `out` holds"""
+    score, span = (torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, 5, dtype=torch.int32, device=dev)) if out is None else out
+    if score.dtype != torch.float32 or span.dtype != torch.int32 or score.shape != (P,) or span.shape != (P, 5) \
+            or not score.is_contiguous() or not span.is_contiguous():
+        raise ValueError(f"{what}: out is (score f32 [P], span int32 [P, 5]{more}), contiguous")
+    return score, span
 
 
 def local_align(x, x_off, table, theta, skew, *, sum_V=None, check_table=False, out=None, ws=None):
@@ -644,46 +661,14 @@ def local_align(x, x_off, table, theta, skew, *, sum_V=None, check_table=False, 
     check_table: verify on the host (one synchronisation) that the slots are the running sum of V, so no two entries share one --
     otherwise that is the caller's contract: overlapping slots stay in bounds but give wrong results for strips beyond the first.
     out: caller-owned (score, span) instead of fresh ones; ws: scratch (uint8, >= local_align_ws_bytes(P, sum_V))."""
-    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
-        raise ValueError("local_align: x is f32 [n_x], contiguous, n_x >= 1")
-    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
-        raise ValueError("local_align: x_off is int64 [P], contiguous, P >= 1")
-    P, dev = x_off.numel(), x.device
-    if table.dtype != torch.int32 or table.shape != (P, 3) or not table.is_contiguous():
-        raise ValueError("local_align: table is int32 [P, 3] = (m, V, first boundary slot), contiguous")
-    theta, skew = float(theta), float(skew)
-    if not math.isfinite(theta) or not (skew >= 0 and math.isfinite(skew)):
-        raise ValueError("local_align: theta finite, skew in [0, +inf)")
-    if check_table or sum_V is None:
-        t = table.cpu().long()
-        if check_table and (int(t[0, 2]) != 0 or bool((t[:, 1] < 1).any()) or not torch.equal(t[1:, 2], torch.cumsum(t[:, 1], 0)[:-1])):
-            raise ValueError("local_align: the table's third column is the running sum of its V (from 0, every V >= 1)")
-        sum_V = int(t[-1, 1] + t[-1, 2]) if sum_V is None else sum_V
-    sum_V = int(sum_V)
-    if not P <= sum_V < 2 ** 31:
-        raise ValueError("local_align: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
-    if out is None:
-        out = (torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, 5, dtype=torch.int32, device=dev))
-    score, span = out
-    if score.dtype != torch.float32 or span.dtype != torch.int32 or score.shape != (P,) or span.shape != (P, 5) \
-            or not score.is_contiguous() or not span.is_contiguous():
-        raise ValueError("local_align: out is (score f32 [P], span int32 [P, 5]), contiguous")
+    P, theta, skew, sum_V = _align_args("local_align", x, x_off, table, theta, skew, sum_V, check_table=check_table)
+    score, span = _align_out("local_align", out, P, x.device)
     lib = _lib.lib()
-    need = lib.tan_local_align_ws_bytes(P, sum_V)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
-        raise ValueError("local_align: ws is uint8 of at least local_align_ws_bytes(P, sum_V) bytes")
+    ws = _scratch(ws, lib.tan_local_align_ws_bytes(P, sum_V), x.device,
+                  "local_align: ws is uint8 of at least local_align_ws_bytes(P, sum_V) bytes")
     _lib.check(lib.tan_local_align(_f32(x), x.numel(), _ptr(x_off), _ptr(table), P, sum_V, theta, skew, _f32(score), _ptr(span), _ptr(ws),
                                    _stream()), "tan_local_align")
     return score, span
-
-
-def local_align_path_ws_bytes(P, sum_V, n_trace):
-    n = _lib.lib().tan_local_align_path_ws_bytes(P, sum_V, n_trace)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_local_align_path_ws_bytes({P}, {sum_V}, {n_trace}): bad argument")
-    return n
 
 
 def local_align_path(x, x_off, table, theta, skew, path_off, *, sum_V=None, n_map, n_trace, out=None, ws=None):
@@ -695,43 +680,21 @@ def local_align_path(x, x_off, table, theta, skew, path_off, *, sum_V=None, n_ma
     a_last and (-1, -1) elsewhere.  A table entry that breaks the limits, or whose map rows or trace entries leave [0, n_map) /
     [0, n_trace), gives the empty result and its map rows are NOT written.
     out: caller-owned (score, span, qmap); ws: scratch (uint8, >= local_align_path_ws_bytes(P, sum_V, n_trace))."""
-    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
-        raise ValueError("local_align_path: x is f32 [n_x], contiguous, n_x >= 1")
-    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
-        raise ValueError("local_align_path: x_off is int64 [P], contiguous, P >= 1")
-    P, dev = x_off.numel(), x.device
-    if table.dtype != torch.int32 or table.shape != (P, 3) or not table.is_contiguous():
-        raise ValueError("local_align_path: table is int32 [P, 3] = (m, V, first boundary slot), contiguous")
-    if path_off.dtype != torch.int64 or path_off.shape != (P, 2) or not path_off.is_contiguous():
-        raise ValueError("local_align_path: path_off is int64 [P, 2] = (first map row, first trace entry), contiguous")
-    theta, skew = float(theta), float(skew)
-    if not math.isfinite(theta) or not (skew >= 0 and math.isfinite(skew)):
-        raise ValueError("local_align_path: theta finite, skew in [0, +inf)")
-    if sum_V is None:
-        t = table[-1].cpu()
-        sum_V = int(t[1]) + int(t[2])
-    sum_V, n_map, n_trace = int(sum_V), int(n_map), int(n_trace)
-    if not P <= sum_V < 2 ** 31:
-        raise ValueError("local_align_path: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
+    P, theta, skew, sum_V = _align_args("local_align_path", x, x_off, table, theta, skew, sum_V, (path_off,))
+    n_map, n_trace = int(n_map), int(n_trace)
     if not 1 <= n_map < 2 ** 31 or n_trace < 1:
         raise ValueError("local_align_path: 1 <= n_map < 2^31, n_trace >= 1")
+    pair, qmap = (None, None) if out is None else ((out[0], out[1]), *out[2:])
+    score, span = _align_out("local_align_path", pair, P, x.device, ", qmap")
     if out is None:
-        out = (torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, 5, dtype=torch.int32, device=dev),
-               torch.empty(n_map, 2, dtype=torch.int32, device=dev))
-    score, span, qmap = out
-    if score.dtype != torch.float32 or span.dtype != torch.int32 or score.shape != (P,) or span.shape != (P, 5) \
-            or not score.is_contiguous() or not span.is_contiguous():
-        raise ValueError("local_align_path: out is (score f32 [P], span int32 [P, 5], qmap), contiguous")
+        qmap = torch.empty(n_map, 2, dtype=torch.int32, device=x.device)
     if qmap.dtype != torch.int32 or qmap.shape != (n_map, 2) or not qmap.is_contiguous():
         raise ValueError("local_align_path: qmap is int32 [n_map, 2], contiguous")
     lib = _lib.lib()
     need = lib.tan_local_align_path_ws_bytes(P, sum_V, n_trace)
     if need < 0:
         raise ValueError("local_align_path: n_trace out of range")
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
-        raise ValueError("local_align_path: ws is uint8 of at least local_align_path_ws_bytes(P, sum_V, n_trace) bytes")
+    ws = _scratch(ws, need, x.device, "local_align_path: ws is uint8 of at least local_align_path_ws_bytes(P, sum_V, n_trace) bytes")
     _lib.check(lib.tan_local_align_path(_f32(x), x.numel(), _ptr(x_off), _ptr(table), P, sum_V, theta, skew, _ptr(path_off), n_map, n_trace,
                                         _f32(score), _ptr(span), _ptr(qmap), _ptr(ws), _stream()), "tan_local_align_path")
     return score, span, qmap
@@ -754,13 +717,6 @@ def moment_extent(tq, vn, v_off, top_score, top_row, top_video, width, *, q_scal
     _call("moment_extent", tq, q_scale, vn, v_scale, Q, N, tq.shape[1], _ptr(v_off), nv, k, _f32(top_score), _ptr(top_row),
           _ptr(top_video), float(width), _ptr(start), _ptr(end))
     return start, end
-
-
-def sequence_topk_ws_bytes(n_seq, N, k):
-    n = _lib.lib().tan_sequence_topk_ws_bytes(n_seq, N, k)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_sequence_topk_ws_bytes({n_seq}, {N}, {k}): bad argument")
-    return n
 
 
 def _sequence_args(what, tq, vn, s_off, v_off, q_scale, v_scale, check_offsets):
@@ -805,13 +761,6 @@ def sequence_scores(tq, vn, s_off, v_off, hits, x_off, x, *, q_scale=None, v_sca
     _call("sequence_scores", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(s_off), ns, _ptr(v_off), nv, _ptr(hits), _ptr(x_off), P,
           _f32(x), x.numel())
     return x
-
-
-def clip_topk_ws_bytes(n_clip, N, k):
-    n = _lib.lib().tan_clip_topk_ws_bytes(n_clip, N, k)
-    if n < 0:
-        raise _lib.TanHipError(f"tan_clip_topk_ws_bytes({n_clip}, {N}, {k}): bad argument")
-    return n
 
 
 def clip_topk(tq, vn, c_off, v_off, k, *, q_scale=None, v_scale=None, splits=0, check_offsets=False, out=None, ws=None):

@@ -1,0 +1,301 @@
+"""The command line (`python -m temporalalignnet_amd.search`; synopsis: the package docstring): one parser, and per subcommand one
+function that checks its arguments (`_check_*`, argparse errors: exit code 2) and one that runs it (`_run_*`: the exit code)."""
+import argparse
+import sys
+
+import numpy as np
+import torch
+
+from . import __doc__ as _PACKAGE_DOC                # its first paragraph is the parser's description
+from ..infer_align import build_aligner, make_embed_text, read_corpus
+from .annotation import annotate, write_per_second_csv, write_segments_csv
+from .index import E4M3, ShardedIndex, VideoIndex, build_index
+from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
+from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, search_clips, search_copies
+
+
+def _parser():
+    # prog: the usage line of `python -m temporalalignnet_amd.search` as it has always read, not "__main__.py"
+    ap = argparse.ArgumentParser(prog="search.py", description=_PACKAGE_DOC.split("\n\n")[0],
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    for name in ("index", "query", "annotate"):
+        p = sub.add_parser(name)
+        p.add_argument("--checkpoint", required=True)
+        p.add_argument("--vocab", required=True, help="s3d_dict.npy (the Word2Vec vocabulary)")
+        p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
+        p.add_argument("--model", choices=("init", "cotrain"), default="init")
+    p = sub.choices["index"]
+    p.add_argument("--feature-dir", required=True)
+    p.add_argument("--asr-json", required=True)
+    p.add_argument("--vlen-csv", required=True)
+    p.add_argument("--out", required=True, help="index file (.npz)")
+    p.add_argument("--index-dtype", choices=("bf16", "fp32", "e4m3"), default=None,
+                   help="row format of the index (default: --dtype); e4m3: 516 bytes per second instead of 1 KiB")
+    p.add_argument("--keep-stem", action="store_true",
+                   help="also keep video_pre_proj of every second (what `query --rerank` needs): + 1 KiB per second in bf16")
+    p.add_argument("--worker-id", type=int, default=0)
+    p.add_argument("--num-workers", type=int, default=1)
+    for name in ("query", "annotate"):
+        _index_options(sub.choices[name])
+    p = sub.choices["annotate"]
+    p.add_argument("--labels", required=True, metavar="FILE", help="the vocabulary: one label text per line, blank lines skipped")
+    p.add_argument("-k", type=int, default=1, help="labels kept per second, 1 to 32 (segments use the best one)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="a second whose best score is below this is background (default: none is)")
+    p.add_argument("--min-len", type=int, default=None, help="drop segments shorter than this many seconds (default 1)")
+    p.add_argument("--smooth", type=float, default=None, metavar="PENALTY",
+                   help="decode every video's labels with this penalty per label change (>= 0; needs a finite --threshold, "
+                        "use -k 5 or more): segments bridge short dips and flickers")
+    p.add_argument("--per-second", action="store_true", help="write vid,second,label,score for the k labels of every second instead")
+    p.add_argument("--out", required=True, metavar="CSV", help="vid,start,end,label,peak,score: one row per segment")
+    p = sub.choices["query"]
+    p.add_argument("-k", type=int, default=10)
+    p.add_argument("--moments", action="store_true",
+                   help="the k best distinct videos, each as `sentence vid start end second score` (seconds of the video)")
+    p.add_argument("--width", type=float, default=None,
+                   help=f"with --moments: a moment extends while the score stays within this of its peak (default {TEMPERATURE})")
+    p.add_argument("--sequence", action="store_true",
+                   help="the sentences are ONE ordered list of steps: the k videos that show them in order, each as "
+                        "`vid score t_0 ... t_{m-1}` (seconds of the video, non-decreasing)")
+    p.add_argument("--rerank", action="store_true",
+                   help="two stages: the --pool best distinct videos of the dual sweep rescored by the joint encoder, the k best as "
+                        "`sentence vid second score confidence alignability dual_second dual_score` (needs index --keep-stem)")
+    p.add_argument("--pool", type=int, default=None, help="with --rerank: candidates per sentence, 1 to 32 (default 32)")
+    p.add_argument("--only", action="append", default=None, metavar="VID", help="search only this video (repeatable)")
+    p.add_argument("--only-file", default=None, metavar="PATH", help="search only the videos listed here, one vid per line")
+    p.add_argument("--exclude", action="append", default=None, metavar="VID", help="leave this video out (repeatable)")
+    p.add_argument("--exclude-file", default=None, metavar="PATH", help="leave out the videos listed here, one vid per line")
+    p.add_argument("--within", action="append", default=None, metavar="VID:FIRST-LAST",
+                   help="search this video only between these seconds, inclusive (repeatable; other videos stay whole)")
+    p.add_argument("sentences", nargs="+")
+    p = sub.add_parser("similar", help="where else in the corpus a piece of an indexed video appears (no checkpoint, no model)")
+    _index_options(p)
+    p.add_argument("--clip", action="append", required=True, metavar="VID:FIRST-LAST",
+                   help=f"these seconds of this video of the index, inclusive, at most {MAX_CLIP_SECONDS} (repeatable)")
+    p.add_argument("-k", type=int, default=10)
+    p.add_argument("--keep-source", action="store_true", help="also list the video the clip was cut from (left out by default)")
+    p.add_argument("--align", action="store_true",
+                   help=f"find re-timed or re-cut copies: the best local alignment of the clip (then up to {MAX_ALIGN_SECONDS} seconds) "
+                        "with each candidate video, as `vid start end score q_start q_end cells` (needs --threshold)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="with --align: a second of the alignment gains its score minus this (no default: it depends on the features)")
+    p.add_argument("--skew", type=float, default=None, help="with --align: the price of a step along one video alone, >= 0 (default 0)")
+    p.add_argument("--pool", type=int, default=None, help="with --align: candidate videos per piece, 1 to 32 (default 32)")
+    p.add_argument("--piece", type=int, default=None,
+                   help=f"with --align: the clip is cut into pieces of this many seconds for the candidate sweep, 1 to {MAX_CLIP_SECONDS} "
+                        "(default 16)")
+    p.add_argument("--map", default=None, metavar="OUT.csv",
+                   help="with --align: write the time map of every hit, one row `query,vid,query_second,first,last` per aligned second "
+                        "of the clip (query_second on the clip's own video timeline; first..last the seconds of vid that show it)")
+    p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
+    p.add_argument("--out", required=True, help="index file (.npz)")
+    p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
+    return ap
+
+
+def _index_options(p):
+    """--index [--shard ...] [--host-resident]: what `query`, `annotate` and `similar` load their index from (`_load_index`)"""
+    p.add_argument("--index", required=True)
+    p.add_argument("--shard", action="append", default=None, metavar="PATH",
+                   help="a further index file searched together with --index, in the order given (repeatable)")
+    p.add_argument("--host-resident", action="store_true",
+                   help="keep the rows in pinned host memory and stream them through the card: for an index larger than the card")
+
+
+def parse_args(argv=None):
+    ap = _parser()
+    a = ap.parse_args(argv)
+    _CHECKS[a.cmd](ap, a)
+    return a
+
+
+def _refuse(ap, *cases):
+    """`ap.error` (exit code 2) with the text of the first case (holds, text) that holds"""
+    for holds, text in cases:
+        if holds:
+            ap.error(text)
+
+
+def _check_index(ap, a):
+    _refuse(ap, (not 0 <= a.worker_id < a.num_workers, "--worker-id must lie in [0, --num-workers)"))
+
+
+def _check_query(ap, a):
+    filtered = any(x is not None for x in (a.only, a.only_file, a.exclude, a.exclude_file, a.within))
+    _refuse(ap,
+            (a.sequence and (a.moments or a.width is not None), "--sequence does not go with --moments / --width"),
+            (a.sequence and len(a.sentences) > 32, "--sequence takes at most 32 sentences"),
+            (a.rerank and (a.sequence or a.moments), "--rerank does not go with --sequence / --moments"),
+            (a.rerank and (a.shard or a.host_resident), "--rerank does not go with --shard / --host-resident; merge the index files"),
+            (a.pool is not None and not a.rerank, "--pool needs --rerank"),
+            (a.pool is not None and not 1 <= a.pool <= 32, "--pool must lie in [1, 32]"),
+            (a.width is not None and not a.moments, "--width needs --moments"),
+            (a.width is not None and not a.width >= 0, "--width must be >= 0"),
+            (filtered and a.sequence, "--only / --exclude / --within do not go with --sequence"),
+            (a.within is not None and a.rerank, "--within does not go with --rerank (the joint window is cut around the dual second)"))
+    try:
+        a.within = None if a.within is None else [parse_within(w) for w in a.within]
+    except ValueError as e:
+        ap.error(str(e))
+
+
+def _check_annotate(ap, a):
+    smooth = a.smooth is not None
+    _refuse(ap,
+            (not 1 <= a.k <= 32, "-k must lie in [1, 32]"),
+            (a.per_second and (a.threshold is not None or a.min_len is not None), "--per-second does not go with --threshold / --min-len"),
+            (a.threshold is not None and a.threshold != a.threshold, "--threshold must not be NaN"),
+            (a.min_len is not None and a.min_len < 1, "--min-len must be >= 1"),
+            (smooth and a.per_second, "--smooth does not go with --per-second"),
+            (smooth and not a.smooth >= 0, "--smooth must be >= 0"),
+            (smooth and (a.threshold is None or not np.isfinite(a.threshold)), "--smooth needs a finite --threshold"))
+
+
+def _check_similar(ap, a):
+    _refuse(ap,
+            (not a.align and any(x is not None for x in (a.threshold, a.skew, a.pool, a.piece)),
+             "--threshold / --skew / --pool / --piece need --align"),
+            (a.map is not None and not a.align, "--map needs --align"),
+            (a.align and (a.threshold is None or not np.isfinite(a.threshold)), "--align needs a finite --threshold"),
+            (a.align and a.skew is not None and not (a.skew >= 0 and np.isfinite(a.skew)), "--skew must be >= 0 and finite"),
+            (a.align and a.pool is not None and not 1 <= a.pool <= 32, "--pool must lie in [1, 32]"),
+            (a.align and a.piece is not None and not 1 <= a.piece <= MAX_CLIP_SECONDS, f"--piece must lie in [1, {MAX_CLIP_SECONDS}]"),
+            (a.align and a.k < 1, "-k must be >= 1"),
+            (not a.align and not 1 <= a.k <= (32 if a.keep_source else 31), "-k must lie in [1, 31], or [1, 32] with --keep-source"))
+    try:
+        a.clip = [parse_within(c, "--clip") for c in a.clip]
+    except ValueError as e:
+        ap.error(str(e))
+    most = MAX_ALIGN_SECONDS if a.align else MAX_CLIP_SECONDS
+    for vid, first, last in a.clip:
+        if first > last:
+            ap.error(f"--clip {vid}:{first}-{last}: FIRST is after LAST")
+        if last - first + 1 > most:
+            ap.error(f"--clip {vid}:{first}-{last} holds {last - first + 1} seconds; cut it into clips of at most {most} seconds")
+
+
+def parse_within(text, option="--within"):
+    """'VID:FIRST-LAST' -> (vid, first, last); the vid may hold colons itself"""
+    vid, sep, span = text.rpartition(":")
+    first, dash, last = span.partition("-")
+    if not sep or not vid or not dash or not first.isdigit() or not last.isdigit():
+        raise ValueError(f"{option} takes VID:FIRST-LAST (seconds, inclusive), not {text!r}")
+    return vid, int(first), int(last)
+
+
+def _read_vids(path):
+    with open(path) as f:
+        return [line.strip() for line in f if line.strip()]
+
+
+def restrict_from_args(index, a):
+    """The `RowFilter` of `query`'s --only / --only-file / --exclude / --exclude-file / --within, or None without any of them"""
+    only = (a.only or []) + (_read_vids(a.only_file) if a.only_file else [])
+    exclude = (a.exclude or []) + (_read_vids(a.exclude_file) if a.exclude_file else [])
+    if not (only or exclude or a.within or a.only is not None or a.only_file):
+        return None
+    return index.restrict(videos=only if (a.only is not None or a.only_file) else None, exclude=exclude or None, windows=a.within)
+
+
+def _load_index(a):
+    """--index [--shard ...] [--host-resident] -> a `VideoIndex` or a `ShardedIndex`"""
+    if a.shard or a.host_resident:
+        return ShardedIndex.load([a.index] + (a.shard or []), resident="host" if a.host_resident else "device")
+    return VideoIndex.load(a.index)
+
+
+def _load_searcher(a):
+    """(the aligner, its sentence embedder, the index) of `query` and `annotate`, loaded in this order"""
+    vocab = np.load(a.vocab)
+    model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
+    from ..word2vec_model import Word2VecTokenizer
+    return model, make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab)), _load_index(a)
+
+
+def _run_merge(a):
+    idx = VideoIndex.concat([VideoIndex.load(p, device="cpu") for p in a.inputs])
+    idx.save(a.out)
+    print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos from {len(a.inputs)} files", file=sys.stderr)
+    return 0
+
+
+def _run_index(a):
+    model = build_aligner(a.checkpoint, np.load(a.vocab), a.model, a.dtype)
+    corpus = read_corpus(a.feature_dir, a.asr_json, a.vlen_csv, a.worker_id, a.num_workers)
+    idx = build_index(model, corpus, dtype={"bf16": torch.bfloat16, "fp32": torch.float32, "e4m3": E4M3}[a.index_dtype or a.dtype],
+                      keep_stem=a.keep_stem)
+    idx.save(a.out)
+    print(f"{a.out}: {len(idx)} seconds of {len(idx.vids)} videos", file=sys.stderr)
+    return 0
+
+
+def _run_similar(a):
+    idx = _load_index(a)
+    try:
+        if a.align:
+            found = search_copies(idx, a.clip, a.k, 32 if a.pool is None else a.pool, 16 if a.piece is None else a.piece,
+                                  threshold=a.threshold, skew=a.skew or 0.0, exclude_source=not a.keep_source,
+                                  paths=a.map is not None)
+        else:
+            found = search_clips(idx, a.clip, a.k, exclude_source=not a.keep_source)
+    except ValueError as e:
+        print(f"similar: {e}", file=sys.stderr)
+        return 2
+    if a.map is not None:                              # only with --align
+        with open(a.map, "w") as f:
+            f.write("query,vid,query_second,first,last\n")
+            for (vid, first, last), hits in zip(a.clip, found):
+                for h, seconds in hits:
+                    for i, (lo, hi) in enumerate(seconds.tolist()):
+                        f.write(f"{vid}:{first}-{last},{h.vid},{first + h.q_start + i},{lo},{hi}\n")
+        found = [[h for h, _ in hits] for hits in found]
+    for hits in found:
+        for h in hits:
+            print(f"{h.vid}\t{h.start}\t{h.end}\t{h.score:.6f}" + (f"\t{h.q_start}\t{h.q_end}\t{h.cells}" if a.align else ""))
+    return 0
+
+
+def _run_annotate(a):
+    model, embed, idx = _load_searcher(a)
+    ann = annotate(idx, model, embed, _read_vids(a.labels), a.k)
+    with open(a.out, "w", newline="") as f:
+        if a.per_second:
+            write_per_second_csv(f, ann)
+        else:
+            write_segments_csv(f, ann.segments(float("-inf") if a.threshold is None else a.threshold, a.min_len or 1, switch=a.smooth))
+    print(f"{a.out}: {len(ann)} seconds of {len(ann.vids)} videos against {len(ann.labels)} labels", file=sys.stderr)
+    return 0
+
+
+def _run_query(a):
+    model, embed, idx = _load_searcher(a)
+    only = restrict_from_args(idx, a)                  # None with --sequence, which takes no filter options
+    if a.sequence:
+        for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
+            print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))
+    elif a.rerank:
+        pool = 32 if a.pool is None else a.pool
+        for sentence, hits in zip(a.sentences, search_rerank(idx, model, embed, a.sentences, min(a.k, pool), pool, restrict=only)):
+            for h in hits:
+                al = "" if h.alignability is None else f"{h.alignability:.6f}"
+                print(f"{sentence}\t{h.vid}\t{h.second}\t{h.score:.6f}\t{h.confidence:.6f}\t{al}\t{h.dual_second}\t{h.dual_score:.6f}")
+    elif a.moments:
+        width = TEMPERATURE if a.width is None else a.width
+        for sentence, hits in zip(a.sentences, search_moments(idx, model, embed, a.sentences, a.k, width, restrict=only)):
+            for m in hits:
+                print(f"{sentence}\t{m.vid}\t{m.start}\t{m.end}\t{m.second}\t{m.score:.6f}")
+    else:
+        for sentence, hits in zip(a.sentences, search(idx, model, embed, a.sentences, a.k, restrict=only)):
+            for vid, sec, score in hits:
+                print(f"{sentence}\t{vid}\t{sec}\t{score:.6f}")
+    return 0
+
+
+_CHECKS = dict(index=_check_index, query=_check_query, annotate=_check_annotate, similar=_check_similar, merge=lambda ap, a: None)
+_RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, merge=_run_merge)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    return _RUNS[a.cmd](a)

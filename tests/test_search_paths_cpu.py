@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from temporalalignnet_amd import search
+from temporalalignnet_amd import ops, search
 
 Q, K = 2, 2
 SEQUENCES = [["a"], ["b", "c", "d"]]
@@ -123,13 +123,17 @@ READ_BACKS = {"search": (2, 1), "search_moments": (2, 1), "search_sequences": (2
 @pytest.mark.parametrize("e4m3", (False, True), ids=("f32", "e4m3"))
 def test_the_searches_make_the_same_ops_calls_in_the_same_order(monkeypatch, e4m3):
     rec = RecordingOps()
-    monkeypatch.setattr(search, "ops", rec)
+    # every module of the package reaches the wrappers as attributes of the one `ops` module: the stub's functions go there
+    for name in dir(rec):
+        if not name.startswith("_") and callable(getattr(rec, name)):
+            monkeypatch.setattr(ops, name, getattr(rec, name))
 
     def zero_queries(index, model, embed_text, queries, text_batch=1024):
         n = len(list(queries))
         return (torch.zeros(n, 512, dtype=torch.uint8), torch.ones(n)) if index.e4m3 else torch.zeros(n, 512)
 
-    monkeypatch.setattr(search, "query_features", zero_queries)
+    for module in (search.text, search.annotation):                        # where the searches and `annotate` resolve it
+        monkeypatch.setattr(module, "query_features", zero_queries)
     read_backs, cpu = [], torch.Tensor.cpu
     monkeypatch.setattr(torch.Tensor, "cpu", lambda t, *a, **kw: read_backs.append(1) or cpu(t, *a, **kw))
 

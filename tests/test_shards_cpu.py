@@ -154,6 +154,41 @@ def test_sharded_index_bookkeeping():
         ShardedIndex(parts, resident="disk")
 
 
+def test_hit_coordinates_match_a_walk_over_the_concatenation():
+    """What the searches map their shard-local hits with: every (shard, row) -> (video, second) and every (shard, video) -> (global
+    video, first row), against a brute-force walk over `VideoIndex.concat`'s v_off."""
+    from temporalalignnet_amd.search import ShardedIndex, VideoIndex
+    from temporalalignnet_amd.search.index import _locate_videos
+    vlens = ([5, 3], [9], [2, 2])
+    parts = [_index(v, "f32", 40 + n) for n, v in enumerate(vlens)]    # tag "v": shards 0 and 2 share the vid strings v0, v1
+    sh, whole = ShardedIndex(parts, resident="device"), VideoIndex.concat(parts)
+    assert whole.vids == ["v0", "v1", "v0", "v0", "v1"] and whole.v_off.tolist() == [0, 5, 8, 17, 19, 21]
+    walk = []                                                          # global row -> (video number, second, the video's first row)
+    for v in range(len(whole.vids)):
+        walk += [(v, g - int(whole.v_off[v]), int(whole.v_off[v])) for g in range(int(whole.v_off[v]), int(whole.v_off[v + 1]))]
+    assert len(walk) == len(whole) == len(sh) == 21
+    g = gv = 0
+    for s, lens in enumerate(vlens):
+        for row in range(sum(lens)):                                   # every row: each video's and each shard's first and last
+            for index, at in ((sh, (s, row)), (whole, (g,))):
+                v, sec = index.locate(*(np.array([a]) for a in at))
+                assert (int(v[0]), int(sec[0])) == walk[g][:2], (s, row)
+            g += 1
+        for video in range(len(lens)):
+            for index, at, base in ((sh, (s, video), int(sh.row_base[s])), (whole, (0, gv), 0)):
+                v, first = _locate_videos(index, *(np.array([a]) for a in at))
+                assert (int(v[0]), base + int(first[0])) == (gv, int(whole.v_off[gv])), (s, video)
+            assert walk[int(whole.v_off[gv])] == (gv, 0, int(whole.v_off[gv]))
+            gv += 1
+    assert (g, gv) == (21, 5)
+    # whole arrays at once, as the searches pass their [Q, k] lists
+    shard, video = np.array([[0, 2], [1, 2]]), np.array([[1, 0], [0, 1]])
+    v, first = _locate_videos(sh, shard, video)
+    assert v.tolist() == [[1, 3], [2, 4]] and first.tolist() == [[5, 0], [0, 2]]
+    v, sec = sh.locate(shard, first + 1)
+    assert v.tolist() == [[1, 3], [2, 4]] and sec.tolist() == [[1, 1], [1, 1]]
+
+
 def test_search_rerank_refuses_a_sharded_index():
     from temporalalignnet_amd import search
     sh = search.ShardedIndex([_index([4], "bf16", 1, stem="bf16")])

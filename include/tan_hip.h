@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -1175,6 +1175,43 @@ int tan_local_align(const float* x, long n_x, const long* x_off, const int* tabl
 long tan_local_align_path_ws_bytes(long P, long sum_V, long n_trace);
 int tan_local_align_path(const float* x, long n_x, const long* x_off, const int* table, long P, long sum_V, float theta, float skew,
                          const long* path_off, long n_map, long n_trace, float* score, int* span, int* qmap, void* ws, void* stream);
+
+/* ---- step discovery: the update half of spherical k-means over the index's rows (`search.discover_steps`) ----
+ * The assignment half is tan_label_topk / _e4m3 with the centroids as the labels and k = 1.
+ * tan_cluster_accumulate: Vn [N, 512] index rows in the formats of tan_label_topk (TAN_F32, TAN_BF16; 16-byte aligned), assign
+ *   int32 [N]: every row's cluster, order int32 [N]: a permutation of the rows, sums [K, 512] `long` (64-bit, 8-byte aligned).
+ *   With v the element as f32 (bf16 widened) and q(n, j) = (long) round-to-nearest-even(v * 2^30) -- the f32 multiply by a power
+ *   of two is exact, the conversion is __float2ll_rn --:
+ *       sums[assign[n]][j] += q(n, j)      for every row n, in wrapping 64-bit integer arithmetic.
+ *   The kernel ADDS: the caller zeroes sums once, and several launches (one per shard of an index) add into the same buffer.
+ *   Integer addition is associative, so the result is the same bits for EVERY permutation `order`, for any split of the rows over
+ *   launches and from run to run, although the flushes are atomics.  `order` only decides how many atomics are issued: a wave
+ *   walks tan_cluster_slab_rows() = 256 consecutive positions of it and flushes its registers when the cluster changes, so with
+ *   order sorted by cluster a launch issues at most (N / 256 + K) * 512 64-bit atomics -- 16 bytes per row and 4 KiB per cluster,
+ *   against the 1 KiB (bf16) it reads per row.
+ *   Contract: |v| <= 2 (index rows are unit vectors), so fewer than 2^31 rows cannot overflow a sum; the image q is exact for every
+ *   bf16 value of magnitude >= 2^-23.  A row whose assign lies outside [0, K), or a position whose order lies outside [0, N), is
+ *   skipped.  A non-finite v contributes an unspecified value; nothing is read or written out of bounds whatever assign and order
+ *   hold.  1 <= N < 2^31, 1 <= K < 2^31; another width than 512, an unknown dtype, a NULL pointer, bad sizes or alignment:
+ *   TAN_ERR_BAD_ARG, nothing launched.
+ * tan_cluster_accumulate_e4m3: the same over the e4m3 codes and per-row power-of-two scales of tan_rank_topk_e4m3 (v_scale [N]);
+ *   v = decode(code) * v_scale[n], one f32 multiply.
+ * tan_cluster_centroids: sums [K, 512] as above, counts int32 [K]: the rows of every cluster, prev f32 [K, 512] -> cent f32
+ *   [K, 512], cohesion f32 [K].  One wave per cluster; every step is ONE correctly rounded f32 operation, never contracted:
+ *       x_j    = (float) sums[c][j] * 2^-30            (int64 -> f32 round to nearest even; the scaling is exact)
+ *       norm2  : lane l = 0 .. 63 adds x_j * x_j over j = l, l + 64, ..., l + 448 in that order (to 0), then the 64 partial sums
+ *                are folded by an xor butterfly over the lane distances 32, 16, 8, 4, 2, 1: p[l] = p[l] + p[l ^ d]
+ *       norm   = sqrt(norm2);   cent[c][j] = x_j / norm  (a division, not a reciprocal);   cohesion[c] = norm / (float) counts[c]
+ *   cohesion is the mean resultant length of the cluster's rows, in [0, 1] for unit rows: 1 when they all coincide.  If
+ *   counts[c] <= 0, or norm is 0 or not finite: cent[c] = prev[c] bit for bit and cohesion[c] = 0 -- an empty cluster keeps its
+ *   centroid.  cent may be prev itself.  1 <= K < 2^31; another width, a NULL pointer: TAN_ERR_BAD_ARG, nothing launched.        */
+int tan_cluster_slab_rows(void);
+int tan_cluster_accumulate(const void* Vn, int dtype, long N, int C, const int* assign, const int* order, long K, long* sums,
+                           void* stream);
+int tan_cluster_accumulate_e4m3(const void* Vn, const float* v_scale, long N, int C, const int* assign, const int* order, long K,
+                                long* sums, void* stream);
+int tan_cluster_centroids(const long* sums, const int* counts, const float* prev, long K, int C, float* cent, float* cohesion,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -613,6 +613,60 @@ def label_decode(top_score, top_label, v_off, threshold, switch, *, out=None, ws
     return dec_l, dec_s
 
 
+CLUSTER_SLAB_ROWS = 256           # tan_cluster_slab_rows(): the positions of `order` one wave of tan_cluster_accumulate walks
+
+
+def _is(t, dtype, shape):
+    return t is not None and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+
+
+def cluster_accumulate(vn, assign, order, sums, v_scale=None):
+    """sums[assign[n]] += the fixed-point image of row n, for every row (tan_cluster_accumulate / _e4m3; the exact definition is in
+    include/tan_hip.h): vn [N, 512] f32 / bf16 rows, or uint8 e4m3 codes with v_scale f32 [N]; assign int32 [N]: the rows'
+    clusters (a row outside [0, K) is skipped); order int32 [N]: a permutation of the rows, which decides only how many atomics
+    are issued (sorted by cluster: the fewest); sums int64 [K, 512], caller-owned: the call ADDS, so zero it once and let one call
+    per shard add into it.  The result is the same bits for every order and every split of the rows over calls.  Returns sums."""
+    if vn.dim() != 2 or vn.shape[1] != 512 or vn.shape[0] < 1 or not vn.is_contiguous():
+        raise ValueError("cluster_accumulate: vn is [N, 512], contiguous, N >= 1")
+    if vn.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+        raise TypeError("cluster_accumulate: f32 or bf16 rows, or uint8 e4m3 codes")
+    N, e4m3 = vn.shape[0], vn.dtype == torch.uint8
+    if (v_scale is not None) != e4m3 or (e4m3 and not _is(v_scale, torch.float32, (N,))):
+        raise ValueError("cluster_accumulate: v_scale f32 [N], contiguous, goes with uint8 e4m3 codes, and only with them")
+    if not _is(assign, torch.int32, (N,)) or not _is(order, torch.int32, (N,)):
+        raise ValueError("cluster_accumulate: assign and order are int32 [N], contiguous")
+    if sums is None or sums.dtype != torch.int64 or sums.dim() != 2 or sums.shape[0] < 1 or sums.shape[1] != 512 or not sums.is_contiguous():
+        raise ValueError("cluster_accumulate: sums is int64 [K, 512], contiguous, K >= 1")
+    K, lib = sums.shape[0], _lib.lib()
+    if e4m3:
+        _lib.check(lib.tan_cluster_accumulate_e4m3(_ptr(vn), _f32(v_scale), N, 512, _ptr(assign), _ptr(order), K, _ptr(sums), _stream()),
+                   "tan_cluster_accumulate_e4m3")
+    else:
+        _lib.check(lib.tan_cluster_accumulate(_ptr(vn), _dt(vn), N, 512, _ptr(assign), _ptr(order), K, _ptr(sums), _stream()),
+                   "tan_cluster_accumulate")
+    return sums
+
+
+def cluster_centroids(sums, counts, prev, *, out=None):
+    """The new unit centroids of `cluster_accumulate`'s sums (tan_cluster_centroids; the exact definition is in include/tan_hip.h):
+    sums int64 [K, 512], counts int32 [K]: the rows of every cluster, prev f32 [K, 512].  Returns (cent f32 [K, 512], cohesion f32
+    [K]: the mean resultant length of the cluster's rows); an empty cluster, or one whose rows cancel, keeps prev's centroid bit
+    for bit with cohesion 0.  out: caller-owned (cent, cohesion) instead of fresh ones; cent may be prev."""
+    if sums.dtype != torch.int64 or sums.dim() != 2 or sums.shape[0] < 1 or sums.shape[1] != 512 or not sums.is_contiguous():
+        raise ValueError("cluster_centroids: sums is int64 [K, 512], contiguous, K >= 1")
+    K, dev = sums.shape[0], sums.device
+    if not _is(counts, torch.int32, (K,)) or not _is(prev, torch.float32, (K, 512)):
+        raise ValueError("cluster_centroids: counts is int32 [K] and prev f32 [K, 512], contiguous")
+    if out is None:
+        out = (torch.empty(K, 512, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.float32, device=dev))
+    cent, cohesion = out
+    if not _is(cent, torch.float32, (K, 512)) or not _is(cohesion, torch.float32, (K,)):
+        raise ValueError("cluster_centroids: out is (cent f32 [K, 512], cohesion f32 [K]), contiguous")
+    _lib.check(_lib.lib().tan_cluster_centroids(_ptr(sums), _ptr(counts), _f32(prev), K, 512, _f32(cent), _f32(cohesion), _stream()),
+               "tan_cluster_centroids")
+    return cent, cohesion
+
+
 def _align_args(what, x, x_off, table, theta, skew, sum_V, path_off=(), check_table=False):
     """The checks that `local_align` and `local_align_path` share, in their order: (P, theta, skew, sum_V).  path_off: a 1-tuple from
     `local_align_path`; check_table: `local_align`'s option.  Without sum_V the table's last entry is read back."""

@@ -125,8 +125,16 @@ def annotate(index, model, embed_text, labels, k=1):
     k = int(k)
     if not 1 <= k <= min(32, len(labels)):
         raise ValueError("annotate: k must lie in [1, min(32, len(labels))]")
+    score, label = label_lists(index, query_features(index, model, embed_text, labels), k)
+    return Annotation(label, score, labels, index.v_off, index.vids)
+
+
+def label_lists(index, tl, k, each_shard=None):
+    """(score f32, label int32) [N, k] on the index's device: the k best rows of tl -- label features in the index's row format, as
+    `query_features` makes them (an e4m3 index: (codes, scales)) -- for every row of the index, one `tan_label_topk` launch per
+    shard into the shard's slice of the outputs.  each_shard(feat, scale, score, label): called with every shard's view and its
+    slices while the shard is in its slot (`discover_steps` adds the shard's rows to its sums there)."""
     N, dev = len(index), index.device
-    tl = query_features(index, model, embed_text, labels)
     score = torch.empty(N, k, dtype=torch.float32, device=dev)
     label = torch.empty(N, k, dtype=torch.int32, device=dev)
     for s, feat, scale, _ in index.shard_views():
@@ -135,7 +143,9 @@ def annotate(index, model, embed_text, labels, k=1):
             ops.label_topk_e4m3(*tl, feat, scale, k, out=out)
         else:
             ops.label_topk(tl, feat, k, out=out)
-    return Annotation(label, score, labels, index.v_off, index.vids)
+        if each_shard is not None:
+            each_shard(feat, scale, *out)
+    return score, label
 
 
 def write_segments_csv(f, segments):

@@ -9,6 +9,7 @@ import torch
 from . import __doc__ as _PACKAGE_DOC                # its first paragraph is the parser's description
 from ..infer_align import build_aligner, make_embed_text, read_corpus
 from .annotation import annotate, write_per_second_csv, write_segments_csv
+from .cluster import MAX_CLUSTERS, StepClusters, discover_steps
 from .index import E4M3, ShardedIndex, VideoIndex, build_index
 from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
 from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, search_clips, search_copies
@@ -20,11 +21,7 @@ def _parser():
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
     for name in ("index", "query", "annotate"):
-        p = sub.add_parser(name)
-        p.add_argument("--checkpoint", required=True)
-        p.add_argument("--vocab", required=True, help="s3d_dict.npy (the Word2Vec vocabulary)")
-        p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
-        p.add_argument("--model", choices=("init", "cotrain"), default="init")
+        _model_options(sub.add_parser(name), required=name != "annotate")      # annotate --clusters takes no model
     p = sub.choices["index"]
     p.add_argument("--feature-dir", required=True)
     p.add_argument("--asr-json", required=True)
@@ -39,7 +36,9 @@ def _parser():
     for name in ("query", "annotate"):
         _index_options(sub.choices[name])
     p = sub.choices["annotate"]
-    p.add_argument("--labels", required=True, metavar="FILE", help="the vocabulary: one label text per line, blank lines skipped")
+    p.add_argument("--labels", default=None, metavar="FILE", help="the vocabulary: one label text per line, blank lines skipped")
+    p.add_argument("--clusters", default=None, metavar="FILE",
+                   help="in --labels' place: the steps `discover` found (its --out), for this or another index; no checkpoint needed")
     p.add_argument("-k", type=int, default=1, help="labels kept per second, 1 to 32 (segments use the best one)")
     p.add_argument("--threshold", type=float, default=None,
                    help="a second whose best score is below this is background (default: none is)")
@@ -88,10 +87,33 @@ def _parser():
     p.add_argument("--map", default=None, metavar="OUT.csv",
                    help="with --align: write the time map of every hit, one row `query,vid,query_second,first,last` per aligned second "
                         "of the clip (query_second on the clip's own video timeline; first..last the seconds of vid that show it)")
+    p = sub.add_parser("discover", help="which steps recur in the corpus: cluster the index's seconds (no checkpoint, no vocabulary)")
+    _index_options(p)
+    _model_options(p, required=False)
+    p.add_argument("-k", type=int, required=True, help=f"clusters, 1 to {MAX_CLUSTERS}")
+    p.add_argument("--iters", type=int, default=10, help="centroid updates at most (default 10); stops early when no second moves")
+    p.add_argument("--seed", type=int, default=0, help="of the k seconds the centroids start from")
+    p.add_argument("--out", required=True, metavar="FILE", help="the clusters (.npz), what `annotate --clusters` takes")
+    p.add_argument("--exemplars", type=int, default=None, metavar="N", help="also print every cluster's N best seconds, 1 to 32")
+    p.add_argument("--labels", default=None, metavar="FILE",
+                   help="name every cluster by the nearest line of this vocabulary (needs --checkpoint and --vocab)")
+    p.add_argument("--segments", default=None, metavar="CSV", help="also write the clustered index's segments, as `annotate` does")
+    p.add_argument("--threshold", type=float, default=None, help="with --segments: a second scoring below this is background")
+    p.add_argument("--min-len", type=int, default=None, help="with --segments: drop segments shorter than this many seconds")
+    p.add_argument("--smooth", type=float, default=None, metavar="PENALTY",
+                   help="with --segments: decode every video's steps with this penalty per change (needs a finite --threshold)")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
     return ap
+
+
+def _model_options(p, required=True):
+    """--checkpoint --vocab [--dtype] [--model]: the aligner of `index`, `query`, `annotate --labels` and `discover --labels`"""
+    p.add_argument("--checkpoint", required=required, default=None)
+    p.add_argument("--vocab", required=required, default=None, help="s3d_dict.npy (the Word2Vec vocabulary)")
+    p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16")
+    p.add_argument("--model", choices=("init", "cotrain"), default="init")
 
 
 def _index_options(p):
@@ -143,11 +165,30 @@ def _check_query(ap, a):
 def _check_annotate(ap, a):
     smooth = a.smooth is not None
     _refuse(ap,
+            ((a.labels is None) == (a.clusters is None), "one of --labels and --clusters is required"),
+            (a.labels is not None and (a.checkpoint is None or a.vocab is None),
+             "the following arguments are required: --checkpoint, --vocab"),
             (not 1 <= a.k <= 32, "-k must lie in [1, 32]"),
             (a.per_second and (a.threshold is not None or a.min_len is not None), "--per-second does not go with --threshold / --min-len"),
             (a.threshold is not None and a.threshold != a.threshold, "--threshold must not be NaN"),
             (a.min_len is not None and a.min_len < 1, "--min-len must be >= 1"),
             (smooth and a.per_second, "--smooth does not go with --per-second"),
+            (smooth and not a.smooth >= 0, "--smooth must be >= 0"),
+            (smooth and (a.threshold is None or not np.isfinite(a.threshold)), "--smooth needs a finite --threshold"))
+
+
+def _check_discover(ap, a):
+    smooth = a.smooth is not None
+    _refuse(ap,
+            (not 1 <= a.k <= MAX_CLUSTERS, f"-k must lie in [1, {MAX_CLUSTERS}]"),
+            (a.iters < 1, "--iters must be >= 1"),
+            (a.exemplars is not None and not 1 <= a.exemplars <= 32, "--exemplars must lie in [1, 32]"),
+            (a.labels is not None and (a.checkpoint is None or a.vocab is None), "--labels needs --checkpoint and --vocab"),
+            (a.labels is None and (a.checkpoint is not None or a.vocab is not None), "--checkpoint / --vocab need --labels"),
+            (a.segments is None and any(x is not None for x in (a.threshold, a.min_len, a.smooth)),
+             "--threshold / --min-len / --smooth need --segments"),
+            (a.threshold is not None and a.threshold != a.threshold, "--threshold must not be NaN"),
+            (a.min_len is not None and a.min_len < 1, "--min-len must be >= 1"),
             (smooth and not a.smooth >= 0, "--smooth must be >= 0"),
             (smooth and (a.threshold is None or not np.isfinite(a.threshold)), "--smooth needs a finite --threshold"))
 
@@ -205,12 +246,17 @@ def _load_index(a):
     return VideoIndex.load(a.index)
 
 
-def _load_searcher(a):
-    """(the aligner, its sentence embedder, the index) of `query` and `annotate`, loaded in this order"""
+def _load_model(a):
+    """(the aligner, its sentence embedder) of --checkpoint --vocab"""
     vocab = np.load(a.vocab)
     model = build_aligner(a.checkpoint, vocab, a.model, a.dtype)
     from ..word2vec_model import Word2VecTokenizer
-    return model, make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab)), _load_index(a)
+    return model, make_embed_text(model, Word2VecTokenizer(max_words=32, vocab=vocab))
+
+
+def _load_searcher(a):
+    """(the aligner, its sentence embedder, the index) of `query` and `annotate`, loaded in this order"""
+    return (*_load_model(a), _load_index(a))
 
 
 def _run_merge(a):
@@ -256,9 +302,47 @@ def _run_similar(a):
     return 0
 
 
+def _write_segments(path, ann, a):
+    with open(path, "w", newline="") as f:
+        write_segments_csv(f, ann.segments(float("-inf") if a.threshold is None else a.threshold, a.min_len or 1, switch=a.smooth))
+
+
+def _run_discover(a):
+    idx = _load_index(a)
+    try:
+        found = discover_steps(idx, a.k, a.iters, a.seed)
+    except ValueError as e:
+        print(f"discover: {e}", file=sys.stderr)
+        return 2
+    found.save(a.out)
+    names = found.name(idx, *_load_model(a), _read_vids(a.labels)) if a.labels else None
+    best = found.exemplars(idx, a.exemplars) if a.exemplars else None
+    for c in range(len(found)):                        # cluster, seconds, cohesion[, name, its score][, vid:second:score ...]
+        row = [str(c), str(int(found.sizes[c])), f"{found.cohesion[c]:.6f}"]
+        if names is not None:
+            row += [names[c][0], f"{names[c][1]:.6f}"]
+        if best is not None:
+            row += [f"{vid}:{sec}:{score:.6f}" for vid, sec, score in best[c]]
+        print("\t".join(row))
+    if a.segments is not None:
+        k = 1 if a.smooth is None else min(5, len(found))                      # a decode chooses among a second's k best steps
+        _write_segments(a.segments, found.annotation(idx, k, None if names is None else [n for n, _ in names]), a)
+    print(f"{a.out}: {len(found)} steps over {len(idx)} seconds of {len(idx.vids)} videos, {len(found.moved)} passes, "
+          f"{int((found.sizes == 0).sum())} empty", file=sys.stderr)
+    return 0
+
+
 def _run_annotate(a):
-    model, embed, idx = _load_searcher(a)
-    ann = annotate(idx, model, embed, _read_vids(a.labels), a.k)
+    if a.clusters is not None:
+        idx = _load_index(a)
+        found = StepClusters.load(a.clusters, idx.device)
+        if a.k > len(found):
+            print(f"annotate: -k {a.k} exceeds the {len(found)} steps of {a.clusters}", file=sys.stderr)
+            return 2
+        ann = found.annotation(idx, a.k)
+    else:
+        model, embed, idx = _load_searcher(a)
+        ann = annotate(idx, model, embed, _read_vids(a.labels), a.k)
     with open(a.out, "w", newline="") as f:
         if a.per_second:
             write_per_second_csv(f, ann)
@@ -292,8 +376,9 @@ def _run_query(a):
     return 0
 
 
-_CHECKS = dict(index=_check_index, query=_check_query, annotate=_check_annotate, similar=_check_similar, merge=lambda ap, a: None)
-_RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, merge=_run_merge)
+_CHECKS = dict(index=_check_index, query=_check_query, annotate=_check_annotate, similar=_check_similar, discover=_check_discover,
+               merge=lambda ap, a: None)
+_RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, discover=_run_discover, merge=_run_merge)
 
 
 def main(argv=None):

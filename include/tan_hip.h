@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -811,6 +811,43 @@ int tan_quantize_rows_e4m3(const void* x, int dtype, long n_rows, int C, void* c
 int tan_rank_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Q, long N, int C,
                        const int* pair, int k, int splits, int* higher, int* ties, float* top_score, int* top_row, void* ws,
                        void* stream);
+/* ---- the coarse image: 272 bytes per second of video in MXFP4, the block-scaled 4-bit format gfx950 multiplies natively
+ * (v_mfma_scale_f32_32x32x64_f8f6f4) -- what `search(..., coarse=)` sweeps on the card before the exact sweep rescores its candidates ----
+ * Row format.  A row of 512 elements is 16 blocks of 32 consecutive elements.  codes: uint8 [n_rows, 256], two e2m1 codes per byte;
+ * scales: uint8 [n_rows, 16], one e8m0 byte per block; both contiguous.
+ *   Block scale.  With amax = max|x| over the block and amax = m * 2^e, m in [0.5, 1) (frexp):
+ *       s = e - 3 if m <= 0.75, else s = e - 2;  s is clamped to [-127, 127];  the byte is s + 127;  amax == 0: the byte is 127.
+ *     Hence amax * 2^-s lies in (3, 6] (6 is e2m1's largest value): a block never saturates, as an e4m3 row never does.  The NaN
+ *     byte 255 is never written.
+ *   Code.  code = RNE_e2m1(x * 2^-s): the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6 are the codes 0 .. 7 in bits 0 to 2; round to
+ *     nearest, ties to the even code: 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4.  Bit 3 is the sign
+ *     bit of x, whatever the magnitude rounds to: a negative element that rounds to zero, and -0.0 itself, have the code 8 (the
+ *     instruction reads it as zero).
+ *   Nibble order.  Element 2 j of a row is the LOW nibble (bits 0 to 3) of byte j, element 2 j + 1 the high one: the order in
+ *     which the scaled MFMA consumes a 4-bit operand, so the 16 bytes of a block go into a lane's operand registers unpermuted
+ *     (pinned with exact data by tests/test_coarse_gpu.py).
+ *   Inputs are finite; x * 2^-s is exact apart from f32 underflow, which rounds to the code 0 either way.
+ * tan_quantize_rows_mxfp4: x [n_rows, C] (TAN_F32 or TAN_BF16, 16-byte aligned), C == 512, 1 <= n_rows < 2^31 -> codes (4-byte
+ *   aligned) and scales.  One wave per row, a block is four lanes, no atomics: run-to-run identical.
+ * tan_rank_topk_mxfp4: the k best rows per query of such an image.  The QUERY keeps the e4m3 row format above (Tq [Q, 512] codes,
+ *   16-byte aligned, q_scale [Q]); codes [N, 256] and scales [N, 16] are 16-byte aligned.
+ *       score_c(q, n) = (sum over blocks b of 2^s[n][b] * sum over i in b of qcode[q][i] * vcode[n][i]) * q_scale[q]
+ *   accumulated in f32 by v_mfma_scale_f32_32x32x64_f8f6f4 in ascending K order (the image is the fp4 operand with its block scales
+ *   in the instruction's scale operand, the query the fp8 operand with scale 2^0), then ONE f32 multiply by q_scale[q].
+ *   top_score / top_row [Q, k] <- per query the k best (score_c, row) by descending score, equal scores by ascending row.
+ *   Cutoff.  below_score / below_row [Q] (f32 / int32), both NULL or both given: a row is admitted only when it comes STRICTLY AFTER
+ *     (below_score[q], below_row[q]) in that order -- score_c < below_score[q], or equal and row > below_row[q].  A cutoff row of -1
+ *     admits every row at an equal score, 0x7fffffff none.  So a list continues: two calls with k = 16, the second cut off below
+ *     the first's last entry, give exactly the one call with k = 32.  With fewer than k admitted rows the tail holds empty slots
+ *     (-inf, row 0x7fffffff), which tan_topk_fold sorts last.
+ *   1 <= k <= 32, k <= N; splits, determinism (bit-identical for every `splits`) and sizes as tan_rank_topk.
+ *   ws: tan_rank_topk_mxfp4_ws_bytes(Q, N, k) bytes of scratch, 16-byte aligned (-1 for invalid sizes).
+ *   NULL pointers, another width, bad sizes or alignment: TAN_ERR_BAD_ARG, nothing launched.                                       */
+int tan_quantize_rows_mxfp4(const void* x, int dtype, long n_rows, int C, void* codes, void* scales, void* stream);
+long tan_rank_topk_mxfp4_ws_bytes(long Q, long N, int k);
+int tan_rank_topk_mxfp4(const void* Tq, const float* q_scale, const void* codes, const void* scales, long Q, long N, int C, int k,
+                        int splits, const float* below_score, const int* below_row, float* top_score, int* top_row, void* ws,
+                        void* stream);
 /* ---- moment search: the k best DISTINCT videos per query, each with its best second and the extent of the moment around it ----
  * tan_rank_topk_video: tan_rank_topk's sweep (Tq [Q, C], Vn [N, C], C == 512, `dtype` TAN_F32 or TAN_BF16, 16-byte aligned) over
  * an index whose rows are grouped into videos: v_off [n_videos + 1] int32 on the device, v_off[0] == 0, v_off[n_videos] == N,

@@ -41,17 +41,12 @@
 
 #include "tan_mma.h"
 #include "tan_sort.h"
+#include "tan_topk.h"
 
 namespace tal {
 namespace {
 
 constexpr int RC = 512;                     // feature width (the model's)
-constexpr int BQ = 128;                     // queries per block: 4 waves x 32
-constexpr int BN = 64;                      // index rows per tile
-constexpr int CAP = 64;                     // candidate slots per query
-constexpr int KMAX = 32;
-constexpr int MAX_SPLITS = 256;
-constexpr int SENT_ROW = 0x7fffffff;
 constexpr int FILT_HEAD = 4;                // int32 words before a filter image's tile list (include/tan_hip.h)
 
 template <typename T> struct RCfg;
@@ -483,26 +478,6 @@ __global__ void __launch_bounds__(256) rank_kernel(const T* __restrict__ Tq, con
             }
         }
     }
-}
-
-// launch 3: one wave per query; lanes 0..31 carry the best so far, lanes 32..63 take the next split's list
-__global__ void __launch_bounds__(256) rank_merge_kernel(const float* __restrict__ part_s, const int* __restrict__ part_n, long Q, int k,
-                                                         int splits, float* __restrict__ top_s, int* __restrict__ top_n) {
-    const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (q >= Q) return;
-    float s = -INFINITY;
-    int n = SENT_ROW;
-    for (int sp = 0; sp < splits; ++sp) {
-        if (lane >= 32) {
-            const bool real = lane - 32 < k;
-            const long o = ((long)sp * Q + q) * k + (lane - 32);
-            s = real ? part_s[o] : -INFINITY;
-            n = real ? part_n[o] : SENT_ROW;
-        }
-        sort64(s, n, lane);
-    }
-    if (lane < k) { top_s[q * k + lane] = s; top_n[q * k + lane] = n; }
 }
 
 // tan_rank_topk_video's merge: the same fold, each step by distinct64 -- a video that straddles splits is in several lists and keeps
@@ -1212,18 +1187,6 @@ __global__ void __launch_bounds__(256) quantize_rows_kernel(const T* __restrict_
     if (lane == 0) scale[g] = __uint_as_float((unsigned)(s + 127) << 23);
 }
 
-inline long n_index_tiles(long N) { return (N + BN - 1) / BN; }
-
-// how many splits a sweep launches (`splits` = 0: chosen from Q and N) and the index tiles each one takes
-inline int n_splits(long Q, long N, int splits, long* tiles_per_split) {
-    const long n_tiles = n_index_tiles(N), q_tiles = (Q + BQ - 1) / BQ;
-    long want = splits > 0 ? splits : (512 + q_tiles - 1) / q_tiles;
-    want = want < 1 ? 1 : (want > MAX_SPLITS ? MAX_SPLITS : want);
-    want = want > n_tiles ? n_tiles : want;
-    *tiles_per_split = (n_tiles + want - 1) / want;
-    return (int)((n_tiles + *tiles_per_split - 1) / *tiles_per_split);
-}
-
 // a sweep's scratch: VIDEO: tvid [tiles rounded up to 2] int2, otherwise dscore [Q rounded up to 4] f32; then the splits' lists
 // (score, row[, video]), 4 bytes per entry each
 inline long sweep_ws_head(bool video, long Q, long N) { return video ? (n_index_tiles(N) + 1) / 2 * 2 * 8 : (Q + 3) / 4 * 4 * 4; }
@@ -1678,8 +1641,6 @@ inline bool rows_ok(int fmt, const void* Tq, const float* q_scale, const void* V
 template <typename F> int by_format(int fmt, F launch) {
     return fmt == TAN_BF16 ? launch(Rows<bf16_t>()) : fmt == TAN_F32 ? launch(Rows<float>()) : launch(Rows<e4m3_t>());
 }
-
-inline long max_splits(long N) { return n_index_tiles(N) < MAX_SPLITS ? n_index_tiles(N) : MAX_SPLITS; }
 
 }  // namespace
 

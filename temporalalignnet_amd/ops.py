@@ -434,6 +434,45 @@ def rank_topk_e4m3(tq, q_scale, vn, v_scale, pair=None, k=0, *, splits=0, check_
     return _rank_topk("rank_topk_e4m3", tq, q_scale, vn, v_scale, pair, k, splits, check_pair, out, ws)
 
 
+def quantize_rows_mxfp4(x, codes=None, scales=None):
+    """x [n, 512] (f32 / bf16, contiguous) -> (codes uint8 [n, 256]: two e2m1 codes per byte, scales uint8 [n, 16]: one e8m0 byte per
+    block of 32 elements), the coarse row format of include/tan_hip.h (tan_quantize_rows_mxfp4).  codes / scales: caller-owned
+    outputs instead of fresh ones."""
+    assert x.dim() == 2 and x.is_contiguous()
+    n, dev = x.shape[0], x.device
+    codes = torch.empty(n, x.shape[1] // 2, dtype=torch.uint8, device=dev) if codes is None else codes
+    scales = torch.empty(n, x.shape[1] // 32, dtype=torch.uint8, device=dev) if scales is None else scales
+    assert codes.dtype == torch.uint8 and codes.shape == (n, x.shape[1] // 2) and codes.is_contiguous()
+    assert scales.dtype == torch.uint8 and scales.shape == (n, x.shape[1] // 32) and scales.is_contiguous()
+    _lib.check(_lib.lib().tan_quantize_rows_mxfp4(_ptr(x), _dt(x), n, x.shape[1], _ptr(codes), _ptr(scales), _stream()),
+               "tan_quantize_rows_mxfp4")
+    return codes, scales
+
+
+def rank_topk_mxfp4(tq, q_scale, codes, scales, k, *, splits=0, below=None, out=None, ws=None):
+    """The k best rows per query of a coarse image (tan_rank_topk_mxfp4): tq [Q, 512] uint8 e4m3 codes with q_scale [Q] f32, as
+    `quantize_rows_e4m3` makes them; codes [N, 256] / scales [N, 16] uint8, as `quantize_rows_mxfp4` makes them.  Returns
+    (top_score [Q, k] f32, top_row [Q, k] int32) by descending coarse score, equal scores by ascending row.
+    below = (score [Q] f32, row [Q] int32): only rows strictly after that entry in this order are admitted (row -1: every row at an
+    equal score, 0x7fffffff: none); with fewer than k of them the tail holds empty slots (-inf, 0x7fffffff).
+    out / ws: caller-owned outputs (the same pair) and scratch (uint8, >= tan_rank_topk_mxfp4_ws_bytes) instead of fresh ones."""
+    assert tq.dim() == 2 and tq.dtype == torch.uint8 and tq.is_contiguous()
+    Q, N, dev = tq.shape[0], codes.shape[0], tq.device
+    assert q_scale.dtype == torch.float32 and q_scale.shape == (Q,) and q_scale.is_contiguous()
+    assert codes.dtype == torch.uint8 and codes.shape == (N, tq.shape[1] // 2) and codes.is_contiguous()
+    assert scales.dtype == torch.uint8 and scales.shape == (N, tq.shape[1] // 32) and scales.is_contiguous()
+    b_score, b_row = (None, None) if below is None else below
+    if below is not None:
+        assert b_score.dtype == torch.float32 and b_row.dtype == torch.int32 and b_score.shape == b_row.shape == (Q,)
+        assert b_score.is_contiguous() and b_row.is_contiguous()
+    top_s, top_r = _lists(Q, k, dev) if out is None else out
+    ws = _scratch(ws, _lib.lib().tan_rank_topk_mxfp4_ws_bytes(Q, N, k), dev)
+    _lib.check(_lib.lib().tan_rank_topk_mxfp4(_ptr(tq), _f32(q_scale), _ptr(codes), _ptr(scales), Q, N, tq.shape[1], k, splits,
+                                              _f32(b_score), _ptr(b_row), _f32(top_s), _ptr(top_r), _ptr(ws), _stream()),
+               "tan_rank_topk_mxfp4")
+    return top_s, top_r
+
+
 def _video_args(what, tq, vn, v_off, q_scale, v_scale):
     assert v_off.dtype == torch.int32 and v_off.dim() == 1 and v_off.numel() >= 2 and v_off.is_contiguous()
     return _rows_args(what, tq, vn, q_scale, v_scale)

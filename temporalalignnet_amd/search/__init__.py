@@ -16,6 +16,8 @@ seconds into the steps that recur in it, and its `StepClusters` serve as the voc
     python -m temporalalignnet_amd.search query ... --index I0.npz --shard I1.npz --shard I2.npz [--host-resident] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --only VID --only-file vids.txt --exclude VID --within VID:30-90 "crack two eggs" ...
     python -m temporalalignnet_amd.search merge --out I.npz I0.npz I1.npz ...
+    python -m temporalalignnet_amd.search coarse --index I.npz [--shard I1.npz ...] [--host-resident] --out I.c4.npz
+    python -m temporalalignnet_amd.search query ... --index I.npz [--shard ...] [--host-resident] --coarse I.c4.npz [--pool 64] "crack two eggs" ...
     python -m temporalalignnet_amd.search annotate --checkpoint C --vocab s3d_dict.npy --index I.npz --labels steps.txt [-k K]
         [--threshold X] [--min-len M] [--smooth PENALTY] [--per-second] --out segments.csv
     python -m temporalalignnet_amd.search similar --index I.npz [--shard I1.npz ...] [--host-resident] --clip VID:10-29 [-k K] [--keep-source]
@@ -27,6 +29,7 @@ seconds into the steps that recur in it, and its `StepClusters` serve as the voc
 """
 from .annotation import Annotation, annotate, label_lists, write_per_second_csv, write_segments_csv  # noqa: F401
 from .cli import main, parse_args, parse_within, restrict_from_args                                 # noqa: F401
+from .coarse import CoarseImage                                                                     # noqa: F401
 from .cluster import MAX_CLUSTERS, StepClusters, centroid_image, discover_steps                      # noqa: F401
 from .index import E4M3, RowFilter, ShardedIndex, VideoIndex, _index_chunks, build_index, plan_index_windows, restrict_spans  # noqa: F401
 from .text import (RERANK_TEXT_SLOTS, TEMPERATURE, Moment, Reranked, SequenceHit, _rerank_table,    # noqa: F401

@@ -10,6 +10,7 @@ from . import __doc__ as _PACKAGE_DOC                # its first paragraph is th
 from ..infer_align import build_aligner, make_embed_text, read_corpus
 from .annotation import annotate, write_per_second_csv, write_segments_csv
 from .cluster import MAX_CLUSTERS, StepClusters, discover_steps
+from .coarse import CoarseImage
 from .index import E4M3, ShardedIndex, VideoIndex, build_index
 from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
 from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, search_clips, search_copies
@@ -60,7 +61,11 @@ def _parser():
     p.add_argument("--rerank", action="store_true",
                    help="two stages: the --pool best distinct videos of the dual sweep rescored by the joint encoder, the k best as "
                         "`sentence vid second score confidence alignability dual_second dual_score` (needs index --keep-stem)")
-    p.add_argument("--pool", type=int, default=None, help="with --rerank: candidates per sentence, 1 to 32 (default 32)")
+    p.add_argument("--pool", type=int, default=None,
+                   help="with --rerank: candidates per sentence, 1 to 32 (default 32); with --coarse: any number >= 1 (default 64)")
+    p.add_argument("--coarse", default=None, metavar="FILE",
+                   help="the index's coarse image (what `coarse` writes): it proposes --pool candidates per sentence on the card and "
+                        "only their full rows are scored exactly -- for a --host-resident index no shard crosses the host link")
     p.add_argument("--only", action="append", default=None, metavar="VID", help="search only this video (repeatable)")
     p.add_argument("--only-file", default=None, metavar="PATH", help="search only the videos listed here, one vid per line")
     p.add_argument("--exclude", action="append", default=None, metavar="VID", help="leave this video out (repeatable)")
@@ -102,6 +107,9 @@ def _parser():
     p.add_argument("--min-len", type=int, default=None, help="with --segments: drop segments shorter than this many seconds")
     p.add_argument("--smooth", type=float, default=None, metavar="PENALTY",
                    help="with --segments: decode every video's steps with this penalty per change (needs a finite --threshold)")
+    p = sub.add_parser("coarse", help="the MXFP4 image of an index, 272 bytes per second: what `query --coarse` takes (no checkpoint)")
+    _index_options(p)
+    p.add_argument("--out", required=True, metavar="FILE", help="the image (.npz)")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
@@ -150,8 +158,11 @@ def _check_query(ap, a):
             (a.sequence and len(a.sentences) > 32, "--sequence takes at most 32 sentences"),
             (a.rerank and (a.sequence or a.moments), "--rerank does not go with --sequence / --moments"),
             (a.rerank and (a.shard or a.host_resident), "--rerank does not go with --shard / --host-resident; merge the index files"),
-            (a.pool is not None and not a.rerank, "--pool needs --rerank"),
-            (a.pool is not None and not 1 <= a.pool <= 32, "--pool must lie in [1, 32]"),
+            (a.pool is not None and not a.rerank and a.coarse is None, "--pool needs --rerank or --coarse"),
+            (a.pool is not None and a.rerank and not 1 <= a.pool <= 32, "--pool must lie in [1, 32]"),
+            (a.pool is not None and a.pool < 1, "--pool must be at least 1"),
+            (a.coarse is not None and (a.sequence or a.moments or a.rerank), "--coarse does not go with --sequence / --moments / --rerank"),
+            (a.coarse is not None and filtered, "--coarse does not go with --only / --exclude / --within"),
             (a.width is not None and not a.moments, "--width needs --moments"),
             (a.width is not None and not a.width >= 0, "--width must be >= 0"),
             (filtered and a.sequence, "--only / --exclude / --within do not go with --sequence"),
@@ -266,6 +277,14 @@ def _run_merge(a):
     return 0
 
 
+def _run_coarse(a):
+    idx = _load_index(a)
+    image = CoarseImage.build(idx)
+    image.save(a.out)
+    print(f"{a.out}: {len(idx)} seconds in {len(image.parts)} shards, {image.nbytes()} bytes", file=sys.stderr)
+    return 0
+
+
 def _run_index(a):
     model = build_aligner(a.checkpoint, np.load(a.vocab), a.model, a.dtype)
     corpus = read_corpus(a.feature_dir, a.asr_json, a.vlen_csv, a.worker_id, a.num_workers)
@@ -370,15 +389,24 @@ def _run_query(a):
             for m in hits:
                 print(f"{sentence}\t{m.vid}\t{m.start}\t{m.end}\t{m.second}\t{m.score:.6f}")
     else:
-        for sentence, hits in zip(a.sentences, search(idx, model, embed, a.sentences, a.k, restrict=only)):
+        image = None if a.coarse is None else CoarseImage.load(a.coarse, idx.device)
+        if image is not None:
+            try:
+                image.check(idx)
+            except ValueError as e:                    # an image of another index
+                print(f"query: {e}", file=sys.stderr)
+                return 2
+        found = search(idx, model, embed, a.sentences, a.k, restrict=only, coarse=image, pool=64 if a.pool is None else a.pool)
+        for sentence, hits in zip(a.sentences, found):
             for vid, sec, score in hits:
                 print(f"{sentence}\t{vid}\t{sec}\t{score:.6f}")
     return 0
 
 
 _CHECKS = dict(index=_check_index, query=_check_query, annotate=_check_annotate, similar=_check_similar, discover=_check_discover,
-               merge=lambda ap, a: None)
-_RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, discover=_run_discover, merge=_run_merge)
+               merge=lambda ap, a: None, coarse=lambda ap, a: None)
+_RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, discover=_run_discover, merge=_run_merge,
+             coarse=_run_coarse)
 
 
 def main(argv=None):

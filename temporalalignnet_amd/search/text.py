@@ -23,6 +23,7 @@ import torch
 
 from .. import ops
 from ..infer_align import JOINT_MAX_LEN, _aligner
+from . import coarse as c2f
 from .index import ShardedIndex, _locate, _locate_videos, _on_device
 
 TEMPERATURE = 0.07
@@ -49,7 +50,11 @@ def _top_k(what, k, n, name="k"):
 
 def unit_rows(index, t):
     """f32 rows t [n, 512] (contiguous, on the index's device) as a sweep's query: unit rows in the index's row format (`query_features`)"""
-    t = ops.l2norm_fwd(t, torch.empty_like(t), None, t.shape[0], 512)
+    return _row_format(index, ops.l2norm_fwd(t, torch.empty_like(t), None, t.shape[0], 512))
+
+
+def _row_format(index, t):
+    """f32 unit rows t in the index's row format: the second half of `unit_rows`"""
     if index.e4m3:
         return ops.quantize_rows_e4m3(t)
     return t if index.row_dtype == torch.float32 else ops.cast(t, torch.empty(t.shape, dtype=index.row_dtype, device=index.device))
@@ -144,24 +149,41 @@ def read_back(tensors):
 @torch.no_grad()
 def query_features(index, model, embed_text, queries, text_batch=1024):
     """Unit text features [Q, 512] in the index's dtype; for an e4m3 index (codes uint8 [Q, 512], scale f32 [Q])."""
+    return unit_rows(index, _text_features(index, model, embed_text, queries, text_batch))
+
+
+def _text_features(index, model, embed_text, queries, text_batch=1024):
+    """The sentences' text features, f32 [Q, 512] on the index's device, not yet normalised"""
     net = _aligner(model)
     dev = index.device
-    t = torch.cat([net.get_textual_feature(embed_text(list(queries[a:a + text_batch])).to(dev)).float().reshape(-1, 512)
-                   for a in range(0, len(queries), text_batch)], 0).contiguous()
-    return unit_rows(index, t)
+    return torch.cat([net.get_textual_feature(embed_text(list(queries[a:a + text_batch])).to(dev)).float().reshape(-1, 512)
+                      for a in range(0, len(queries), text_batch)], 0).contiguous()
 
 
 @torch.no_grad()
-def search(index, model, embed_text, queries, k=10, splits=0, restrict=None):
+def search(index, model, embed_text, queries, k=10, splits=0, restrict=None, coarse=None, pool=64):
     """Per query the k best seconds of the corpus: [[(vid, second, score)] * k] * len(queries), by descending score (equal scores
     by index row).  score = <index row, unit text feature>: the stitched dual cosine; / 0.07 gives the evaluation's logit.
     `index`: a `VideoIndex`, or a `ShardedIndex` -- then exactly what `VideoIndex.concat` of its shards gives (as for
     `search_moments` and `search_sequences`): one sweep and one `tan_topk_fold` per shard.  One read-back at the end for either.
     restrict: a `RowFilter` of this index (`index.restrict(...)`): only its rows are swept (`tan_rank_topk_filtered`) and returned,
-    with the scores and the order the unrestricted call gives them; k is clamped to the admitted rows."""
+    with the scores and the order the unrestricted call gives them; k is clamped to the admitted rows.
+    coarse: a `CoarseImage` of this index (search/coarse.py): its MXFP4 rows are swept on the device for `pool` candidates per query,
+    and only the candidates' full rows -- gathered, for a host-resident index over the host link, instead of every shard -- meet
+    the exact sweep.  Every returned entry has the score and the relative order this call gives it without `coarse=`, and the
+    results are equal whenever that call's k best lie among the candidates; k is clamped to the distinct candidates.  Not with
+    `restrict`."""
     queries = list(queries)
     if not queries:
         return []
+    if coarse is not None:
+        if restrict is not None:
+            raise ValueError("search: coarse= does not go with restrict=")
+        coarse.check(index)
+        k = _top_k("search", k, len(index))
+        unit = _text_features(index, model, embed_text, queries)
+        unit = ops.l2norm_fwd(unit, torch.empty_like(unit), None, unit.shape[0], 512)
+        return c2f.locate(index, *c2f.search_coarse(index, coarse, unit, _row_format(index, unit), k, pool, splits))
     if restrict is not None:
         restrict.check(index)
     k = _top_k("search", k, len(index) if restrict is None else restrict.n_rows)

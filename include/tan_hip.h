@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -966,6 +966,42 @@ int tan_clip_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, in
 int tan_clip_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
                        const int* c_off, long n_clip, const int* v_off, long n_videos, int k, int splits, float* top_score,
                        int* top_row, int* top_video, void* ws, void* stream);
+/* ---- cover search: the k videos that share the most seconds with a set of query rows, in any order and at any pace ----
+ * A SET is 1 to 4096 (tan_cover_max_rows()) consecutive rows of Tq [Qt, C]: q_off [n_set + 1] int32 on the device, q_off[0] == 0,
+ * q_off[n_set] == Qt, strictly increasing, every difference in [1, 4096].  A VIDEO v is the index rows [v_off[v], v_off[v + 1]) -- the
+ * v_off contract of tan_rank_topk_video.  For set p with rows q_0 .. q_{m-1} and video v with V rows, let
+ * x_i[t] = score(q_i, v_off[v] + t), the row sweep's score with the bits tan_sequence_scores returns (e4m3:
+ * (acc * v_scale[n]) * q_scale[q]).  Inputs are finite.  The measure is the Chamfer similarity of the two sets of rows:
+ *     a_i  = max_t x_i[t]          b_t = max_i x_i[t]                       (exact)
+ *     fix(x) = __float2ll_rn(x * 2^30)                                      (tan_cluster_accumulate's image; the multiply is exact)
+ *     F = sum_i fix(a_i)           B = sum_t fix(b_t)                       (64-bit integers: order-free)
+ *     fwd(p, v) = ((float) F * 2^-30f) / (float) m                          (int64 -> f32 round to nearest even, exact scaling, ONE f32 division)
+ *     bwd(p, v) = ((float) B * 2^-30f) / (float) V
+ *     score = fwd                    rank == TAN_COVER_QUERY  ("how much of my video is in v")
+ *           = bwd                    rank == TAN_COVER_VIDEO  ("how much of v is in my video")
+ *           = (fwd + bwd) * 0.5f     rank == TAN_COVER_BOTH   (one f32 add, one exact multiply)
+ * |x| <= 2 and m, V < 2^31, so no sum overflows.  Given the bits of x, nothing depends on tiling, slabs, launch shape or shards.
+ * tan_cover_topk (Tq, Vn, dtype, C == 512, alignment as tan_rank_topk):
+ *   fwd / bwd [n_set, n_videos] f32, caller-owned, always fully written: the all-pairs result and the only storage that grows with
+ *     n_set * n_videos.  Nothing of size Qt x N, n_set x N or Qt x n_videos is stored; no scratch, no atomics in global memory,
+ *     run-to-run identical bits.
+ *   top_score (f32) / top_row / top_video (int32) [n_set, k], 1 <= k <= min(32, n_videos): per set the k videos by descending score,
+ *     equal scores by ascending top_row = v_off[v] -- the sweeps' order, so tan_topk_fold folds the lists as they are.
+ * 1 <= n_set <= 65535, Qt in [n_set, 4096 n_set], 1 <= N < 2^31, n_videos in [1, N].  Another width, k outside [1, min(32, n_videos)],
+ * an unknown dtype or rank, a NULL pointer, misalignment, sizes outside these ranges: TAN_ERR_BAD_ARG, nothing launched.
+ * A q_off or v_off that breaks its contract is the CALLER's error: every lookup is clamped (a set of more than 4096 rows is cut to
+ * 4096; an empty video gets fwd = bwd = 0), nothing is read or written out of bounds, and the results are unspecified.  The Python
+ * wrapper checks on request.  tan_cover_topk_e4m3 takes the codes and scales of tan_rank_topk_e4m3.                              */
+#define TAN_COVER_QUERY 0
+#define TAN_COVER_VIDEO 1
+#define TAN_COVER_BOTH 2
+int tan_cover_max_rows(void);                      /* 4096 */
+int tan_cover_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* q_off, long n_set, const int* v_off,
+                   long n_videos, int rank, int k, float* fwd, float* bwd, float* top_score, int* top_row, int* top_video,
+                   void* stream);
+int tan_cover_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                        const int* q_off, long n_set, const int* v_off, long n_videos, int rank, int k, float* fwd, float* bwd,
+                        float* top_score, int* top_row, int* top_video, void* stream);
 /* Clip pooling of test_retrieval_yc2 (:197-214).  stage: one stage of the video stack's output, window w's frame f at
  * stage + w * win_stride + f * 512 elements of `dtype` (win_stride >= T * 512, a multiple of 8); table [W, 3] int32 = (clip,
  * first_frame, n_frames) per window.  normalize != 0: every selected frame is L2-normalised (sim = 'cos').  sum [n_clips, 512] /

@@ -34,6 +34,9 @@
 // tan_label_topk / _e4m3 answer the transposed question, the k best LABELS of every index row: label_kernel is the sweep with the
 // roles swapped (a tile of index rows resident, the label matrix streamed; tile_scores, the candidate buffers and sort64 carry over),
 // one workgroup per 128 rows, no splits, no scratch, no merge.  tan_label_runs compacts the rows' best labels into label segments.
+// tan_cover_topk / _e4m3 rank videos by the seconds they share with a SET of up to 4096 query rows in any order: cover_kernel is
+// label_kernel's organisation per (video, set) with the score tile reduced along both axes (every row's best second, every second's
+// best row; 64-bit fixed-point sums), and cover_select_kernel folds a set's scores into its k best videos.
 //
 // tan_segment_pool_* and tan_window_feat_* follow tan_stitch.hip's ownership rule: an accumulator row is owned by the first window
 // of the launch that touches it, and its owner adds every such window in window order -- no atomics, run-to-run identical bits.
@@ -1481,6 +1484,265 @@ int label_launch(const void* Tl, const void* Vn, long L, long N, int k, float* t
     return 0;
 }
 
+// ---- cover search: videos ranked by the seconds they share with a SET of query rows, in any order (include/tan_hip.h) ----
+// label_kernel's organisation with both reductions of the Chamfer similarity fused into the sweep: grid (video, set).  The workgroup
+// walks its video in slabs of BQ = 128 rows -- a wave keeps 32 of them in registers as the B fragments; the tail columns of the last
+// slab repeat the video's last row -- and the set's rows stream through LDS in 64-row tiles by tile_scores (rows past the set's end
+// load as zero).  A lane's 32 accumulators of a tile belong to ONE video row, so
+//   b_t  is a running max in registers over the tile rows that are the set's (a zero-filled tail row is not: 0 beats an all-negative
+//        column), finished by one lane ^ 32 exchange per slab; the columns that are the video's go through fix() into a per-lane
+//        64-bit sum (a repeated tail column does not), reduced once at the end;
+//   a_i  needs, for each of the tile's 64 rows, the max over the wave's 32 columns (a repeated column changes no max): four DPP
+//        steps inside a row of 16 lanes and one ds_swizzle across, per accumulator, on order-preserving integer keys (exact, like
+//        the float maximum, and one instruction a step); the lane whose column equals the accumulator's
+//        index keeps the result, and the wave writes its 64 maxima to its row of the [4][64] staging block.  After the NEXT tile's
+//        first barrier (tile_scores' callback) thread r < 64 folds the four waves' values of row r into rowmax[m] -- the same thread
+//        for a given row every time, so the fold needs no atomics -- and the stage is free again before any wave passes that tile's
+//        second barrier, behind which the next stage writes lie (every format has at least two K chunks).
+// rowmax starts at -inf; a tail row of the set's last tile is never folded.  After the last slab one pass sums fix(rowmax[i]); F and
+// B are integer sums, so nothing depends on their order, and fwd / bwd leave by two plain stores.  e4m3: label_kernel's scale order
+// (tile scale 1, the video row's scale as the column's, the set row's scale after the MFMA loop, two buffers by tile parity).
+constexpr int COVER_MAX = 4096;
+template <typename T> constexpr int cover_lds() {
+    return (tile_bytes<T>() + 15) / 16 * 16 + COVER_MAX * 4 + 4 * BN * 4 + 8 * 8 + (sizeof(T) == 1 ? 2 * BN * 4 : 0);
+}
+
+// A float as an int32 whose SIGNED order is the float's (finite values and infinities; -0 sorts just below +0, and fix() sends both
+// to 0), and back: the map is its own inverse.  The cross-lane maximum runs on these keys: v_max_i32 takes the DPP operand directly,
+// where a float maximum of a lane-crossed value first pays a canonicalising v_max_f32.
+__device__ __forceinline__ int order_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+
+template <int CTRL> __device__ __forceinline__ int dpp_max(int x) {
+    const int y = __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true);
+    return x > y ? x : y;
+}
+
+// the maximum over the 32 lanes of the caller's half-wave, in every lane of it.  All 64 lanes must be active.
+__device__ __forceinline__ int half_wave_max(int x) {
+    x = dpp_max<0xB1>(x);                                          // quad_perm [1, 0, 3, 2]: lane ^ 1
+    x = dpp_max<0x4E>(x);                                          // quad_perm [2, 3, 0, 1]: lane ^ 2
+    x = dpp_max<0x141>(x);                                         // row_half_mirror: the other quad of the 8
+    x = dpp_max<0x140>(x);                                         // row_mirror: the other 8 of the 16
+    const int y = __builtin_amdgcn_ds_swizzle(x, 0x401F);          // bit mode, xor 16: the other row of the half-wave
+    return x > y ? x : y;
+}
+
+__device__ __forceinline__ long long wave_sum_ll(long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// tan_cluster_accumulate's image of a value: the multiply by 2^30 is exact
+__device__ __forceinline__ long long cover_fix(float x) { return __float2ll_rn(x * 0x1p30f); }
+
+template <typename T>
+__global__ void __launch_bounds__(256) cover_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Qt, long N,
+                                                    const int* __restrict__ q_off, int n_set, const int* __restrict__ v_off,
+                                                    int n_videos, const float* __restrict__ q_scale,
+                                                    const float* __restrict__ v_scale, float* __restrict__ fwd,
+                                                    float* __restrict__ bwd) {
+#pragma clang fp contract(off)
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int LD = RCfg<T>::LD, KS = M::KS, NCH = RC / RCfg<T>::KC, NFR = RC / KS;
+    constexpr int TS = BN * LD;
+    constexpr long ROWB = (long)RC * sizeof(T);
+    constexpr bool F8 = sizeof(T) == 1;
+    static_assert(NCH >= 2, "the stage is freed between a tile's first and second barrier");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* tile = reinterpret_cast<T*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + 2 * TS * sizeof(T));   // F8: tile_scores' tile scales, all 1 here
+    float* rowmax = reinterpret_cast<float*>(smem + (tile_bytes<T>() + 15) / 16 * 16);
+    float* stage = rowmax + COVER_MAX;                                // [4 waves][64 tile rows]
+    long long* red = reinterpret_cast<long long*>(stage + 4 * BN);   // F of the four waves, then B
+    float* qsc = reinterpret_cast<float*>(red + 8);                   // F8: the set rows' scales of two tiles
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
+    const int v = blockIdx.x, p = blockIdx.y;                      // v < n_videos, p < n_set: the grid
+    const long o = (long)p * n_videos + v;
+
+    // the video's rows [lo, hi) and the set's rows [q0, q0 + m); every lookup is clamped
+    long lo = v_off[v], hi = v_off[v + 1];
+    lo = lo < 0 ? 0 : (lo > N ? N : lo);
+    hi = hi < lo ? lo : (hi > N ? N : hi);
+    const long V = hi - lo;
+    long q0 = q_off[p];
+    q0 = q0 < 0 ? 0 : (q0 >= Qt ? Qt - 1 : q0);
+    long m_l = (long)q_off[p + 1] - q0;
+    m_l = m_l > Qt - q0 ? Qt - q0 : m_l;
+    const int m = m_l < 1 ? 1 : (m_l > COVER_MAX ? COVER_MAX : (int)m_l);
+    if (V < 1) {                                                   // block-uniform; only under a broken v_off
+        if (tid == 0) { fwd[o] = 0.0f; bwd[o] = 0.0f; }
+        return;
+    }
+    const int n_t = (m + BN - 1) / BN;
+    const long n_slab = (V + BQ - 1) / BQ;
+
+    for (int i = tid; i < m; i += 256) rowmax[i] = -INFINITY;     // read after the second tile's first barrier at the earliest
+
+    uint4 pre[4];
+    float pqs = 0.0f;
+    const float one = 1.0f;
+    auto issue = [&](int t, int kc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i, row = e >> 4, c16 = e & 15;
+            const int l = t * BN + row;
+            pre[i] = l < m ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Tq) + (q0 + l) * ROWB + kc * 256 + c16 * 16)
+                           : make_uint4(0, 0, 0, 0);
+        }
+        if constexpr (F8) {
+            if (kc == 0 && tid < BN) {                             // the set rows' scales ride with the tile's first chunk
+                const int l = t * BN + tid;
+                pqs = l < m ? q_scale[q0 + l] : 0.0f;
+            }
+        }
+    };
+
+    int pend = -1;                                                 // the first set row of the tile whose stage awaits its fold
+    auto fold = [&]() {
+        if (pend >= 0 && tid < BN && pend + tid < m) {
+            const float a = fmaxf(fmaxf(stage[tid], stage[BN + tid]), fmaxf(stage[2 * BN + tid], stage[3 * BN + tid]));
+            rowmax[pend + tid] = fmaxf(rowmax[pend + tid], a);
+        }
+    };
+    // the tile row whose maximum this lane keeps: accumulator (rt, r) = (col >> 4, col & 15) of its half-wave
+    const int keep_row = 32 * (col >> 4) + acc_row(col & 15, lane);
+
+    long long bsum = 0;                                            // the lane's share of B
+    long g = 0;                                                    // tiles so far: the parity of the scale buffers
+    issue(0, 0);
+    for (long s = 0; s < n_slab; ++s) {
+        const long cme = s * BQ + wave * 32 + col;
+        const bool cok = cme < V;
+        const long nrow = lo + (cok ? cme : V - 1);                // a tail column repeats the video's last row
+        frag_t qf[NFR];                                            // the wave's 32 video rows, resident for the slab
+        {
+            const T* vrow = Vn + nrow * RC;
+#pragma unroll
+            for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(vrow, j, lane);
+        }
+        float vs = 1.0f;
+        if constexpr (F8) vs = v_scale[nrow];
+        float bmax = -INFINITY;
+        for (int t = 0; t < n_t; ++t, ++g) {
+            if constexpr (F8) {
+                // label_kernel's argument: read after this tile's barriers, written again behind the next tile's
+                if (tid < BN) qsc[(g & 1) * BN + tid] = pqs;
+            }
+            f32x16 acc[2];
+            tile_scores<T>(tile, sc, tid, lane, pre, one, qf, vs, acc, [&](int kc) {
+                if (kc == 0) fold();
+                if (kc + 1 < NCH) issue(t, kc + 1);
+                else if (t + 1 < n_t) issue(t + 1, 0);
+                else if (s + 1 < n_slab) issue(0, 0);
+            });
+            if constexpr (F8) {
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        const float4 s4 = *reinterpret_cast<const float4*>(qsc + (g & 1) * BN + rt * 32 + 8 * gq + 4 * (lane >> 5));
+                        acc[rt][4 * gq + 0] *= s4.x;
+                        acc[rt][4 * gq + 1] *= s4.y;
+                        acc[rt][4 * gq + 2] *= s4.z;
+                        acc[rt][4 * gq + 3] *= s4.w;
+                    }
+            }
+            const int left = m - t * BN;                           // the tile's rows [0, left) are the set's
+            if (left >= BN) {                                      // block-uniform
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) bmax = fmaxf(bmax, acc[rt][r]);
+            } else {
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (rt * 32 + acc_row(r, lane) < left) bmax = fmaxf(bmax, acc[rt][r]);
+            }
+            int w = 0;
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int a = half_wave_max(order_key(__float_as_int(acc[rt][r])));
+                    w = col == rt * 16 + r ? a : w;
+                }
+            // behind this tile's last barrier; folded behind the next one
+            stage[wave * BN + keep_row] = __int_as_float(order_key(w));
+            pend = t * BN;
+        }
+        bmax = fmaxf(bmax, __shfl_xor(bmax, 32, 64));
+        if (lane < 32 && cok) bsum += cover_fix(bmax);
+    }
+    __syncthreads();
+    fold();
+    __syncthreads();
+    long long fsum = 0;
+    for (int i = tid; i < m; i += 256) fsum += cover_fix(rowmax[i]);
+    fsum = wave_sum_ll(fsum);
+    bsum = wave_sum_ll(bsum);
+    if (lane == 0) { red[wave] = fsum; red[4 + wave] = bsum; }
+    __syncthreads();
+    if (tid == 0) {
+        const long long F = red[0] + red[1] + red[2] + red[3], B = red[4] + red[5] + red[6] + red[7];
+        fwd[o] = __fdiv_rn(__ll2float_rn(F) * 0x1p-30f, (float)m);
+        bwd[o] = __fdiv_rn(__ll2float_rn(B) * 0x1p-30f, (float)V);
+    }
+}
+
+// one wave per set: lanes 0..31 carry the best so far, lanes 32..63 take the next 32 videos of score[p, :]; sort64v's order is the
+// sweeps' (score descending, equal scores by ascending row v_off[v])
+__global__ void __launch_bounds__(256) cover_select_kernel(const float* __restrict__ fwd, const float* __restrict__ bwd,
+                                                           const int* __restrict__ v_off, long n_set, long n_videos, int rank, int k,
+                                                           float* __restrict__ top_s, int* __restrict__ top_n, int* __restrict__ top_v) {
+#pragma clang fp contract(off)
+    const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (p >= n_set) return;
+    float s = -INFINITY;
+    int n = SENT_ROW, v = -1;
+    for (long c0 = 0; c0 < n_videos; c0 += 32) {
+        if (lane >= 32) {
+            const long c = c0 + lane - 32;
+            s = -INFINITY;
+            n = SENT_ROW;
+            v = -1;
+            if (c < n_videos) {
+                const float f = fwd[p * n_videos + c], b = bwd[p * n_videos + c];
+                s = rank == TAN_COVER_QUERY ? f : rank == TAN_COVER_VIDEO ? b : (f + b) * 0.5f;
+                n = v_off[c];
+                v = (int)c;
+            }
+        }
+        sort64v(s, n, v, lane);
+    }
+    if (lane < k) {
+        top_s[p * k + lane] = s;
+        top_n[p * k + lane] = n;
+        top_v[p * k + lane] = n != SENT_ROW ? v : -1;
+    }
+}
+
+template <typename T>
+int cover_launch(const void* Tq, const void* Vn, long Qt, long N, const int* q_off, long n_set, const int* v_off, long n_videos, int rank,
+                 int k, float* fwd, float* bwd, float* top_s, int* top_n, int* top_v, hipStream_t st, const float* q_scale = nullptr,
+                 const float* v_scale = nullptr) {
+    static std::atomic<unsigned long long> lds_done{0};
+    const hipError_t attr = ensure_dyn_lds((const void*)cover_kernel<T>, cover_lds<T>(), lds_done);
+    if (attr != hipSuccess) return (int)attr;
+    hipLaunchKernelGGL((cover_kernel<T>), dim3((unsigned)n_videos, (unsigned)n_set), dim3(256), cover_lds<T>(), st, (const T*)Tq,
+                       (const T*)Vn, Qt, N, q_off, (int)n_set, v_off, (int)n_videos, q_scale, v_scale, fwd, bwd);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cover_select_kernel, dim3(cdiv(n_set, 4)), dim3(256), 0, st, (const float*)fwd, (const float*)bwd, v_off, n_set,
+                       n_videos, rank, k, top_s, top_n, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- tan_label_runs: the rows' best labels -> label segments (include/tan_hip.h) ----
 // lab[n] is the row's column-0 label (clamped into [0, L)) if its score is >= threshold, else -1.  A row STARTS a run if lab != -1
 // and the row before it is in another video or has another lab, and ENDS one by the same rule on the row after it: every maximal
@@ -1869,6 +2131,35 @@ extern "C" int tan_clip_topk_e4m3(const void* Tq, const float* q_scale, const vo
                                   int* top_row, int* top_video, void* ws, void* stream) {
     return clip_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, c_off, n_clip, v_off, n_videos, k, splits, top_score, top_row,
                      top_video, ws, stream);
+}
+
+extern "C" int tan_cover_max_rows(void) { return COVER_MAX; }
+
+static int cover_topk(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+               const int* q_off, long n_set, const int* v_off, long n_videos, int rank, int k, float* fwd, float* bwd,
+               float* top_score, int* top_row, int* top_video, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && q_off && v_off && fwd && bwd && top_score && top_row && top_video);
+    TAN_REQUIRE(C == RC && N >= 1 && N < (1L << 31) && n_set >= 1 && n_set <= 65535 && Qt >= n_set && Qt <= COVER_MAX * n_set &&
+                n_videos >= 1 && n_videos <= N && k >= 1 && k <= KMAX && k <= n_videos);
+    TAN_REQUIRE(rank == TAN_COVER_QUERY || rank == TAN_COVER_VIDEO || rank == TAN_COVER_BOTH);
+    return by_format(fmt, [&](auto r) {
+        return cover_launch<typename decltype(r)::type>(Tq, Vn, Qt, N, q_off, n_set, v_off, n_videos, rank, k, fwd, bwd, top_score,
+                                                        top_row, top_video, (hipStream_t)stream, q_scale, v_scale);
+    });
+}
+
+extern "C" int tan_cover_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* q_off, long n_set,
+                              const int* v_off, long n_videos, int rank, int k, float* fwd, float* bwd, float* top_score, int* top_row,
+                              int* top_video, void* stream) {
+    return cover_topk(dtype, Tq, nullptr, Vn, nullptr, Qt, N, C, q_off, n_set, v_off, n_videos, rank, k, fwd, bwd, top_score, top_row,
+                      top_video, stream);
+}
+
+extern "C" int tan_cover_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                                   const int* q_off, long n_set, const int* v_off, long n_videos, int rank, int k, float* fwd,
+                                   float* bwd, float* top_score, int* top_row, int* top_video, void* stream) {
+    return cover_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, q_off, n_set, v_off, n_videos, rank, k, fwd, bwd, top_score,
+                      top_row, top_video, stream);
 }
 
 static int label_topk(int fmt, const void* Tl, const float* l_scale, const void* Vn, const float* v_scale, long L, long N, int C, int k,

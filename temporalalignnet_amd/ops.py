@@ -874,6 +874,48 @@ def clip_topk(tq, vn, c_off, v_off, k, *, q_scale=None, v_scale=None, splits=0, 
     return top_s, top_r, top_v
 
 
+COVER_MAX_ROWS = 4096                                                 # tan_cover_max_rows(): the longest set of `cover_topk`
+COVER_RANKS = {"query": 0, "video": 1, "both": 2}                     # TAN_COVER_QUERY / _VIDEO / _BOTH
+
+
+def cover_topk(tq, vn, q_off, v_off, k, *, rank="both", q_scale=None, v_scale=None, check_offsets=False, out=None):
+    """The k videos that share the most seconds with each SET of query rows, in any order (tan_cover_topk / _e4m3; the Chamfer
+    similarity in 64-bit fixed point is defined in include/tan_hip.h): tq [Qt, 512] holds the sets' rows one after the other, q_off
+    [n_set + 1] int32 (device) each set's first row, then Qt (1 to 4096 rows each, at most 65535 sets); vn / v_off / q_scale /
+    v_scale as for `rank_topk_video`.  rank: "query" = fwd, the mean over the set's rows of each row's best second in the video
+    ("how much of my video is in v"); "video" = bwd, the mean over the video's seconds of each second's best row of the set ("how
+    much of v is in my video"); "both" = their mean.
+    Returns (top_score [n_set, k] f32, top_row [n_set, k] int32: the video's first index row, top_video [n_set, k] int32, fwd
+    [n_set, n_videos] f32, bwd [n_set, n_videos] f32): the lists by descending score, equal scores by ascending row; fwd / bwd are
+    the all-pairs result.  check_offsets: verify q_off and v_off on the host (one synchronisation); otherwise they are the caller's
+    contract.  out: caller-owned outputs (the same 5-tuple) instead of fresh ones.  ValueError: an unknown rank, or sizes the entry
+    point would refuse -- raised before anything touches the device."""
+    _video_args("cover_topk", tq, vn, v_off, q_scale, v_scale)
+    assert q_off.dtype == torch.int32 and q_off.dim() == 1 and q_off.numel() >= 2 and q_off.is_contiguous()
+    if rank not in COVER_RANKS:
+        raise ValueError(f"cover_topk: rank must be one of {sorted(COVER_RANKS)}, not {rank!r}")
+    Qt, N, ns, nv, dev = tq.shape[0], vn.shape[0], q_off.numel() - 1, v_off.numel() - 1, tq.device
+    if ns > 65535 or not ns <= Qt <= COVER_MAX_ROWS * ns:
+        raise ValueError(f"cover_topk: at most 65535 sets of 1 to {COVER_MAX_ROWS} rows each, not {ns} sets over {Qt} rows")
+    if not 1 <= int(k) <= min(32, nv):
+        raise ValueError(f"cover_topk: k must lie in [1, min(32, n_videos = {nv})]")
+    if check_offsets:
+        s, v = q_off.cpu(), v_off.cpu()
+        if int(s[0]) != 0 or int(s[-1]) != Qt or not bool(((s[1:] - s[:-1] >= 1) & (s[1:] - s[:-1] <= COVER_MAX_ROWS)).all()):
+            raise ValueError(f"cover_topk: q_off must start at 0, end at Qt and grow by 1 to {COVER_MAX_ROWS} per set")
+        if int(v[0]) != 0 or int(v[-1]) != N or not bool((v[1:] > v[:-1]).all()):
+            raise ValueError("cover_topk: v_off must start at 0, end at N and strictly increase")
+    if out is None:
+        top_s, top_r, top_v = _lists(ns, k, dev, video=True)
+        fwd, bwd = (torch.empty(ns, nv, dtype=torch.float32, device=dev) for _ in range(2))
+    else:
+        top_s, top_r, top_v, fwd, bwd = out
+        assert all(t.is_contiguous() for t in out) and fwd.shape == bwd.shape == (ns, nv) and top_s.shape == (ns, k)
+    _call("cover_topk", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(q_off), ns, _ptr(v_off), nv,
+          COVER_RANKS[rank], int(k), _f32(fwd), _f32(bwd), _f32(top_s), _ptr(top_r), _ptr(top_v))
+    return top_s, top_r, top_v, fwd, bwd
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

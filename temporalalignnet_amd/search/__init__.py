@@ -5,7 +5,7 @@ the dual encoder only about a video's own ASR sentences.  Here the video side is
 sentence is ranked against all of it.  One module per concern -- `index`, `text` (with what every search shares), `video`,
 `annotation`, `cluster`, `cli` -- each with its own account of what it does; every public name is re-exported here, and only here.
 A search starts from a sentence (`search`, `search_moments`, `search_sequences`, `search_rerank`), from a vocabulary (`annotate`),
-from a piece of video (`search_clips`, `search_copies`, `align_paths`) -- or from nothing: `discover_steps` clusters the index's
+from a piece of video (`search_clips`, `search_copies`, `align_paths`, `search_cover`) -- or from nothing: `discover_steps` clusters the index's
 seconds into the steps that recur in it, and its `StepClusters` serve as the vocabulary nobody had to write.
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
@@ -23,6 +23,7 @@ seconds into the steps that recur in it, and its `StepClusters` serve as the voc
     python -m temporalalignnet_amd.search similar --index I.npz [--shard I1.npz ...] [--host-resident] --clip VID:10-29 [-k K] [--keep-source]
     python -m temporalalignnet_amd.search similar --index I.npz --clip VID:0-599 --align --threshold X [--skew Y] [--pool P] [--piece S] [-k K]
     python -m temporalalignnet_amd.search similar --index I.npz --clip VID:0-599 --align --threshold X --map OUT.csv
+    python -m temporalalignnet_amd.search similar --index I.npz --clip VID:0-599 --cover [--rank both|query|video] [-k K] [--keep-source]
     python -m temporalalignnet_amd.search discover --index I.npz [--shard I1.npz ...] [--host-resident] -k 64 [--iters 10] [--seed 0]
         --out clusters.npz [--exemplars 3] [--labels steps.txt --checkpoint C --vocab V] [--segments seg.csv --threshold X [--min-len M] [--smooth P]]
     python -m temporalalignnet_amd.search annotate --index J.npz --clusters clusters.npz [-k K] [--threshold X] ... --out segments.csv
@@ -34,6 +35,7 @@ from .cluster import MAX_CLUSTERS, StepClusters, centroid_image, discover_steps 
 from .index import E4M3, RowFilter, ShardedIndex, VideoIndex, _index_chunks, build_index, plan_index_windows, restrict_spans  # noqa: F401
 from .text import (RERANK_TEXT_SLOTS, TEMPERATURE, Moment, Reranked, SequenceHit, _rerank_table,    # noqa: F401
                    _Sweep, _TopLists, query_features, rerank_window, search, search_moments, search_rerank, search_sequences)
-from .video import (EMPTY_ROW, MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, PIECE_ROWS, ClipHit, CopyHit, CopyPath, align_paths,  # noqa: F401
-                    align_spans, align_tables, clip_features, clip_spans, copy_interval, copy_inverse, copy_pieces, drop_source,
-                    path_tables, piece_offsets, search_clips, search_copies, transfer_segments)
+from .video import (EMPTY_ROW, MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, PIECE_ROWS, ClipHit, CopyHit,  # noqa: F401
+                    CopyPath, CoverHit, align_paths, align_spans, align_tables, clip_features, clip_spans, copy_interval,
+                    copy_inverse, copy_pieces, drop_source, path_tables, piece_offsets, search_clips, search_copies, search_cover,
+                    transfer_segments)

@@ -13,7 +13,7 @@ from .cluster import MAX_CLUSTERS, StepClusters, discover_steps
 from .coarse import CoarseImage
 from .index import E4M3, ShardedIndex, VideoIndex, build_index
 from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
-from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, search_clips, search_copies
+from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, search_clips, search_copies, search_cover
 
 
 def _parser():
@@ -92,6 +92,12 @@ def _parser():
     p.add_argument("--map", default=None, metavar="OUT.csv",
                    help="with --align: write the time map of every hit, one row `query,vid,query_second,first,last` per aligned second "
                         "of the clip (query_second on the clip's own video timeline; first..last the seconds of vid that show it)")
+    p.add_argument("--cover", action="store_true",
+                   help=f"rank videos by the seconds they share with the clip (then up to {MAX_COVER_SECONDS} seconds) in any order and "
+                        "at any pace, as `vid score forward backward`")
+    p.add_argument("--rank", choices=("both", "query", "video"), default=None,
+                   help="with --cover: rank by how much of the clip is in the video (query), how much of the video is in the clip "
+                        "(video), or the mean of the two (both, the default)")
     p = sub.add_parser("discover", help="which steps recur in the corpus: cluster the index's seconds (no checkpoint, no vocabulary)")
     _index_options(p)
     _model_options(p, required=False)
@@ -206,6 +212,8 @@ def _check_discover(ap, a):
 
 def _check_similar(ap, a):
     _refuse(ap,
+            (a.cover and a.align, "--cover does not go with --align"),
+            (a.rank is not None and not a.cover, "--rank needs --cover"),
             (not a.align and any(x is not None for x in (a.threshold, a.skew, a.pool, a.piece)),
              "--threshold / --skew / --pool / --piece need --align"),
             (a.map is not None and not a.align, "--map needs --align"),
@@ -219,7 +227,7 @@ def _check_similar(ap, a):
         a.clip = [parse_within(c, "--clip") for c in a.clip]
     except ValueError as e:
         ap.error(str(e))
-    most = MAX_ALIGN_SECONDS if a.align else MAX_CLIP_SECONDS
+    most = MAX_ALIGN_SECONDS if a.align else MAX_COVER_SECONDS if a.cover else MAX_CLIP_SECONDS
     for vid, first, last in a.clip:
         if first > last:
             ap.error(f"--clip {vid}:{first}-{last}: FIRST is after LAST")
@@ -302,11 +310,18 @@ def _run_similar(a):
             found = search_copies(idx, a.clip, a.k, 32 if a.pool is None else a.pool, 16 if a.piece is None else a.piece,
                                   threshold=a.threshold, skew=a.skew or 0.0, exclude_source=not a.keep_source,
                                   paths=a.map is not None)
+        elif a.cover:
+            found = search_cover(idx, a.clip, a.k, a.rank or "both", exclude_source=not a.keep_source)
         else:
             found = search_clips(idx, a.clip, a.k, exclude_source=not a.keep_source)
     except ValueError as e:
         print(f"similar: {e}", file=sys.stderr)
         return 2
+    if a.cover:
+        for hits in found:
+            for h in hits:
+                print(f"{h.vid}\t{h.score:.6f}\t{h.forward:.6f}\t{h.backward:.6f}")
+        return 0
     if a.map is not None:                              # only with --align
         with open(a.map, "w") as f:
             f.write("query,vid,query_second,first,last\n")

@@ -37,6 +37,11 @@ CopyPath = namedtuple("CopyPath", ("hit", "seconds"))
 MAX_ALIGN_SECONDS = 4096        # a query of `align_spans`: 12 bits of tan_local_align's packed origin
 PIECE_ROWS = 32                 # `align_spans` hands a query to tan_sequence_scores as sequences of this many rows
 EMPTY_ROW = 0x7fffffff          # the row of an empty top-k slot (include/tan_hip.h)
+# one hit of `search_cover`: the video, the score it was ranked by, and both directions of the Chamfer similarity: forward = the mean
+# over the QUERY's seconds of each one's best second in the video, backward = the mean over the VIDEO's seconds of each one's best
+# second of the query
+CoverHit = namedtuple("CoverHit", ("vid", "score", "forward", "backward"))
+MAX_COVER_SECONDS = 4096        # a query of `search_cover`: the rows of tan_cover_topk's LDS array of row maxima
 
 
 def _video_number(index, vid, by_name):
@@ -406,3 +411,60 @@ def search_copies(index, queries, k=10, pool=32, piece=16, *, threshold, skew=0.
         if hit is not None:
             out[q].append((-(hit.hit if paths else hit).score, gv, hit))
     return [[hit for _, _, hit in sorted(hits, key=lambda e: e[:2])[:k]] for hits in out]
+
+
+@torch.no_grad()
+def search_cover(index, queries, k=10, rank="both", exclude_source=False):
+    """Video to video whatever the order and the pace: per QUERY the videos of the corpus that share the most seconds with it,
+    [[CoverHit(vid, score, forward, backward)]] by descending score (equal scores by index row).  A query is (vid, first, last) --
+    seconds of a video of this index, inclusive --, a bare vid (the whole video; a string names the first video that carries it, an
+    int is a video number) or a float tensor [m, 512] of index-style rows; 1 to 4096 seconds.  forward is the mean over the query's
+    seconds of each second's best score in the hit's video ("how much of my video is in it": a long compilation that contains the
+    query scores high), backward the mean over the hit's seconds of each second's best score in the query ("how much of it is in my
+    video": a short excerpt of the query scores high); rank = "query" orders by forward, "video" by backward, "both" by their
+    mean.  The scores are `search`'s (the stitched dual cosine), the means are `tan_cover_topk`'s: sums in 64-bit fixed point, the
+    same bits whatever the tiling or the shards (include/tan_hip.h).
+    k is clamped to the number of videos and must lie in [1, 32].  exclude_source: leave out the video a query was cut from (a
+    tensor query has none); the sweep is asked for k + 1, so k <= 31.
+    `index`: a `VideoIndex`, or a `ShardedIndex` (host-resident too) -- one sweep and one `tan_topk_fold` per shard, exactly what
+    `VideoIndex.concat` of its shards gives.  One read-back.  The all-pairs forward / backward block of a shard view (8 bytes x
+    queries x videos) is held on the device during its sweep.  There is no `restrict=` here.  ValueError before anything touches
+    the device: an unknown rank, k out of range, and what `clip_spans` raises."""
+    queries = list(queries)
+    if rank not in ops.COVER_RANKS:
+        raise ValueError(f"search_cover: rank must be one of {sorted(ops.COVER_RANKS)}, not {rank!r}")
+    if not queries:
+        return []
+    whole = {}
+    for q, query in enumerate(queries):                                    # a bare vid: the whole video
+        if isinstance(query, (str, int, np.integer)):
+            v = _video_number(index, query, whole)
+            if v is None:
+                raise ValueError(f"clip {q}: no video {query!r} in the index")
+            queries[q] = (v, 0, int(index.v_off[v + 1] - index.v_off[v]) - 1)
+    spans = clip_spans(index, queries, MAX_COVER_SECONDS)
+    if len(queries) > 65535:
+        raise ValueError("search_cover: at most 65535 queries per call")
+    k = min(int(k), len(index.vids))
+    kk = min(k + 1, len(index.vids)) if exclude_source else k
+    if not 1 <= k <= kk <= 32:
+        raise ValueError("search_cover: k must lie in [1, 32], and in [1, 31] with exclude_source")
+    tq, q_off = clip_features(index, queries, MAX_COVER_SECONDS)
+    sweep = _Sweep(index, tq)
+    top = _TopLists(index, len(queries), kk, 3)
+    for s, feat, scale, v_off in index.shard_views():
+        score, row, video, fwd, bwd = ops.cover_topk(sweep.tq, feat, q_off, v_off, min(kk, v_off.numel() - 1), rank=rank,
+                                                     **sweep.scales(scale))
+        at = video.long()
+        top.add(s, (score, row, video, fwd.gather(1, at).view(torch.int32), bwd.gather(1, at).view(torch.int32)))
+    score, shard, (row, video, fwd, bwd) = top.read()                      # shard-local; an empty slot has row 0x7fffffff
+    fwd, bwd = fwd.view(np.float32), bwd.view(np.float32)
+    out = []
+    for p, (m, source) in enumerate(spans):
+        n = int((row[p] != EMPTY_ROW).sum())
+        number, _ = _locate_videos(index, shard[p, :n], video[p, :n])
+        entries = [(int(number[i]), float(score[p, i]), float(fwd[p, i]), float(bwd[p, i])) for i in range(n)]
+        if exclude_source:
+            entries = drop_source(entries, None if source is None else source[0], k)
+        out.append([CoverHit(index.vids[gv], sc, f, b) for gv, sc, f, b in entries])
+    return out

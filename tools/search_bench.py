@@ -65,6 +65,9 @@ sweep), `filtered_ms`, `plain_ms` (`ops.rank_topk` over the whole index) beside 
 the feature: `index_select` of the admitted rows, then the plain sweep over them, the gather included).  `equals_gather`: the filtered
 lists have the gathered sweep's scores (bit patterns) and rows.
 
+--cover times cover search INSTEAD (`ops.cover_topk`, bf16 and e4m3, one set of m rows for m in --cover-rows; use --rows 1048576):
+`cover_topk_ms` beside `label_topk_ms`, `ops.label_topk(k = 1)` at L = m over the same rows -- the same MFMA work in the same
+organisation without the two reductions --, the two alternating call by call, and `self_pair_spread`, cover_topk against itself.
 --annotate times corpus annotation INSTEAD (`ops.label_topk` / `ops.label_topk_e4m3`, then `ops.label_runs` over its lists), bf16 and
 e4m3, for L in --labels and k in --annotate-k (default 1, 5; use --rows 1048576): `label_topk_ms` beside `swapped_rank_ms`, what a caller has without the
 entry point -- `ops.rank_topk` with the rows as queries and the labels as the index, over chunks of rows small enough for its scratch
@@ -597,6 +600,36 @@ def annotate_table(N, v16, v8, s8, a):
     return rows
 
 
+def cover_table(N, v16, v8, s8, a):
+    """One row per (format, m): `ops.cover_topk` of ONE set of m rows over N rows in videos of 60 to 1 200 rows (rank "both", k = 10,
+    caller-owned outputs), alternating call by call with `ops.label_topk(k = 1)` at L = m over the same rows -- the same MFMA work in
+    the same organisation, without the two reductions -- and `self_pair_spread`, the same alternation of cover_topk with itself."""
+    v_off = video_layouts(N)["corpus"]
+    nv = v_off.numel() - 1
+    rows = []
+    for fmt in ("bf16", "e4m3"):
+        for m in a.cover_rows:
+            q = unit_rows(m, 9000 + m)
+            q_off = torch.tensor([0, m], dtype=torch.int32, device="cuda")
+            out = (torch.empty(1, 10, device="cuda"), torch.empty(1, 10, dtype=torch.int32, device="cuda"),
+                   torch.empty(1, 10, dtype=torch.int32, device="cuda"), torch.empty(1, nv, device="cuda"), torch.empty(1, nv, device="cuda"))
+            lab = (torch.empty(N, 1, device="cuda"), torch.empty(N, 1, dtype=torch.int32, device="cuda"))
+            if fmt == "bf16":
+                tq = q.to(torch.bfloat16)
+                cover = lambda: ops.cover_topk(tq, v16, q_off, v_off, 10, out=out)           # noqa: E731
+                label = lambda: ops.label_topk(tq, v16, 1, out=lab)                          # noqa: E731
+            else:
+                tq, qs = ops.quantize_rows_e4m3(q)
+                cover = lambda: ops.cover_topk(tq, v8, q_off, v_off, 10, q_scale=qs, v_scale=s8, out=out)   # noqa: E731
+                label = lambda: ops.label_topk_e4m3(tq, qs, v8, s8, 1, out=lab)              # noqa: E731
+            t_new, t_lab = timed_pair(cover, label, a.warmup, a.reps)
+            s_a, s_b = timed_pair(cover, cover, a.warmup, a.reps)
+            rows.append({"fmt": fmt, "m": m, "videos": nv, "cover_topk_ms": round(t_new, 4), "label_topk_ms": round(t_lab, 4),
+                         "new_over_label": round(t_new / t_lab, 4), "self_pair_spread": round(abs(s_a / s_b - 1), 4),
+                         "TFLOPs": round(2 * N * m * 512 / t_new / 1e9, 1)})
+    return rows
+
+
 def rerank_table(N, v16, stem, a):
     import time
 
@@ -707,6 +740,8 @@ def main():
     ap.add_argument("--annotate", action="store_true", help="time label_topk and label_runs instead (see the module docstring)")
     ap.add_argument("--labels", type=int, nargs="+", default=[128, 1024, 8192], help="with --annotate: vocabulary sizes")
     ap.add_argument("--annotate-k", type=int, nargs="+", default=list(ANNOTATE_KS), help="with --annotate: labels kept per row")
+    ap.add_argument("--cover", action="store_true", help="time cover_topk against label_topk(k = 1) at L = m instead (use --rows 1048576)")
+    ap.add_argument("--cover-rows", type=int, nargs="+", default=[128, 1024, 4096], help="with --cover: rows of the one set")
     a = ap.parse_args()
     N, k = a.rows, a.k
     if a.rerank:
@@ -740,6 +775,23 @@ def main():
         v16[r:r + SLICE] = x.to(torch.bfloat16)
         ops.quantize_rows_e4m3(x, v8[r:r + SLICE], s8[r:r + SLICE])
     del x
+    if a.cover:
+        rows = cover_table(N, v16, v8, s8, a)
+        res = {"rows": N, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "cover": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --cover --rows {N}: median of {a.reps} after {a.warmup} warm-ups, device events, caller-owned "
+                         f"outputs, {res['gpu']}\n")
+                fh.write("# cover_topk = ops.cover_topk of one set of m random unit rows over all rows, videos of 60 to 1 200 rows, rank both, "
+                         "k = 10; label_topk = ops.label_topk(k = 1) with the set as L = m labels over the same rows, the two alternating call by "
+                         "call; self_pair_spread = |ratio - 1| of cover_topk alternating with itself; TFLOPs = 2 N m 512 / cover_topk time\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>17}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>17}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
     if a.annotate:
         rows = annotate_table(N, v16, v8, s8, a)
         res = {"rows": N, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "annotate": rows}

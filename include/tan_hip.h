@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 108: tan_storyboard_select; 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -1285,6 +1285,42 @@ int tan_cluster_accumulate_e4m3(const void* Vn, const float* v_scale, long N, in
                                 long* sums, void* stream);
 int tan_cluster_centroids(const long* sums, const int* counts, const float* prev, long K, int C, float* cent, float* cohesion,
                           void* stream);
+
+/* ---- storyboards: the k seconds that together show a video best (`search.storyboard`) ----
+ * A video has rows r_0 .. r_{V-1}.  x[s][t] is the row sweep's score with row s as the QUERY row and row t as the index row: the bits
+ * tan_sequence_scores writes for the video's own rows, cut into 32-row pieces, against the video -- one row-major [V, V] block (e4m3:
+ * (acc * v_scale[t]) * q_scale[s], the row's own scale on both sides).  x[s][t] == x[t][s] is NOT assumed.  Greedy facility location:
+ *     fix(x)  = __float2ll_rn(x * 2^30f)                                    (tan_cover_topk's image; the multiply is exact)
+ *     C_0[t]  = -2^62 for every t
+ *     T_j(s)  = sum_t max(fix(x[s][t]), C_{j-1}[t])                         (64-bit integers: order-free)
+ *     s_j     = the s with the largest T_j(s); equal sums: the lowest s
+ *     stop before writing entry j (j >= 2) when
+ *             gain = T_j(s_j) - sum_t C_{j-1}[t] <= 0
+ *          or gain < G_min * V,   G_min = min(__float2ll_rn(min_gain * 2^30f), 2^40)
+ *     C_j[t]  = max(C_{j-1}[t], fix(x[s_j][t]))
+ *     owner[t] = j wherever fix(x[s_j][t]) > C_{j-1}[t] (strictly), else kept
+ *     coverage[j] = ((float) sum_t C_j[t] * 2^-30f) / (float) V             (int64 -> f32 round to nearest even, exact scaling, ONE f32 division)
+ * Contract: |x| <= 2 and finite (index rows are unit vectors), so no sum overflows; a gain is then below 2^32 * V, which is why the
+ * clamp of G_min changes nothing and G_min * V is exact.  The entries are stored 0-BASED: second[j - 1] = s_j as a second of the
+ * video (0 = its first), coverage[j - 1], and owner[t] = j - 1.  The first entry is always made (the row with the largest summed
+ * score; every owner is then 0); a row already chosen has gain 0, so no second is chosen twice.  Entries after a stop, and entries
+ * beyond V, hold second = -1 and coverage = 0.  coverage is the mean over the video's seconds of the best score to any second chosen
+ * so far: it does not decrease.  owner[t] is the entry that shows second t best, equal scores going to the earliest entry.  Every
+ * sum is an integer: given the bits of x the result depends on no reduction order, tiling or launch shape.
+ * tan_storyboard_select: x holds n_x elements; x_off [P] `long` element offsets and table [P, 2] int32 = (V, first owner slot) on the
+ *   device, the slot being the running sum of V over the entries before, sum_V the sum over all (tan_local_align's layout with m = V).
+ *   second int32 [P, k], coverage f32 [P, k]: always fully written; owner int32 [sum_V].  1 <= V <= 4096
+ *   (tan_storyboard_max_rows()), 1 <= k <= 4096, min_gain finite and >= 0.
+ *   One launch, one workgroup per video, which runs the k iterations itself: C in LDS (32 KiB), every candidate row read once per
+ *   iteration, a wave per row; no scratch, no atomics, bit-identical from run to run.  A video costs min(k, V) * V * V score reads:
+ *   V and k near their limits TOGETHER are one workgroup's serial chain of minutes.
+ *   A NULL pointer, n_x < 1, P or sum_V outside [1, 2^31), sum_V < P, k outside [1, 4096], a min_gain that is negative, infinite or
+ *   NaN: TAN_ERR_BAD_ARG, nothing launched, nothing written.  A table entry outside the limits, whose block leaves [0, n_x) or whose
+ *   slots leave [0, sum_V), gets the empty result (second = -1, coverage = 0) and its owner slots are NOT written; every other entry
+ *   is computed, and nothing is read or written out of bounds -- tan_local_align's convention.                                      */
+int tan_storyboard_max_rows(void);                 /* 4096 */
+int tan_storyboard_select(const float* x, long n_x, const long* x_off, const int* table, long P, long sum_V, int k, float min_gain,
+                          int* second, float* coverage, int* owner, void* stream);
 
 #ifdef __cplusplus
 }

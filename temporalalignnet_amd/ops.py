@@ -916,6 +916,59 @@ def cover_topk(tq, vn, q_off, v_off, k, *, rank="both", q_scale=None, v_scale=No
     return top_s, top_r, top_v, fwd, bwd
 
 
+STORYBOARD_MAX_ROWS = 4096                                            # tan_storyboard_max_rows(): the longest video of `storyboard_select`
+STORYBOARD_MAX_K = 4096
+
+
+def storyboard_select(x, x_off, table, k, *, min_gain=0.0, sum_V=None, out=None):
+    """The k seconds that together show each video best (tan_storyboard_select; greedy facility location in 64-bit fixed point, defined
+    bit for bit in include/tan_hip.h): x f32 [n_x] holds row-major [V, V] blocks of a video's second x second scores as
+    `sequence_scores` writes them for the video's own rows; x_off int64 [P] each block's first element, table int32 [P, 2] = (V,
+    first owner slot = the running sum of V), both on the device; 1 <= V <= 4096, 1 <= k <= 4096, min_gain finite and >= 0: the
+    selection stops when the next second would raise the mean coverage by less than min_gain (or not at all).
+    Returns (second int32 [P, k], coverage f32 [P, k], owner int32 [sum_V]) on the device, nothing read back: the chosen seconds in
+    the order they were chosen, the mean over the video's seconds of the best score to any second chosen so far, and per second of
+    the video the entry (0-based) that shows it best.  Entries after a stop or beyond V are (-1, 0).  A table entry that breaks the
+    limits, or whose block or owner slots leave x / owner, gives the empty result and its owner slots are NOT written.
+    sum_V: the number of owner slots, the sum of the table's V; the caller built the table and knows it -- without it the wrapper
+    reads the table's last entry back (V + slot: one synchronisation).  out: caller-owned (second, coverage, owner) instead of fresh
+    ones.  ValueError: shapes, dtypes or sizes the entry point would refuse -- raised before anything touches the device."""
+    what = "storyboard_select"
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError(f"{what}: x is f32 [n_x], contiguous, n_x >= 1")
+    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
+        raise ValueError(f"{what}: x_off is int64 [P], contiguous, P >= 1")
+    P = x_off.numel()
+    if table.dtype != torch.int32 or table.shape != (P, 2) or not table.is_contiguous():
+        raise ValueError(f"{what}: table is int32 [P, 2] = (V, first owner slot), contiguous")
+    k, min_gain = int(k), float(min_gain)
+    if not 1 <= k <= STORYBOARD_MAX_K:
+        raise ValueError(f"{what}: k must lie in [1, {STORYBOARD_MAX_K}]")
+    if not (min_gain >= 0 and math.isfinite(min_gain)):
+        raise ValueError(f"{what}: min_gain finite and >= 0")
+    if sum_V is not None and not P <= int(sum_V) < 2 ** 31:
+        raise ValueError(f"{what}: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
+    if out is not None:
+        second, coverage, owner = out
+        if second.dtype != torch.int32 or coverage.dtype != torch.float32 or owner.dtype != torch.int32 or second.shape != (P, k) \
+                or coverage.shape != (P, k) or owner.dim() != 1 or (sum_V is not None and owner.numel() != int(sum_V)) \
+                or not all(t.is_contiguous() for t in out):
+            raise ValueError(f"{what}: out is (second int32 [P, k], coverage f32 [P, k], owner int32 [sum_V]), contiguous")
+    if sum_V is None:
+        t = table[-1:].cpu().long()
+        sum_V = int(t[0, 0] + t[0, 1])
+        if not P <= sum_V < 2 ** 31 or (out is not None and out[2].numel() != sum_V):
+            raise ValueError(f"{what}: P <= sum_V < 2^31, and owner holds sum_V slots (sum_V: the sum of the table's V)")
+    sum_V = int(sum_V)
+    if out is None:
+        dev = x.device
+        second, coverage, owner = (torch.empty(P, k, dtype=torch.int32, device=dev), torch.empty(P, k, dtype=torch.float32, device=dev),
+                                   torch.empty(sum_V, dtype=torch.int32, device=dev))
+    _lib.check(_lib.lib().tan_storyboard_select(_f32(x), x.numel(), _ptr(x_off), _ptr(table), P, sum_V, k, min_gain, _ptr(second),
+                                                _f32(coverage), _ptr(owner), _stream()), "tan_storyboard_select")
+    return second, coverage, owner
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

@@ -12,6 +12,7 @@ from .annotation import annotate, write_per_second_csv, write_segments_csv
 from .cluster import MAX_CLUSTERS, StepClusters, discover_steps
 from .coarse import CoarseImage
 from .index import E4M3, ShardedIndex, VideoIndex, build_index
+from .summary import MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, storyboard, write_storyboard_csv
 from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
 from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, search_clips, search_copies, search_cover
 
@@ -116,6 +117,18 @@ def _parser():
     p = sub.add_parser("coarse", help="the MXFP4 image of an index, 272 bytes per second: what `query --coarse` takes (no checkpoint)")
     _index_options(p)
     p.add_argument("--out", required=True, metavar="FILE", help="the image (.npz)")
+    p = sub.add_parser("storyboard", help="the k seconds that best summarise each video (no checkpoint, no model)")
+    _index_options(p)
+    p.add_argument("-k", type=int, default=8, help=f"seconds per video at most, 1 to {MAX_STORYBOARD_K} (default 8)")
+    p.add_argument("--min-gain", type=float, default=None, metavar="X",
+                   help="stop a video's selection when the next second would raise its mean coverage by less than this (default 0: "
+                        "only when it would add nothing)")
+    p.add_argument("--only", action="append", default=None, metavar="VID", help="only this video (repeatable)")
+    p.add_argument("--only-file", default=None, metavar="PATH", help="only the videos listed here, one vid per line")
+    p.add_argument("--skip-long", action="store_true",
+                   help=f"leave out videos of more than {MAX_STORYBOARD_SECONDS} seconds instead of refusing them")
+    p.add_argument("--out", required=True, metavar="CSV", help="vid,rank,second,coverage,share: one row per chosen second")
+    p.add_argument("--npz", default=None, metavar="FILE", help="also save the storyboard (seconds, coverage, owners) as .npz")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
@@ -235,6 +248,13 @@ def _check_similar(ap, a):
             ap.error(f"--clip {vid}:{first}-{last} holds {last - first + 1} seconds; cut it into clips of at most {most} seconds")
 
 
+def _check_storyboard(ap, a):
+    _refuse(ap,
+            (not 1 <= a.k <= MAX_STORYBOARD_K, f"-k must lie in [1, {MAX_STORYBOARD_K}]"),
+            (a.min_gain is not None and not (a.min_gain >= 0 and np.isfinite(a.min_gain)), "--min-gain must be >= 0 and finite"),
+            (a.only is not None and a.only_file is not None, "--only does not go with --only-file"))
+
+
 def parse_within(text, option="--within"):
     """'VID:FIRST-LAST' -> (vid, first, last); the vid may hold colons itself"""
     vid, sep, span = text.rpartition(":")
@@ -336,6 +356,23 @@ def _run_similar(a):
     return 0
 
 
+def _run_storyboard(a):
+    idx = _load_index(a)
+    only = a.only if a.only is not None else _read_vids(a.only_file) if a.only_file is not None else None
+    try:
+        board = storyboard(idx, a.k, videos=only, min_gain=a.min_gain or 0.0, skip_long=a.skip_long)
+    except (ValueError, KeyError) as e:
+        print(f"storyboard: {e.args[0] if isinstance(e, KeyError) else e}", file=sys.stderr)
+        return 2
+    with open(a.out, "w", newline="") as f:
+        write_storyboard_csv(f, board)
+    if a.npz is not None:
+        board.save(a.npz)
+    print(f"{a.out}: {int((board.second >= 0).sum())} seconds of {len(board)} videos" +
+          (f", {len(board.skipped)} over-long videos left out" if board.skipped else ""), file=sys.stderr)
+    return 0
+
+
 def _write_segments(path, ann, a):
     with open(path, "w", newline="") as f:
         write_segments_csv(f, ann.segments(float("-inf") if a.threshold is None else a.threshold, a.min_len or 1, switch=a.smooth))
@@ -419,9 +456,9 @@ def _run_query(a):
 
 
 _CHECKS = dict(index=_check_index, query=_check_query, annotate=_check_annotate, similar=_check_similar, discover=_check_discover,
-               merge=lambda ap, a: None, coarse=lambda ap, a: None)
+               merge=lambda ap, a: None, coarse=lambda ap, a: None, storyboard=_check_storyboard)
 _RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, discover=_run_discover, merge=_run_merge,
-             coarse=_run_coarse)
+             coarse=_run_coarse, storyboard=_run_storyboard)
 
 
 def main(argv=None):

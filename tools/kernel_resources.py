@@ -1,10 +1,14 @@
 #!/usr/bin/env python
 """Registers, LDS and the occupancy they allow for every kernel of csrc/*.hip (compiles each file with `hipcc -S`; no GPU needed).
 A kernel whose VGPR + AGPR total exceeds 256 runs ONE wave per SIMD -- that is how the attention backward lost half its occupancy
-unnoticed.  usage: python tools/kernel_resources.py [substring-filter]"""
+unnoticed.  usage: python tools/kernel_resources.py [substring-filter | NAME]
+NAME: a filter kept by name -- `storyboard`: storyboard_select_kernel (csrc/tan_storyboard.hip), whose table is in DESIGN.md 3.26 and
+which must show no SCRATCH."""
 import glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+FILTERS = {"storyboard": "storyboard_select_kernel"}
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
+flt = FILTERS.get(flt, flt)
 for src in sorted(glob.glob(os.path.join(ROOT, "temporalalignnet_amd", "csrc", "*.hip"))):
     with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",

@@ -68,6 +68,13 @@ lists have the gathered sweep's scores (bit patterns) and rows.
 --cover times cover search INSTEAD (`ops.cover_topk`, bf16 and e4m3, one set of m rows for m in --cover-rows; use --rows 1048576):
 `cover_topk_ms` beside `label_topk_ms`, `ops.label_topk(k = 1)` at L = m over the same rows -- the same MFMA work in the same
 organisation without the two reductions --, the two alternating call by call, and `self_pair_spread`, cover_topk against itself.
+--storyboard times storyboards INSTEAD (`search.storyboard`'s two launches over ALL videos of --cover's corpus in one pass, k = 8, bf16 and
+e4m3; use --rows 1048576): `scores_ms`, `ops.sequence_scores` with the index's own rows as the queries, and `select_ms`,
+`ops.storyboard_select` over its blocks, as `select_GBs` over the k * sum V^2 * 4 bytes it must read (`of_stream`: of STREAM_TBS) -- beside
+`torch_ms`, what a caller has without the kernel on the same card from the same blocks: per video k iterations of
+`torch.maximum(fix(X), C).sum(1).argmax()` in int64, the two alternating call by call (`equals_torch`: the same seconds, and
+the coverage bits that the header's formula makes of the composition's exact int64 sums), `self_pair_spread`, the kernel against itself, and `longest_alone_ms`, the launch over the longest video alone: one workgroup's
+serial chain, the tail the launch cannot end before.
 --annotate times corpus annotation INSTEAD (`ops.label_topk` / `ops.label_topk_e4m3`, then `ops.label_runs` over its lists), bf16 and
 e4m3, for L in --labels and k in --annotate-k (default 1, 5; use --rows 1048576): `label_topk_ms` beside `swapped_rank_ms`, what a caller has without the
 entry point -- `ops.rank_topk` with the rows as queries and the labels as the index, over chunks of rows small enough for its scratch
@@ -630,6 +637,64 @@ def cover_table(N, v16, v8, s8, a):
     return rows
 
 
+STORYBOARD_K = 8
+
+
+def torch_storyboard(x, x_off, lens, k, second, total):
+    """What a caller writes without tan_storyboard_select, from the same blocks: per video k iterations of
+    `torch.maximum(fix(X), C).sum(1).argmax()` in int64 (k <= every V and no stop test: random rows always gain); no host round trip.
+    second int32 [P, k]; total int64 [P, k]: sum C after every entry, exact"""
+    for p, (o, V) in enumerate(zip(x_off, lens)):
+        F = torch.round(x[o:o + V * V].view(V, V) * 2.0 ** 30).to(torch.int64)
+        C = torch.full((V,), -2 ** 62, dtype=torch.int64, device=x.device)
+        for j in range(k):
+            s = torch.maximum(F, C).sum(1).argmax()
+            C = torch.maximum(C, F.index_select(0, s.view(1))[0])
+            second[p, j] = s
+            total[p, j] = C.sum()                                  # int64: the host makes the coverage of it, outside the timing
+
+
+def storyboard_table(N, v16, v8, s8, a):
+    """One row per format: the two launches of `search.storyboard` over all videos of `cover_table`'s corpus in ONE pass (see the module
+    docstring)"""
+    from temporalalignnet_amd.search import align_tables, piece_offsets
+    v_off = video_layouts(N)["corpus"]
+    lens = np.diff(v_off.cpu().numpy().astype(np.int64))
+    nv, k = len(lens), STORYBOARD_K
+    s_off, first = piece_offsets(lens)
+    hits, hit_off, x_off, table, n_x, sum_V = align_tables(lens, lens, first[:-1], np.arange(nv))
+    dev = lambda arr, dt: torch.from_numpy(np.ascontiguousarray(arr, dtype=dt)).cuda()        # noqa: E731
+    s_off_d, hits_d, hit_off_d, x_off_d, table_d = dev(s_off, np.int32), dev(hits, np.int32), dev(hit_off, np.int64), dev(x_off, np.int64), \
+        dev(table[:, 1:], np.int32)
+    big = int(np.argmax(lens))
+    one_off, one_table = dev([x_off[big]], np.int64), dev([[lens[big], 0]], np.int32)
+    x = torch.empty(n_x, device="cuda")
+    new = lambda n: (torch.empty(n, k, dtype=torch.int32, device="cuda"), torch.empty(n, k, device="cuda"))        # noqa: E731
+    out, out_one = new(nv) + (torch.empty(sum_V, dtype=torch.int32, device="cuda"),), new(1) + (torch.empty(int(lens[big]), dtype=torch.int32, device="cuda"),)
+    t_second, t_total = torch.empty(nv, k, dtype=torch.int32, device="cuda"), torch.empty(nv, k, dtype=torch.int64, device="cuda")
+    rows = []
+    for fmt in ("bf16", "e4m3"):
+        feat, kw = (v16, {}) if fmt == "bf16" else (v8, dict(q_scale=s8, v_scale=s8))
+        scores = lambda: ops.sequence_scores(feat, feat, s_off_d, v_off, hits_d, hit_off_d, x, **kw)             # noqa: E731
+        select = lambda: ops.storyboard_select(x, x_off_d, table_d, k, sum_V=sum_V, out=out)                    # noqa: E731
+        alone = lambda: ops.storyboard_select(x, one_off, one_table, k, sum_V=int(lens[big]), out=out_one)      # noqa: E731
+        compose = lambda: torch_storyboard(x, x_off, lens, k, t_second, t_total)                                  # noqa: E731
+        t_scores, _ = timed(scores, a.warmup, a.reps)
+        t_sel, t_torch = timed_pair(select, compose, a.warmup, a.reps)
+        s_a, s_b = timed_pair(select, select, a.warmup, a.reps)
+        t_alone, _ = timed(alone, a.warmup, a.reps)
+        # coverage of the composition's exact sums by the header's formula: int64 -> f32 to nearest even, * 2^-30, ONE f32 division
+        want_cov = (t_total.cpu().numpy().astype(np.float32) * np.float32(2.0 ** -30)) / lens.astype(np.float32)[:, None]
+        same_s = bool(torch.equal(out[0], t_second))
+        same_c = bool(np.array_equal(out[1].cpu().numpy().view(np.int32), want_cov.view(np.int32)))
+        gbs = k * float((lens * lens).sum()) * 4 / t_sel / 1e6
+        rows.append({"fmt": fmt, "videos": nv, "sum_V2": int((lens * lens).sum()), "scores_ms": round(t_scores, 4), "select_ms": round(t_sel, 4),
+                     "torch_ms": round(t_torch, 4), "select_over_torch": round(t_sel / t_torch, 5), "self_pair_spread": round(abs(s_a / s_b - 1), 4),
+                     "equals_torch": same_s and same_c, "same_seconds": same_s, "same_coverage": same_c, "select_GBs": round(gbs, 1), "of_stream": round(gbs / (STREAM_TBS * 1e3), 4),
+                     "longest_V": int(lens[big]), "longest_alone_ms": round(t_alone, 4)})
+    return rows
+
+
 def rerank_table(N, v16, stem, a):
     import time
 
@@ -740,6 +805,7 @@ def main():
     ap.add_argument("--annotate", action="store_true", help="time label_topk and label_runs instead (see the module docstring)")
     ap.add_argument("--labels", type=int, nargs="+", default=[128, 1024, 8192], help="with --annotate: vocabulary sizes")
     ap.add_argument("--annotate-k", type=int, nargs="+", default=list(ANNOTATE_KS), help="with --annotate: labels kept per row")
+    ap.add_argument("--storyboard", action="store_true", help="time storyboard_select and its score blocks instead (use --rows 1048576)")
     ap.add_argument("--cover", action="store_true", help="time cover_topk against label_topk(k = 1) at L = m instead (use --rows 1048576)")
     ap.add_argument("--cover-rows", type=int, nargs="+", default=[128, 1024, 4096], help="with --cover: rows of the one set")
     a = ap.parse_args()
@@ -775,6 +841,25 @@ def main():
         v16[r:r + SLICE] = x.to(torch.bfloat16)
         ops.quantize_rows_e4m3(x, v8[r:r + SLICE], s8[r:r + SLICE])
     del x
+    if a.storyboard:
+        rows = storyboard_table(N, v16, v8, s8, a)
+        res = {"rows": N, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "storyboard": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --storyboard --rows {N}: median of {a.reps} after {a.warmup} warm-ups, device events, caller-owned "
+                         f"outputs, {res['gpu']}\n")
+                fh.write(f"# all videos (60 to 1 200 rows) in one pass, k = {STORYBOARD_K}; scores = ops.sequence_scores, the index's own rows as the "
+                         "queries; select = ops.storyboard_select over its blocks; torch = per video k iterations of "
+                         "torch.maximum(fix(X), C).sum(1).argmax() in int64 from the same blocks, alternating call by call with select; "
+                         "self_pair_spread = |ratio - 1| of select alternating with itself; select_GBs = k sum_V2 4 bytes / select time, of_stream: of "
+                         f"{STREAM_TBS} TB/s; longest_alone = select over the longest video alone (one workgroup)\n")
+                cols = list(rows[0])
+                fh.write(" ".join(f"{c:>17}" for c in cols) + "\n")
+                for r in rows:
+                    fh.write(" ".join(f"{str(r[c]):>17}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
     if a.cover:
         rows = cover_table(N, v16, v8, s8, a)
         res = {"rows": N, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "cover": rows}

@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 108: tan_storyboard_select; 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 109: tan_chapter_costs / _decode; 108: tan_storyboard_select; 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -1321,6 +1321,55 @@ int tan_cluster_centroids(const long* sums, const int* counts, const float* prev
 int tan_storyboard_max_rows(void);                 /* 4096 */
 int tan_storyboard_select(const float* x, long n_x, const long* x_off, const int* table, long P, long sum_V, int k, float min_gain,
                           int* second, float* coverage, int* owner, void* stream);
+
+/* ---- chapters: a video cut into contiguous scenes by an exact dynamic programme (`search.chapters`) ----
+ * Kernel temporal segmentation (Potapov et al., ECCV 2014) over a video's own block.  x[s][t] is the video's block exactly as
+ * storyboards define it above: the bits tan_sequence_scores writes.  x[s][t] == x[t][s] is NOT assumed; only sums over squares are
+ * used.  fix(x) = __float2ll_rn(x * 2^30f).  All arithmetic below is on 64-bit integers.  INF = 2^62.
+ * Costs, for 0 <= s < e <= V:
+ *     D(s,e) = sum_{s<=t<e} fix(x[t][t])
+ *     Q(s,e) = sum_{s<=i<e} sum_{s<=t<e} fix(x[i][t])
+ *     J(s,e) = D(s,e) - floor(Q(s,e) / (e - s))                            floor toward minus infinity
+ * Decode, with the parameters k, min_len >= 1 and penalty >= 0, and m = min(k, V):
+ *     G       = min(__float2ll_rn(penalty * 2^30f), 2^50)
+ *     dp_1[e] = J(0,e) if e >= min_len or e == V, else INF                  (a video shorter than min_len is one chapter)
+ *     dp_j[e] = min over s in [1, e - min_len] with dp_{j-1}[s] < INF of dp_{j-1}[s] + J(s,e)             (2 <= j <= m)
+ *               equal sums: the LOWEST s, kept as arg_j[e]; INF if there is no such s
+ *     j is feasible when dp_j[V] < INF (j = 1 always is)
+ *     count   = the lowest feasible j with the smallest dp_j[V] + (j - 1) * G
+ *     b_count = V;  b_{j-1} = arg_j[b_j]
+ *     start[c] = b_c for c = 0 .. count-1                                   (start[0] = 0)
+ *     chapter[t] = c for start[c] <= t < start[c+1]
+ *     scatter[j-1] = (float) dp_j[V] * 2^-30f                               (one int64 -> f32 rounding, exact scaling)
+ * scatter[j-1] is the f32 +infinity (bits 0x7f800000) for every infeasible j <= k; start[c] = -1 for c >= count.  penalty is
+ * absolute, in score x seconds: a boundary is kept only if it lowers the summed scatter by at least that much (merging two scenes of
+ * a and b seconds costs about ab / (a + b) times their squared distance, whatever the video's length).
+ * Contract: |x| <= 2 and finite.  Then |Q| <= 2^55, |J| < 2^45, every dp stays below 2^46 and (j - 1) * G < 2^58.
+ * x_off [P] `long` element offsets and table [P, 2] int32 = (V, first chapter slot) are tan_storyboard_select's tables.
+ * tan_chapter_costs: cost holds n_x 64-bit elements at the same element offsets as x: cost[x_off[p] + (e-1)*V + s] = J(s,e) for
+ *   0 <= s < e <= V.  The other half of a video's block is the kernels' to use; its contents are unspecified afterwards.  Nothing
+ *   outside a video's block is written.  Three launches over all videos of the call (row scans, the upper triangle's column scans,
+ *   the lower triangle's column scans with the transposed upper tile through LDS and the division), all in place in cost; the
+ *   column scans walk 64 x 64 tiles with carries.  No scratch, no atomics, no allocation; bit-identical from run to run.
+ *   A NULL pointer, n_x < 1, P outside [1, 2^31): TAN_ERR_BAD_ARG, nothing launched.  A table entry with V outside [1, 4096]
+ *   (tan_chapter_max_rows()) or whose block leaves [0, n_x) is skipped: its cost block stays untouched (the slot column is not read).
+ * tan_chapter_decode: count int32 [P], start int32 [P, k], scatter f32 [P, k]: always fully written; chapter int32 [sum_V].
+ *   1 <= V <= 4096, 1 <= k <= 256, 1 <= min_len <= 4096, penalty finite and >= 0.  ws: tan_chapter_decode_ws_bytes(P, sum_V, k)
+ *   bytes (sum_V * k * 2: arg_j[e] as 16 bits; TAN_ERR_BAD_ARG for sizes the entry point refuses), caller-owned.
+ *   One launch, one workgroup of 16 waves per video, which runs every level itself: dp_{j-1} and dp_j in LDS (2 x 4097 x 8 bytes), a
+ *   wave per end e reads row e - 1 of the costs from column (j-1) * min_len to e - min_len in 16-byte loads and keeps its next
+ *   row's first loads in flight across the reduction; ends below j * min_len are INF without a read; the levels stop at
+ *   min(k, V / min_len).  No scratch, no atomics, bit-identical from run to run.  A video reads about min(k, V / min_len) * V^2 / 2
+ *   cost elements of 8 bytes through ONE workgroup: V and k near their limits TOGETHER are a serial chain of minutes.
+ *   A NULL pointer, n_x < 1, P or sum_V outside [1, 2^31), sum_V < P, k outside [1, 256], min_len outside [1, 4096], a penalty that
+ *   is negative, infinite or NaN: TAN_ERR_BAD_ARG, nothing launched, nothing written.  A table entry outside the limits, whose block
+ *   leaves [0, n_x) or whose slots leave [0, sum_V), gets the empty result (count = 0, start = -1, scatter = +inf) and its chapter
+ *   slots are NOT written; every other entry is computed, and nothing is read or written out of bounds.                            */
+int tan_chapter_max_rows(void);                    /* 4096 */
+int tan_chapter_costs(const float* x, long n_x, const long* x_off, const int* table, long P, long* cost, void* stream);
+long tan_chapter_decode_ws_bytes(long P, long sum_V, int k);
+int tan_chapter_decode(const long* cost, long n_x, const long* x_off, const int* table, long P, long sum_V, int k, int min_len,
+                       float penalty, int* count, int* start, float* scatter, int* chapter, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

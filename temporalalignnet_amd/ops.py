@@ -969,6 +969,101 @@ def storyboard_select(x, x_off, table, k, *, min_gain=0.0, sum_V=None, out=None)
     return second, coverage, owner
 
 
+CHAPTER_MAX_ROWS = 4096                                               # tan_chapter_max_rows(): the longest video of `chapter_costs` / `chapter_decode`
+CHAPTER_MAX_K = 256
+
+
+def _chapter_tables(what, x_off, table):
+    if x_off.dim() != 1 or x_off.dtype != torch.int64 or not x_off.is_contiguous() or x_off.numel() < 1:
+        raise ValueError(f"{what}: x_off is int64 [P], contiguous, P >= 1")
+    P = x_off.numel()
+    if table.dtype != torch.int32 or table.shape != (P, 2) or not table.is_contiguous():
+        raise ValueError(f"{what}: table is int32 [P, 2] = (V, first chapter slot), contiguous")
+    return P
+
+
+def chapter_costs(x, x_off, table, *, out=None):
+    """The cost of making seconds [s, e) of a video one chapter, for every s < e (tan_chapter_costs; the within-segment scatter in
+    64-bit fixed point, defined bit for bit in include/tan_hip.h): x f32 [n_x] holds row-major [V, V] blocks of a video's second x
+    second scores as `sequence_scores` writes them for the video's own rows; x_off int64 [P] and table int32 [P, 2] = (V, first
+    chapter slot) are `storyboard_select`'s tables, on the device; 1 <= V <= 4096.
+    Returns cost int64 [n_x] on the device: cost[x_off[p] + (e-1) * V + s] = J(s, e) for 0 <= s < e <= V; the other half of a block
+    is unspecified, and nothing outside the blocks is written.  A table entry that breaks the limits or whose block leaves x is
+    skipped.  out: a caller-owned cost instead of a fresh one.  ValueError: shapes, dtypes or sizes the entry point would refuse --
+    raised before anything touches the device."""
+    what = "chapter_costs"
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError(f"{what}: x is f32 [n_x], contiguous, n_x >= 1")
+    P = _chapter_tables(what, x_off, table)
+    if out is not None and (out.dtype != torch.int64 or out.shape != x.shape or not out.is_contiguous()):
+        raise ValueError(f"{what}: out is int64 [n_x], contiguous")
+    cost = torch.empty(x.numel(), dtype=torch.int64, device=x.device) if out is None else out
+    _lib.check(_lib.lib().tan_chapter_costs(_f32(x), x.numel(), _ptr(x_off), _ptr(table), P, _ptr(cost), _stream()), "tan_chapter_costs")
+    return cost
+
+
+def chapter_decode_ws_bytes(P, sum_V, k):
+    """the scratch `chapter_decode` needs: sum_V * k * 2 bytes (the arguments of every level as 16 bits)"""
+    return int(sum_V) * int(k) * 2
+
+
+def chapter_decode(cost, x_off, table, k, *, penalty, min_len=1, sum_V=None, out=None, ws=None):
+    """Each video cut into at most k contiguous chapters of at least min_len seconds (tan_chapter_decode; an exact dynamic programme
+    over `chapter_costs`' costs, defined bit for bit in include/tan_hip.h): the boundaries that minimise the summed scatter plus
+    `penalty` (finite, >= 0; absolute, in score x seconds) per boundary.  cost int64 [n_x], x_off, table as `chapter_costs` took
+    them; 1 <= k <= 256, 1 <= min_len <= 4096.
+    Returns (count int32 [P], start int32 [P, k], scatter f32 [P, k], chapter int32 [sum_V]) on the device, nothing read back: the
+    number of chapters, each chapter's first second (-1 from `count` on), the summed scatter of the best cut into j chapters at
+    [j - 1] (+inf where j chapters are not possible) and per second of the video its chapter.  A table entry that breaks the limits,
+    or whose block or slots leave cost / chapter, gives the empty result (0, -1, +inf) and its chapter slots are NOT written.
+    sum_V: the number of chapter slots, the sum of the table's V; without it the wrapper reads the table's last entry back (one
+    synchronisation).  out: caller-owned outputs (the same 4-tuple).  ws: caller-owned scratch, uint8 of at least
+    `chapter_decode_ws_bytes(P, sum_V, k)`.  ValueError: shapes, dtypes or sizes the entry point would refuse -- raised before
+    anything touches the device."""
+    what = "chapter_decode"
+    if cost.dim() != 1 or cost.dtype != torch.int64 or not cost.is_contiguous() or cost.numel() < 1:
+        raise ValueError(f"{what}: cost is int64 [n_x], contiguous, n_x >= 1")
+    P = _chapter_tables(what, x_off, table)
+    k, min_len, penalty = int(k), int(min_len), float(penalty)
+    if not 1 <= k <= CHAPTER_MAX_K:
+        raise ValueError(f"{what}: k must lie in [1, {CHAPTER_MAX_K}]")
+    if not 1 <= min_len <= CHAPTER_MAX_ROWS:
+        raise ValueError(f"{what}: min_len must lie in [1, {CHAPTER_MAX_ROWS}]")
+    if not (penalty >= 0 and math.isfinite(penalty)):
+        raise ValueError(f"{what}: penalty finite and >= 0")
+    if sum_V is not None and not P <= int(sum_V) < 2 ** 31:
+        raise ValueError(f"{what}: P <= sum_V < 2^31 (sum_V: the sum of the table's V)")
+
+    def out_ok(n):
+        count, start, scatter, chapter = out
+        return (count.dtype == start.dtype == chapter.dtype == torch.int32 and scatter.dtype == torch.float32 and count.shape == (P,)
+                and start.shape == (P, k) and scatter.shape == (P, k) and chapter.dim() == 1 and (n is None or chapter.numel() == n)
+                and all(t.is_contiguous() for t in out))
+    text = f"{what}: out is (count int32 [P], start int32 [P, k], scatter f32 [P, k], chapter int32 [sum_V]), contiguous"
+    if out is not None and (len(out) != 4 or not out_ok(None if sum_V is None else int(sum_V))):
+        raise ValueError(text)
+    if ws is not None and (ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_contiguous()
+                           or (sum_V is not None and ws.numel() < chapter_decode_ws_bytes(P, sum_V, k))):
+        raise ValueError(f"{what}: ws is uint8, contiguous, of at least chapter_decode_ws_bytes(P, sum_V, k) bytes")
+    if sum_V is None:
+        t = table[-1:].cpu().long()
+        sum_V = int(t[0, 0] + t[0, 1])
+        if not P <= sum_V < 2 ** 31 or (out is not None and not out_ok(sum_V)) \
+                or (ws is not None and ws.numel() < chapter_decode_ws_bytes(P, sum_V, k)):
+            raise ValueError(f"{what}: P <= sum_V < 2^31, and chapter and ws are sized for it (sum_V: the sum of the table's V)")
+    sum_V = int(sum_V)
+    dev = cost.device
+    if out is None:
+        out = (torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, k, dtype=torch.int32, device=dev),
+               torch.empty(P, k, dtype=torch.float32, device=dev), torch.empty(sum_V, dtype=torch.int32, device=dev))
+    count, start, scatter, chapter = out
+    if ws is None:
+        ws = torch.empty(max(chapter_decode_ws_bytes(P, sum_V, k), 1), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib().tan_chapter_decode(_ptr(cost), cost.numel(), _ptr(x_off), _ptr(table), P, sum_V, k, min_len, penalty, _ptr(count),
+                                             _ptr(start), _f32(scatter), _ptr(chapter), _ptr(ws), _stream()), "tan_chapter_decode")
+    return count, start, scatter, chapter
+
+
 def segment_pool_acc(stage, table, sum_, cnt, normalize=True):
     """sum_ [n_clips, 512] / cnt [n_clips] f32 += the (L2-normalised) frames table [W, 3] int32 = (clip, first_frame, n_frames)
     selects from stage [W, T, 512] (f32 / bf16; the window stride may exceed T * 512: a stage view of a [W, S, T, 512] stack)."""

@@ -7,7 +7,7 @@ sentence is ranked against all of it.  One module per concern -- `index`, `text`
 A search starts from a sentence (`search`, `search_moments`, `search_sequences`, `search_rerank`), from a vocabulary (`annotate`),
 from a piece of video (`search_clips`, `search_copies`, `align_paths`, `search_cover`) -- or from nothing: `discover_steps` clusters the index's
 seconds into the steps that recur in it, and its `StepClusters` serve as the vocabulary nobody had to write.  `storyboard` says what
-a video looks like: the k seconds that together cover it best.
+a video looks like: the k seconds that together cover it best; `chapters` says where its parts begin and end.
 
     python -m temporalalignnet_amd.search index --checkpoint C --feature-dir F --asr-json A --vlen-csv V --vocab s3d_dict.npy --out I.npz
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
@@ -30,14 +30,16 @@ a video looks like: the k seconds that together cover it best.
     python -m temporalalignnet_amd.search annotate --index J.npz --clusters clusters.npz [-k K] [--threshold X] ... --out segments.csv
     python -m temporalalignnet_amd.search storyboard --index I.npz [--shard I1.npz ...] [--host-resident] [-k 8] [--min-gain X]
         [--only VID ... | --only-file F] [--skip-long] --out story.csv [--npz story.npz]
+    python -m temporalalignnet_amd.search chapters --index I.npz [--shard I1.npz ...] [--host-resident] [-k 12] --penalty X [--min-len M]
+        [--only VID ... | --only-file F] [--skip-long] --out chapters.csv [--npz chapters.npz]
 """
 from .annotation import Annotation, annotate, label_lists, write_per_second_csv, write_segments_csv  # noqa: F401
 from .cli import main, parse_args, parse_within, restrict_from_args                                 # noqa: F401
 from .coarse import CoarseImage                                                                     # noqa: F401
 from .cluster import MAX_CLUSTERS, StepClusters, centroid_image, discover_steps                      # noqa: F401
 from .index import E4M3, RowFilter, ShardedIndex, VideoIndex, _index_chunks, build_index, plan_index_windows, restrict_spans  # noqa: F401
-from .summary import (MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, Storyboard, plan_passes, storyboard,  # noqa: F401
-                      write_storyboard_csv)
+from .summary import (MAX_CHAPTER_K, MAX_CHAPTER_SECONDS, MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, Chapters,  # noqa: F401
+                      Storyboard, chapters, plan_passes, storyboard, write_chapters_csv, write_storyboard_csv)
 from .text import (RERANK_TEXT_SLOTS, TEMPERATURE, Moment, Reranked, SequenceHit, _rerank_table,    # noqa: F401
                    _Sweep, _TopLists, query_features, rerank_window, search, search_moments, search_rerank, search_sequences)
 from .video import (EMPTY_ROW, MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, PIECE_ROWS, ClipHit, CopyHit,  # noqa: F401

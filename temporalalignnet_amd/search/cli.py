@@ -12,7 +12,8 @@ from .annotation import annotate, write_per_second_csv, write_segments_csv
 from .cluster import MAX_CLUSTERS, StepClusters, discover_steps
 from .coarse import CoarseImage
 from .index import E4M3, ShardedIndex, VideoIndex, build_index
-from .summary import MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, storyboard, write_storyboard_csv
+from .summary import (MAX_CHAPTER_K, MAX_CHAPTER_SECONDS, MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, chapters, storyboard,
+                      write_chapters_csv, write_storyboard_csv)
 from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
 from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, search_clips, search_copies, search_cover
 
@@ -129,6 +130,19 @@ def _parser():
                    help=f"leave out videos of more than {MAX_STORYBOARD_SECONDS} seconds instead of refusing them")
     p.add_argument("--out", required=True, metavar="CSV", help="vid,rank,second,coverage,share: one row per chosen second")
     p.add_argument("--npz", default=None, metavar="FILE", help="also save the storyboard (seconds, coverage, owners) as .npz")
+    p = sub.add_parser("chapters", help="cut each video into contiguous chapters (no checkpoint, no model)")
+    _index_options(p)
+    p.add_argument("-k", type=int, default=12, help=f"chapters per video at most, 1 to {MAX_CHAPTER_K} (default 12)")
+    p.add_argument("--penalty", type=float, required=True, metavar="X",
+                   help="keep a boundary only if it lowers the summed within-chapter scatter by at least this much (score x seconds; "
+                        "no default: its scale is the model's)")
+    p.add_argument("--min-len", type=int, default=None, metavar="M", help="seconds per chapter at least (default 1)")
+    p.add_argument("--only", action="append", default=None, metavar="VID", help="only this video (repeatable)")
+    p.add_argument("--only-file", default=None, metavar="PATH", help="only the videos listed here, one vid per line")
+    p.add_argument("--skip-long", action="store_true",
+                   help=f"leave out videos of more than {MAX_CHAPTER_SECONDS} seconds instead of refusing them")
+    p.add_argument("--out", required=True, metavar="CSV", help="vid,chapter,start,end,seconds: one row per chapter")
+    p.add_argument("--npz", default=None, metavar="FILE", help="also save the chapters (starts, scatter, per-second numbers) as .npz")
     p = sub.add_parser("merge", help="concatenate index files into one (no checkpoint, no GPU)")
     p.add_argument("--out", required=True, help="index file (.npz)")
     p.add_argument("inputs", nargs="+", help="index files, in the order their videos get")
@@ -252,6 +266,14 @@ def _check_storyboard(ap, a):
     _refuse(ap,
             (not 1 <= a.k <= MAX_STORYBOARD_K, f"-k must lie in [1, {MAX_STORYBOARD_K}]"),
             (a.min_gain is not None and not (a.min_gain >= 0 and np.isfinite(a.min_gain)), "--min-gain must be >= 0 and finite"),
+            (a.only is not None and a.only_file is not None, "--only does not go with --only-file"))
+
+
+def _check_chapters(ap, a):
+    _refuse(ap,
+            (not 1 <= a.k <= MAX_CHAPTER_K, f"-k must lie in [1, {MAX_CHAPTER_K}]"),
+            (not (a.penalty >= 0 and np.isfinite(a.penalty)), "--penalty must be >= 0 and finite"),
+            (a.min_len is not None and not 1 <= a.min_len <= MAX_CHAPTER_SECONDS, f"--min-len must lie in [1, {MAX_CHAPTER_SECONDS}]"),
             (a.only is not None and a.only_file is not None, "--only does not go with --only-file"))
 
 
@@ -455,10 +477,27 @@ def _run_query(a):
     return 0
 
 
+def _run_chapters(a):
+    idx = _load_index(a)
+    only = a.only if a.only is not None else _read_vids(a.only_file) if a.only_file is not None else None
+    try:
+        chaps = chapters(idx, a.k, penalty=a.penalty, min_len=a.min_len or 1, videos=only, skip_long=a.skip_long)
+    except (ValueError, KeyError) as e:
+        print(f"chapters: {e.args[0] if isinstance(e, KeyError) else e}", file=sys.stderr)
+        return 2
+    with open(a.out, "w", newline="") as f:
+        write_chapters_csv(f, chaps)
+    if a.npz is not None:
+        chaps.save(a.npz)
+    print(f"{a.out}: {int(chaps.count.sum())} chapters of {len(chaps)} videos" +
+          (f", {len(chaps.skipped)} over-long videos left out" if chaps.skipped else ""), file=sys.stderr)
+    return 0
+
+
 _CHECKS = dict(index=_check_index, query=_check_query, annotate=_check_annotate, similar=_check_similar, discover=_check_discover,
-               merge=lambda ap, a: None, coarse=lambda ap, a: None, storyboard=_check_storyboard)
+               merge=lambda ap, a: None, coarse=lambda ap, a: None, storyboard=_check_storyboard, chapters=_check_chapters)
 _RUNS = dict(index=_run_index, query=_run_query, annotate=_run_annotate, similar=_run_similar, discover=_run_discover, merge=_run_merge,
-             coarse=_run_coarse, storyboard=_run_storyboard)
+             coarse=_run_coarse, storyboard=_run_storyboard, chapters=_run_chapters)
 
 
 def main(argv=None):

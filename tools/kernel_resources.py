@@ -3,10 +3,11 @@
 A kernel whose VGPR + AGPR total exceeds 256 runs ONE wave per SIMD -- that is how the attention backward lost half its occupancy
 unnoticed.  usage: python tools/kernel_resources.py [substring-filter | NAME]
 NAME: a filter kept by name -- `storyboard`: storyboard_select_kernel (csrc/tan_storyboard.hip), whose table is in DESIGN.md 3.26 and
-which must show no SCRATCH."""
+which must show no SCRATCH; `chapters`: the four kernels of csrc/tan_chapter.hip (chapter_rows / _upper / _costs / _decode_kernel), whose
+table is in DESIGN.md 3.27 and which must show no SCRATCH either."""
 import glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-FILTERS = {"storyboard": "storyboard_select_kernel"}
+FILTERS = {"storyboard": "storyboard_select_kernel", "chapters": "tal::chapter_"}
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 flt = FILTERS.get(flt, flt)
 for src in sorted(glob.glob(os.path.join(ROOT, "temporalalignnet_amd", "csrc", "*.hip"))):

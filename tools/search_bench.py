@@ -75,6 +75,14 @@ e4m3; use --rows 1048576): `scores_ms`, `ops.sequence_scores` with the index's o
 `torch.maximum(fix(X), C).sum(1).argmax()` in int64, the two alternating call by call (`equals_torch`: the same seconds, and
 the coverage bits that the header's formula makes of the composition's exact int64 sums), `self_pair_spread`, the kernel against itself, and `longest_alone_ms`, the launch over the longest video alone: one workgroup's
 serial chain, the tail the launch cannot end before.
+--chapters times chapters INSTEAD (`search.chapters`' launches after the scores, over ALL videos of --cover's corpus in one pass, k = 12,
+min_len = 5, bf16 and e4m3; use --rows 1048576): `costs_ms` (`ops.chapter_costs`) beside `torch_costs_ms`, and `decode_ms`
+(`ops.chapter_decode`) beside `torch_decode_ms` -- what a caller writes without the kernels on the same card from the same blocks: per
+video fix(X) in int64, two cumsums, the four-corner difference and `torch.div(..., rounding_mode="floor")`, then per level
+`(dp[None, :] + J).min(1)` --, each pair alternating call by call (`same_costs`: the defined triangle bit for bit; `same_scatter`:
+every level's dp_j[V] as the header's f32), `*_spread`, each kernel against itself, `costs_GBs` over the 8 bytes per score element the
+costs must move (`costs_of_stream`: of STREAM_TBS), `decode_GBs` over the cost elements the levels read, and `longest_*_ms`, the longest
+video alone.
 --annotate times corpus annotation INSTEAD (`ops.label_topk` / `ops.label_topk_e4m3`, then `ops.label_runs` over its lists), bf16 and
 e4m3, for L in --labels and k in --annotate-k (default 1, 5; use --rows 1048576): `label_topk_ms` beside `swapped_rank_ms`, what a caller has without the
 entry point -- `ops.rank_topk` with the rows as queries and the labels as the index, over chunks of rows small enough for its scratch
@@ -695,6 +703,106 @@ def storyboard_table(N, v16, v8, s8, a):
     return rows
 
 
+CHAPTER_K, CHAPTER_MIN_LEN, CHAPTER_PENALTY = 12, 5, 0.05
+
+
+def torch_chapter_costs(x, x_off, lens, cost):
+    """What a caller writes without tan_chapter_costs, from the same blocks: per video fix(X) in int64, two cumsums, the four-corner
+    difference and torch.div(..., rounding_mode="floor"); J(s, e) lands at [e - 1][s] of the video's block of `cost` (the other half
+    holds whatever the triangle-blind expression gives); no host round trip"""
+    for o, V in zip(x_off, lens):
+        F = torch.round(x[o:o + V * V].view(V, V) * 2.0 ** 30).to(torch.int64)
+        S = torch.zeros(V + 1, V + 1, dtype=torch.int64, device=x.device)
+        S[1:, 1:] = F.cumsum(0).cumsum(1)
+        d = torch.zeros(V + 1, dtype=torch.int64, device=x.device)
+        d[1:] = F.diagonal().cumsum(0)
+        diag = S.diagonal()
+        ends = torch.arange(V + 1, device=x.device)
+        n = (ends[:, None] - ends[None, :]).clamp(min=1)               # at [e, s]: e - s
+        Q = diag[:, None] - S - S.T + diag[None, :]                    # at [e, s]: S[e,e] - S[e,s] - S[s,e] + S[s,s]
+        J = (d[:, None] - d[None, :]) - torch.div(Q, n, rounding_mode="floor")
+        cost[o:o + V * V].view(V, V).copy_(J[1:, :V])
+
+
+def torch_chapter_decode(cost, x_off, lens, k, min_len, final):
+    """... and without tan_chapter_decode: per video and level `(dp[None, :] + J).min(1)` over the allowed starts, in int64; final
+    int64 [P, k]: dp_j[V] per level (2^62 where infeasible), from which count and scatter follow; no argument, no backtrack (the
+    kernel does both), no host round trip inside a video"""
+    INF = 2 ** 62
+    for p, (o, V) in enumerate(zip(x_off, lens)):
+        J = cost[o:o + V * V].view(V, V)                               # [e - 1, s]
+        ends = torch.arange(1, V + 1, device=cost.device)
+        starts = torch.arange(V, device=cost.device)
+        allowed = (starts[None, :] >= 1) & (starts[None, :] <= ends[:, None] - min_len)
+        dp = torch.full((V + 1,), INF, dtype=torch.int64, device=cost.device)
+        dp[1:] = torch.where((ends >= min_len) | (ends == V), J[:, 0], dp[1:])
+        final[p, 0] = dp[V]
+        for j in range(1, k):
+            cand = torch.where(allowed & (dp[None, :V] < INF), dp[None, :V] + J, torch.full_like(J, INF))
+            dp = torch.cat((dp[:1], cand.min(1).values))
+            final[p, j] = dp[V]
+
+
+def chapters_table(N, v16, v8, s8, a):
+    """One row per format: the launches of `search.chapters` over all videos of `cover_table`'s corpus in ONE pass (see the module
+    docstring)"""
+    from temporalalignnet_amd.search import align_tables, piece_offsets
+    v_off = video_layouts(N)["corpus"]
+    lens = np.diff(v_off.cpu().numpy().astype(np.int64))
+    nv, k, min_len = len(lens), CHAPTER_K, CHAPTER_MIN_LEN
+    s_off, first = piece_offsets(lens)
+    hits, hit_off, x_off, table, n_x, sum_V = align_tables(lens, lens, first[:-1], np.arange(nv))
+    dev = lambda arr, dt: torch.from_numpy(np.ascontiguousarray(arr, dtype=dt)).cuda()        # noqa: E731
+    s_off_d, hits_d, hit_off_d, x_off_d, table_d = dev(s_off, np.int32), dev(hits, np.int32), dev(hit_off, np.int64), dev(x_off, np.int64), \
+        dev(table[:, 1:], np.int32)
+    big = int(np.argmax(lens))
+    one_off, one_table = dev([x_off[big]], np.int64), dev([[lens[big], 0]], np.int32)
+    x = torch.empty(n_x, device="cuda")
+    cost, t_cost = torch.empty(n_x, dtype=torch.int64, device="cuda"), torch.empty(n_x, dtype=torch.int64, device="cuda")
+    new = lambda n, sv: (torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, k, dtype=torch.int32, device="cuda"),   # noqa: E731
+                         torch.empty(n, k, device="cuda"), torch.empty(sv, dtype=torch.int32, device="cuda"))
+    out, out_one = new(nv, sum_V), new(1, int(lens[big]))
+    ws = torch.empty(ops.chapter_decode_ws_bytes(nv, sum_V, k), dtype=torch.uint8, device="cuda")
+    t_final = torch.empty(nv, k, dtype=torch.int64, device="cuda")
+    levels = np.minimum(k, np.maximum(1, lens // min_len))
+    read_bytes = float(((levels - 1) * lens * lens // 2).sum()) * 8
+    lower = torch.zeros(n_x, dtype=torch.bool, device="cuda")
+    for o, V in zip(x_off, lens):
+        lower[o:o + V * V].view(V, V).copy_(torch.ones(V, V, dtype=torch.bool, device="cuda").tril())
+    rows = []
+    for fmt in ("bf16", "e4m3"):
+        feat, kw = (v16, {}) if fmt == "bf16" else (v8, dict(q_scale=s8, v_scale=s8))
+        ops.sequence_scores(feat, feat, s_off_d, v_off, hits_d, hit_off_d, x, **kw)
+        costs = lambda: ops.chapter_costs(x, x_off_d, table_d, out=cost)                                          # noqa: E731
+        t_costs = lambda: torch_chapter_costs(x, x_off, lens, t_cost)                                             # noqa: E731
+        decode = lambda: ops.chapter_decode(cost, x_off_d, table_d, k, penalty=CHAPTER_PENALTY, min_len=min_len, sum_V=sum_V, out=out, ws=ws)   # noqa: E731
+        t_decode = lambda: torch_chapter_decode(cost, x_off, lens, k, min_len, t_final)                           # noqa: E731
+        one_costs = lambda: ops.chapter_costs(x, one_off, one_table, out=cost)                                    # noqa: E731
+        one_decode = lambda: ops.chapter_decode(cost, one_off, one_table, k, penalty=CHAPTER_PENALTY, min_len=min_len,   # noqa: E731
+                                                sum_V=int(lens[big]), out=out_one, ws=ws)
+        c_new, c_torch = timed_pair(costs, t_costs, a.warmup, a.reps)
+        c_a, c_b = timed_pair(costs, costs, a.warmup, a.reps)
+        d_new, d_torch = timed_pair(decode, t_decode, a.warmup, a.reps)
+        d_a, d_b = timed_pair(decode, decode, a.warmup, a.reps)
+        same_costs = bool(torch.equal(cost[lower], t_cost[lower]))
+        want = t_final.cpu().numpy()
+        want_scatter = np.where(want < 2 ** 62, want.astype(np.float32) * np.float32(2.0 ** -30), np.float32(np.inf)).astype(np.float32)
+        same_scatter = bool(np.array_equal(out[2].cpu().numpy().view(np.int32), want_scatter.view(np.int32)))
+        t_one_c, _ = timed(one_costs, a.warmup, a.reps)
+        t_one_d, _ = timed(one_decode, a.warmup, a.reps)
+        sum_v2 = float((lens * lens).sum())
+        c_gbs, d_gbs = sum_v2 * (4 + 4) / c_new / 1e6, read_bytes / d_new / 1e6                                   # costs: x in, half of cost out
+        rows.append({"fmt": fmt, "videos": nv, "sum_V2": int(sum_v2), "costs_ms": round(c_new, 4), "torch_costs_ms": round(c_torch, 4),
+                     "costs_over_torch": round(c_new / c_torch, 5), "costs_spread": round(abs(c_a / c_b - 1), 4), "same_costs": same_costs,
+                     "costs_GBs": round(c_gbs, 1), "costs_of_stream": round(c_gbs / (STREAM_TBS * 1e3), 4),
+                     "decode_ms": round(d_new, 4), "torch_decode_ms": round(d_torch, 4), "decode_over_torch": round(d_new / d_torch, 5),
+                     "decode_spread": round(abs(d_a / d_b - 1), 4), "same_scatter": same_scatter, "decode_GBs": round(d_gbs, 1),
+                     "chapters": int(out[0].sum()), "longest_V": int(lens[big]), "longest_costs_ms": round(t_one_c, 4),
+                     "longest_decode_ms": round(t_one_d, 4)})
+        print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    return rows
+
+
 def rerank_table(N, v16, stem, a):
     import time
 
@@ -806,6 +914,8 @@ def main():
     ap.add_argument("--labels", type=int, nargs="+", default=[128, 1024, 8192], help="with --annotate: vocabulary sizes")
     ap.add_argument("--annotate-k", type=int, nargs="+", default=list(ANNOTATE_KS), help="with --annotate: labels kept per row")
     ap.add_argument("--storyboard", action="store_true", help="time storyboard_select and its score blocks instead (use --rows 1048576)")
+    ap.add_argument("--chapters", action="store_true", help="time chapter_costs and chapter_decode against their torch compositions instead "
+                                                            "(use --rows 1048576)")
     ap.add_argument("--cover", action="store_true", help="time cover_topk against label_topk(k = 1) at L = m instead (use --rows 1048576)")
     ap.add_argument("--cover-rows", type=int, nargs="+", default=[128, 1024, 4096], help="with --cover: rows of the one set")
     a = ap.parse_args()
@@ -858,6 +968,25 @@ def main():
                 fh.write(" ".join(f"{c:>17}" for c in cols) + "\n")
                 for r in rows:
                     fh.write(" ".join(f"{str(r[c]):>17}" for c in cols) + "\n")
+        print(json.dumps(res))
+        return
+    if a.chapters:
+        rows = chapters_table(N, v16, v8, s8, a)
+        res = {"rows": N, "reps": a.reps, "warmup": a.warmup, "gpu": torch.cuda.get_device_name(0), "chapters": rows}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(f"# tools/search_bench.py --chapters --rows {N}: median of {a.reps} after {a.warmup} warm-ups, device events, caller-owned "
+                         f"outputs, {res['gpu']}\n")
+                fh.write(f"# all videos (60 to 1 200 rows) in one pass, k = {CHAPTER_K}, min_len = {CHAPTER_MIN_LEN}, penalty = {CHAPTER_PENALTY}; costs = "
+                         "ops.chapter_costs over tan_sequence_scores' blocks, decode = ops.chapter_decode over its costs; torch_* = what a caller "
+                         "writes without them from the same blocks (per video: fix(X) in int64, two cumsums, the four-corner difference, "
+                         "torch.div floor; per level (dp[None, :] + J).min(1)), alternating call by call with the kernel; *_spread = |ratio - 1| "
+                         "of the kernel alternating with itself; costs_GBs = sum_V2 * 8 bytes (x in, half of cost out) / costs time, of_stream: "
+                         f"of {STREAM_TBS} TB/s; decode_GBs = sum (levels - 1) V^2 / 2 * 8 bytes / decode time; longest_* = the longest video alone\n")
+                for r in rows:
+                    for c in r:
+                        fh.write(f"{r['fmt']:>5} {c:>20} {r[c]}\n")
         print(json.dumps(res))
         return
     if a.cover:

@@ -31,7 +31,7 @@ extern "C" {
 #define TAN_ACT_QUICKGELU_GRAD 2 /* C = acc * d/dx quickgelu(x), x read from aux */
 #define TAN_ACT_RELU 3           /* C = max(acc+bias, 0)  (Word2VecModel fc1, model/word2vec_model.py:86) */
 
-int tan_version(void);          /* 109: tan_chapter_costs / _decode; 108: tan_storyboard_select; 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
+int tan_version(void);          /* 110: tan_compound_topk / _peaks; 109: tan_chapter_costs / _decode; 108: tan_storyboard_select; 107: tan_cover_topk / _e4m3; 106: tan_quantize_rows_mxfp4 / tan_rank_topk_mxfp4; 105: tan_cluster_accumulate / _centroids; 104: tan_local_align_path; 103: tan_local_align; 102: tan_label_decode; 101: tan_clip_topk / _e4m3 (100: everything before them) */
 /* sizeof(tan_gemm_desc | tan_layer_params | tan_layer_bufs | tan_encoder_desc | tan_simfam_desc | tan_simnce_desc) for which = 0..5 (binding self-check) */
 int tan_abi_sizeof(int which);
 
@@ -966,6 +966,52 @@ int tan_clip_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, in
 int tan_clip_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
                        const int* c_off, long n_clip, const int* v_off, long n_videos, int k, int splits, float* top_score,
                        int* top_row, int* top_video, void* ws, void* stream);
+/* ---- compound search: the k videos that satisfy AND / OR / NOT of query rows, in any order ----
+ * A COMPOUND QUERY is 1 to 32 consecutive rows of Tq [Qt, C], its TERMS: t_off [n_query + 1] int32 on the device, t_off[0] == 0,
+ * t_off[n_query] == Qt, strictly increasing, every difference in [1, 32] -- the contract of s_off.  role [Qt] int32 on the device gives
+ * every term its part: j in [0, 31] = the term belongs to CLAUSE j, -1 = the term is BANNED; every query has at least one clause
+ * term.  One float `veto` holds for the whole call.  A VIDEO v is the index rows [v_off[v], v_off[v + 1]) -- the v_off contract of
+ * tan_rank_topk_video.  For a video v with at least one row and a term t, let x[t, n] = score(q_t, n), the row sweep's score: the
+ * MFMA chain of tan_rank_topk in the same K order (e4m3: (acc * v_scale[n]) * q_scale[t]).  Inputs are finite.  Then
+ *     peak    p_t = x[t, r_t], r_t = the first row n of v, ascending, that no other row of v beats under float > -- the value AT that
+ *                   row, not a max() that might pick the other zero of +-0
+ *     clause  g_j = p_t of the first term t of clause j, in term order, that no other term of the clause beats under >         (OR)
+ *     score       = the occupied clauses folded in ascending j, starting from the first one; the running value is replaced only
+ *                   under strict <                                                                (AND: the weakest link)
+ *     veto        : a video with p_t >= veto for any banned term t is not a candidate; without banned terms pass +inf    (NOT)
+ * A video without rows is never a candidate.  Maxima and minima are exact, so given the bits of x nothing depends on tiling,
+ * splits or shards.
+ * tan_compound_topk (Tq, Vn, dtype, C == 512, alignment as tan_rank_topk):
+ *   top_score (f32) / top_video (int32) [n_query, k], 1 <= k <= min(32, n_videos): per query the k candidates with the largest
+ *     score, by descending score, equal scores by ascending video.  With fewer than k candidates the tail is (-inf, 0x7fffffff):
+ *     the empty slots of tan_clip_topk, which tan_topk_fold sorts last.
+ *   splits: as tan_sequence_topk: a split takes WHOLE videos (those whose first row falls into its row range), 0 = chosen from
+ *     n_query and N, at most 256.  Results are bit-identical from run to run and for every `splits`; no float atomics.  Nothing of
+ *     size Qt x N, n_query x N or n_query x n_videos is stored.
+ *   ws: tan_compound_topk_ws_bytes(n_query, N, k) bytes of scratch, 16-byte aligned: the splits' lists (at most 256 * n_query * k * 8
+ *     bytes); it does not depend on `splits`; -1 for invalid sizes.
+ * tan_compound_peaks: for n_hits hits, hits [n_hits, 2] int32 = (query, video) on the device, peak_score f32 / peak_row int32
+ * [n_hits, 32] <- (p_t, r_t) of the query's term t in column t, r_t a GLOBAL index row, with the bits tan_compound_topk used (the
+ * same routine); columns >= the query's number of terms, and every column of a hit whose query or video lies outside the tables or
+ * whose video has no row, hold (-inf, 0x7fffffff): every element is written.  One workgroup per hit, no atomics, no scratch.
+ * Another width, k outside [1, min(32, n_videos)], a NaN veto, an unknown dtype, a NULL pointer, misalignment, negative splits,
+ * n_query < 1, Qt outside [n_query, 32 * n_query], n_videos outside [1, N], N outside [1, 2^31), n_hits outside [1, 2^26):
+ * TAN_ERR_BAD_ARG, nothing launched.  A t_off, role or v_off that breaks its contract is the CALLER's error: every lookup is clamped
+ * (a query of more than 32 terms is cut to 32, a role below -1 counts as banned, a query without a clause term has no candidate),
+ * nothing is read or written out of bounds, and the lists are unspecified.  The Python wrapper checks on request.
+ * The _e4m3 variants take the codes and scales of tan_rank_topk_e4m3.                                                              */
+long tan_compound_topk_ws_bytes(long n_query, long N, int k);
+int tan_compound_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* t_off, const int* role,
+                      long n_query, const int* v_off, long n_videos, float veto, int k, int splits, float* top_score, int* top_video,
+                      void* ws, void* stream);
+int tan_compound_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                           const int* t_off, const int* role, long n_query, const int* v_off, long n_videos, float veto, int k,
+                           int splits, float* top_score, int* top_video, void* ws, void* stream);
+int tan_compound_peaks(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* t_off, long n_query,
+                       const int* v_off, long n_videos, const int* hits, long n_hits, float* peak_score, int* peak_row, void* stream);
+int tan_compound_peaks_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                            const int* t_off, long n_query, const int* v_off, long n_videos, const int* hits, long n_hits,
+                            float* peak_score, int* peak_row, void* stream);
 /* ---- cover search: the k videos that share the most seconds with a set of query rows, in any order and at any pace ----
  * A SET is 1 to 4096 (tan_cover_max_rows()) consecutive rows of Tq [Qt, C]: q_off [n_set + 1] int32 on the device, q_off[0] == 0,
  * q_off[n_set] == Qt, strictly increasing, every difference in [1, 4096].  A VIDEO v is the index rows [v_off[v], v_off[v + 1]) -- the

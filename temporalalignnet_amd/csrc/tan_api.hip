@@ -53,7 +53,7 @@ void prof_end(hipStream_t st, int rec) {
 
 using namespace tal;
 
-extern "C" int tan_version(void) { return 109; }
+extern "C" int tan_version(void) { return 110; }
 
 // sizeof of the ABI structs, so that a binding (ctypes, cgo, JNI ...) can assert its mirror has the same layout
 extern "C" int tan_abi_sizeof(int which) {

@@ -28,6 +28,9 @@
 // tan_clip_topk ranks videos by the best SECOND-FOR-SECOND match of a run of up to 32 query rows -- a diagonal sum over the same
 // matrix-free score tile (clip_kernel: seq_kernel's frame with two add chains per lane instead of the scan) -- and returns each
 // video's best start; rank_merge_video_kernel folds its splits.
+// tan_compound_topk ranks videos by AND / OR / NOT of up to 32 query rows in any order (compound_kernel: the same frame, each term's
+// peak over the video in registers, clauses by readlane, the weakest clause by a wave min, the veto by one __any; no LDS beyond the
+// tiles), and tan_compound_peaks writes the winners' per-term (peak, row) with the sweep's bits.
 // tan_rank_topk_filtered / tan_rank_topk_video_filtered sweep only the rows a FILTER admits (rank_kernel's FILTER mode): the image
 // tan_row_filter_build makes from row spans lists the 64-row tiles that hold an admitted row, with a row mask each; a split walks a
 // range of that list and masks the other rows, so the lists are the plain sweep's over the gathered admitted rows, bit for bit.
@@ -958,6 +961,197 @@ __global__ void __launch_bounds__(256) clip_kernel(const T* __restrict__ Tq, con
     }
 }
 
+// ---- compound search: videos ranked by AND / OR / NOT of up to 32 query rows, in any order (include/tan_hip.h) ----
+// seq_kernel<T, false>'s frame with a third epilogue, the lightest: a wave owns ONE compound query (its up to 32 terms are the wave's
+// resident query columns, padded columns are computed and ignored), a workgroup four queries, a split the videos whose first row
+// falls into its row range, every video is tiled from its own first row by tile_scores.  A lane's 32 accumulators belong to one term,
+// so per tile the lane takes (max, first row) over its rows BELOW the video's end by better() -- a tail row loads as zero and is no
+// candidate: it would beat every row of a video whose scores are all negative -- one __shfl_xor joins the two half-waves, and the
+// result feeds the lane's running peak (pk, pr) of the video under strict better(): tiles arrive in ascending row order, so the first
+// row that attains the maximum survives, with the bits it has at that row.  At the video's end the veto is one __any over the banned
+// columns, a clause's value comes from a readlane loop over the m terms (the first term of the lane's own clause that none beats
+// under >), and the score is a 32-lane min over (value, clause) -- the smaller value, equal values by the smaller clause: the fold in
+// ascending clause order that replaces only under strict <.  No LDS beyond the tile buffers, no scan.  A finished video gives ONE
+// candidate (score, video); the 64 candidates of a query live one per lane in registers, sort64 keeps the k best when they are full
+// and raises the threshold.  rank_merge_kernel folds the splits' lists (row = video: the order is total).
+// PEAKS = true: tan_compound_peaks -- one workgroup per hit (query, video), all four waves hold the hit's query, and at the video's end
+// wave 0 writes the 32 columns' (peak, row), (-inf, 0x7fffffff) for columns >= m.  Same routine, same bits.
+// bf16 / e4m3: held to seq_kernel's two waves per SIMD (256 registers a lane); f32's 256 resident fragment registers allow one.
+template <typename T, bool PEAKS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 1 : 2)))
+compound_kernel(const T* __restrict__ Tq, const T* __restrict__ Vn, long Qt, long N,
+                                                       const int* __restrict__ t_off, const int* __restrict__ role, int n_query,
+                                                       const int* __restrict__ v_off, int n_videos, float veto, int k,
+                                                       long rows_per_split, const float* __restrict__ q_scale,
+                                                       const float* __restrict__ v_scale, float* __restrict__ part_s,
+                                                       int* __restrict__ part_n, const int* __restrict__ hits,
+                                                       float* __restrict__ peak_s, int* __restrict__ peak_n) {
+    typedef Mma<T> M;
+    typedef typename M::frag_t frag_t;
+    constexpr int KC = RCfg<T>::KC, LD = RCfg<T>::LD, NCH = RC / KC, NFR = RC / M::KS;
+    constexpr long ROWB = (long)RC * sizeof(T);
+    constexpr bool F8 = sizeof(T) == 1;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* tile = reinterpret_cast<T*>(smem);
+    float* sc = reinterpret_cast<float*>(smem + 2 * BN * LD * sizeof(T));
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31;
+
+    // the wave's query and the workgroup's videos [va, vb); every lookup is clamped
+    int p, va, vb;
+    bool vok = true;
+    if constexpr (PEAKS) {
+        const int h = blockIdx.x;
+        p = hits[2 * h];
+        va = hits[2 * h + 1];
+        vok = va >= 0 && va < n_videos;
+        va = va < 0 ? 0 : (va >= n_videos ? n_videos - 1 : va);
+        vb = va + 1;
+    } else {
+        p = blockIdx.x * 4 + wave;
+        const long r0 = (long)blockIdx.y * rows_per_split, r1 = r0 + rows_per_split;
+        va = r0 <= 0 ? 0 : videos_below(v_off, r0, n_videos);
+        vb = r1 >= N ? n_videos : videos_below(v_off, r1, n_videos);
+    }
+    const bool pok = p >= 0 && p < n_query;
+    p = p < 0 ? 0 : (p >= n_query ? n_query - 1 : p);
+    long q0 = t_off[p];
+    q0 = q0 < 0 ? 0 : (q0 >= Qt ? Qt - 1 : q0);
+    long m_l = (long)t_off[p + 1] - q0;
+    m_l = m_l > Qt - q0 ? Qt - q0 : m_l;
+    const int m = m_l < 1 ? 1 : (m_l > 32 ? 32 : (int)m_l);        // wave-uniform
+
+    if constexpr (PEAKS) {
+        if (!pok || !vok) {                                        // block-uniform: a hit outside the tables gets the filler alone
+            if (tid < 32) { peak_s[(long)blockIdx.x * 32 + tid] = -INFINITY; peak_n[(long)blockIdx.x * 32 + tid] = SENT_ROW; }
+            return;
+        }
+    }
+
+    frag_t qf[NFR];                                                // the query's terms, resident; columns >= m repeat the last term
+    const long qme = q0 + (col < m ? col : m - 1);
+    {
+        const T* qrow = Tq + qme * RC;
+#pragma unroll
+        for (int j = 0; j < NFR; ++j) qf[j] = QFrag<T>::load(qrow, j, lane);
+    }
+    float qs = 1.0f, psc = 0.0f;
+    if constexpr (F8) qs = q_scale[qme];
+    int rl = -1;                                                   // the column's clause; -1: banned
+    if constexpr (!PEAKS) rl = role[qme];
+    const bool term = col < m;
+
+    // the tile under the MFMAs: video v, its rows [lo, hi) cut to the index, tile t of it
+    struct Cur { int v; long lo, hi, t; };
+    auto open = [&](int v) {
+        Cur c{v, 0, 0, 0};
+        if (v < vb) {
+            c.lo = v_off[v];
+            c.hi = v_off[v + 1];
+            c.lo = c.lo < 0 ? 0 : (c.lo > N ? N : c.lo);
+            c.hi = c.hi < c.lo ? c.lo : (c.hi > N ? N : c.hi);
+        }
+        return c;
+    };
+    uint4 pre[4];
+    auto issue = [&](const Cur& c, int kc) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = tid + 256 * i, row = v >> 4, c16 = v & 15;
+            const long n = c.lo + c.t * BN + row;
+            pre[i] = n < c.hi ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Vn) + n * ROWB + kc * 256 + c16 * 16)
+                              : make_uint4(0, 0, 0, 0);
+        }
+        if constexpr (F8) {
+            if (kc == NCH - 1 && tid < BN) {
+                const long n = c.lo + c.t * BN + tid;
+                psc = n < c.hi ? v_scale[n] : 0.0f;
+            }
+        }
+    };
+
+    float cs = -INFINITY, thr = -INFINITY;                         // the candidate registers: (score, video), one per lane
+    int cn = SENT_ROW, fill = 0;                                   // fill, thr: wave-uniform
+    float pk = -INFINITY;                                          // the video under way: the column's peak and its first row
+    int pr = SENT_ROW;
+
+    Cur cur = open(va);
+    if (cur.v < vb) issue(cur, 0);
+    while (cur.v < vb) {                                           // block-uniform
+        Cur nxt = cur;
+        if ((cur.t + 1) * BN < cur.hi - cur.lo) ++nxt.t; else nxt = open(cur.v + 1);
+        f32x16 acc[2];
+        tile_scores<T>(tile, sc, tid, lane, pre, psc, qf, qs, acc, [&](int kc) {
+            if (kc + 1 < NCH) issue(cur, kc + 1);
+            else if (nxt.v < vb) issue(nxt, 0);
+        });
+        const long V = cur.hi - cur.lo, left = V - cur.t * BN;     // the tile's rows [0, left) are the video's
+        const int nl = left < BN ? (int)left : BN;
+        float ms = -INFINITY;
+        int mn = SENT_ROW;                                         // a tile row here; the global row below
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int j = rt * 32 + acc_row(r, lane);
+                if (j < nl && better(acc[rt][r], j, ms, mn)) { ms = acc[rt][r]; mn = j; }
+            }
+        {
+            const float os = __shfl_xor(ms, 32, 64);
+            const int on = __shfl_xor(mn, 32, 64);
+            if (better(os, on, ms, mn)) { ms = os; mn = on; }
+        }
+        if (mn != SENT_ROW) {
+            const int n = (int)(cur.lo + cur.t * BN + mn);
+            if (better(ms, n, pk, pr)) { pk = ms; pr = n; }
+        }
+        if (nxt.v != cur.v) {                                      // the video is finished
+            if constexpr (PEAKS) {
+                if (wave == 0 && lane < 32) {
+                    peak_s[(long)blockIdx.x * 32 + lane] = term ? pk : -INFINITY;
+                    peak_n[(long)blockIdx.x * 32 + lane] = term ? pr : SENT_ROW;
+                }
+            } else {
+                const bool vetoed = __any(term && rl < 0 && pk >= veto);
+                float g = -INFINITY;                               // the value of the lane's own clause (OR)
+                for (int i = 0; i < m; ++i) {
+                    const float pi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pk), i));
+                    const int ri = __builtin_amdgcn_readlane(rl, i);
+                    if (ri == rl && pi > g) g = pi;
+                }
+                const bool clause = term && rl >= 0;
+                float ws = clause ? g : INFINITY;                  // the weakest clause (AND); both half-waves hold the same columns
+                int wj = clause ? rl : SENT_ROW;
+#pragma unroll
+                for (int o = 16; o > 0; o >>= 1) {
+                    const float os = __shfl_xor(ws, o, 64);
+                    const int oj = __shfl_xor(wj, o, 64);
+                    if (os < ws || (os == ws && oj < wj)) { ws = os; wj = oj; }
+                }
+                if (V > 0 && !vetoed && wj != SENT_ROW && ws >= thr) {     // wave-uniform; one candidate
+                    if (lane == fill) { cs = ws; cn = cur.v; }
+                    if (++fill == CAP) {
+                        sort64(cs, cn, lane);
+                        thr = __shfl(cs, k - 1, 64);
+                        if (lane >= k) { cs = -INFINITY; cn = SENT_ROW; }
+                        fill = k;
+                    }
+                }
+            }
+            pk = -INFINITY;
+            pr = SENT_ROW;
+        }
+        cur = nxt;
+    }
+    if constexpr (!PEAKS) {
+        sort64(cs, cn, lane);
+        if (pok && lane < k) {
+            const long o = ((long)blockIdx.y * n_query + p) * k + lane;
+            part_s[o] = cs;
+            part_n[o] = cn;
+        }
+    }
+}
+
 // ---- one wave per frame row: 64 lanes x 8 channels
 template <typename T> __device__ __forceinline__ f8 ld_row8(const T* p) {
     if constexpr (sizeof(T) == 2) return ld8(p); else return ld8f(p);
@@ -1312,6 +1506,37 @@ int clip_topk_launch(const void* Tq, const void* Vn, long Qt, long N, const int*
     TAN_LAUNCH_CHECK();
     hipLaunchKernelGGL(rank_merge_video_kernel, dim3(cdiv(n_clip, 4)), dim3(256), 0, st, part_s, part_n, (const int*)part_v, n_clip, k, ns,
                        top_s, top_n, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ws: the splits' lists (score, video); the splits are the sequence sweep's.  The tile buffers are the whole LDS: below the 64 KiB that
+// need no attribute.
+template <typename T>
+int compound_topk_launch(const void* Tq, const void* Vn, long Qt, long N, const int* t_off, const int* role, long n_query,
+                         const int* v_off, int n_videos, float veto, int k, int splits, float* top_s, int* top_v, void* ws,
+                         hipStream_t st, const float* q_scale = nullptr, const float* v_scale = nullptr) {
+    static_assert(tile_bytes<T>() <= 48 * 1024, "compound_kernel's LDS needs the dynamic-LDS attribute");
+    long rps;
+    const int ns = n_seq_splits(n_query, N, splits, &rps);
+    float* part_s = (float*)ws;
+    int* part_n = (int*)(part_s + (long)ns * n_query * k);
+    hipLaunchKernelGGL((compound_kernel<T, false>), dim3(cdiv(n_query, 4), (unsigned)ns), dim3(256), tile_bytes<T>(), st, (const T*)Tq,
+                       (const T*)Vn, Qt, N, t_off, role, (int)n_query, v_off, n_videos, veto, k, rps, q_scale, v_scale, part_s, part_n,
+                       (const int*)nullptr, (float*)nullptr, (int*)nullptr);
+    TAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_merge_kernel, dim3(cdiv(n_query, 4)), dim3(256), 0, st, part_s, part_n, n_query, k, ns, top_s, top_v);
+    TAN_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int compound_peaks_launch(const void* Tq, const void* Vn, long Qt, long N, const int* t_off, long n_query, const int* v_off, int n_videos,
+                          const int* hits, long P, float* peak_s, int* peak_n, hipStream_t st, const float* q_scale = nullptr,
+                          const float* v_scale = nullptr) {
+    hipLaunchKernelGGL((compound_kernel<T, true>), dim3((unsigned)P), dim3(256), tile_bytes<T>(), st, (const T*)Tq, (const T*)Vn, Qt, N,
+                       t_off, (const int*)nullptr, (int)n_query, v_off, n_videos, 0.0f, 0, 0L, q_scale, v_scale, (float*)nullptr,
+                       (int*)nullptr, hits, peak_s, peak_n);
     TAN_LAUNCH_CHECK();
     return 0;
 }
@@ -2131,6 +2356,62 @@ extern "C" int tan_clip_topk_e4m3(const void* Tq, const float* q_scale, const vo
                                   int* top_row, int* top_video, void* ws, void* stream) {
     return clip_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, c_off, n_clip, v_off, n_videos, k, splits, top_score, top_row,
                      top_video, ws, stream);
+}
+
+extern "C" long tan_compound_topk_ws_bytes(long n_query, long N, int k) {
+    if (n_query < 1 || n_query >= (1L << 29) || N < 1 || N >= (1L << 31) || k < 1 || k > KMAX) return TAN_ERR_BAD_ARG;
+    return max_splits(N) * n_query * k * 8;
+}
+
+static int compound_topk(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                  const int* t_off, const int* role, long n_query, const int* v_off, long n_videos, float veto, int k, int splits,
+                  float* top_score, int* top_video, void* ws, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && t_off && role && v_off && top_score && top_video && ws &&
+                (uintptr_t)ws % 16 == 0);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_query, n_videos) && k >= 1 && k <= KMAX && k <= n_videos && splits >= 0 && veto == veto);
+    return by_format(fmt, [&](auto r) {
+        return compound_topk_launch<typename decltype(r)::type>(Tq, Vn, Qt, N, t_off, role, n_query, v_off, (int)n_videos, veto, k, splits,
+                                                                top_score, top_video, ws, (hipStream_t)stream, q_scale, v_scale);
+    });
+}
+
+extern "C" int tan_compound_topk(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* t_off, const int* role,
+                                 long n_query, const int* v_off, long n_videos, float veto, int k, int splits, float* top_score,
+                                 int* top_video, void* ws, void* stream) {
+    return compound_topk(dtype, Tq, nullptr, Vn, nullptr, Qt, N, C, t_off, role, n_query, v_off, n_videos, veto, k, splits, top_score,
+                         top_video, ws, stream);
+}
+
+extern "C" int tan_compound_topk_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                                      const int* t_off, const int* role, long n_query, const int* v_off, long n_videos, float veto,
+                                      int k, int splits, float* top_score, int* top_video, void* ws, void* stream) {
+    return compound_topk(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, t_off, role, n_query, v_off, n_videos, veto, k, splits, top_score,
+                         top_video, ws, stream);
+}
+
+static int compound_peaks(int fmt, const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                   const int* t_off, long n_query, const int* v_off, long n_videos, const int* hits, long n_hits, float* peak_score,
+                   int* peak_row, void* stream) {
+    TAN_REQUIRE(rows_ok(fmt, Tq, q_scale, Vn, v_scale) && t_off && v_off && hits && peak_score && peak_row);
+    TAN_REQUIRE(seq_sizes_ok(Qt, N, C, n_query, n_videos) && n_hits >= 1 && n_hits < (1L << 26));
+    return by_format(fmt, [&](auto r) {
+        return compound_peaks_launch<typename decltype(r)::type>(Tq, Vn, Qt, N, t_off, n_query, v_off, (int)n_videos, hits, n_hits,
+                                                                 peak_score, peak_row, (hipStream_t)stream, q_scale, v_scale);
+    });
+}
+
+extern "C" int tan_compound_peaks(const void* Tq, const void* Vn, int dtype, long Qt, long N, int C, const int* t_off, long n_query,
+                                  const int* v_off, long n_videos, const int* hits, long n_hits, float* peak_score, int* peak_row,
+                                  void* stream) {
+    return compound_peaks(dtype, Tq, nullptr, Vn, nullptr, Qt, N, C, t_off, n_query, v_off, n_videos, hits, n_hits, peak_score, peak_row,
+                          stream);
+}
+
+extern "C" int tan_compound_peaks_e4m3(const void* Tq, const float* q_scale, const void* Vn, const float* v_scale, long Qt, long N, int C,
+                                       const int* t_off, long n_query, const int* v_off, long n_videos, const int* hits, long n_hits,
+                                       float* peak_score, int* peak_row, void* stream) {
+    return compound_peaks(FMT_E4M3, Tq, q_scale, Vn, v_scale, Qt, N, C, t_off, n_query, v_off, n_videos, hits, n_hits, peak_score,
+                          peak_row, stream);
 }
 
 extern "C" int tan_cover_max_rows(void) { return COVER_MAX; }

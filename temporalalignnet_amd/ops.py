@@ -344,6 +344,7 @@ local_align_ws_bytes = _bytes("local_align_ws_bytes")                # (P, sum_V
 local_align_path_ws_bytes = _bytes("local_align_path_ws_bytes")      # (P, sum_V, n_trace)
 sequence_topk_ws_bytes = _bytes("sequence_topk_ws_bytes")            # (n_seq, N, k)
 clip_topk_ws_bytes = _bytes("clip_topk_ws_bytes")                    # (n_clip, N, k)
+compound_topk_ws_bytes = _bytes("compound_topk_ws_bytes")            # (n_query, N, k)
 
 
 def _rows_args(what, tq, vn, q_scale, v_scale):
@@ -872,6 +873,61 @@ def clip_topk(tq, vn, c_off, v_off, k, *, q_scale=None, v_scale=None, splits=0, 
     _call("clip_topk", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(c_off), nc, _ptr(v_off), nv, k, splits, _f32(top_s),
           _ptr(top_r), _ptr(top_v), _ptr(ws))
     return top_s, top_r, top_v
+
+
+def _compound_args(what, tq, vn, t_off, role, v_off, q_scale, v_scale, check_offsets):
+    _sequence_args(what, tq, vn, t_off, v_off, q_scale, v_scale, check_offsets)
+    if role is None:
+        return
+    assert role.dtype == torch.int32 and role.shape == (tq.shape[0],) and role.is_contiguous()
+    if check_offsets:
+        r, t = role.cpu(), t_off.cpu().long()
+        if not bool(((r >= -1) & (r <= 31)).all()):
+            raise ValueError(f"{what}: role must lie in [-1, 31] (a clause, or -1 = banned)")
+        clause = torch.cat((torch.zeros(1, dtype=torch.long), torch.cumsum((r >= 0).long(), 0)))
+        if not bool((clause[t[1:]] > clause[t[:-1]]).all()):
+            raise ValueError(f"{what}: every query needs at least one clause term (role >= 0)")
+
+
+def compound_topk(tq, vn, t_off, role, v_off, k, *, veto=float("inf"), q_scale=None, v_scale=None, splits=0, check_offsets=False,
+                  out=None, ws=None):
+    """The k videos that satisfy each COMPOUND query best (tan_compound_topk / _e4m3; peak, clause, score and veto are defined in
+    include/tan_hip.h): tq [Qt, 512] holds the queries' terms one after the other, t_off [n_query + 1] int32 (device) each query's
+    first row, then Qt (1 to 32 terms each); role [Qt] int32 (device): the term's clause in [0, 31], or -1 = banned; vn / v_off /
+    q_scale / v_scale as for `rank_topk_video`.  A term's peak is its best score over the video's rows, a clause is worth its best
+    term (OR), a video its weakest clause (AND), and a video where a banned term's peak is >= veto is no candidate (NOT).
+    Returns (top_score [n_query, k] f32, top_video [n_query, k] int32), by descending score, equal scores by ascending video; with
+    fewer than k candidates the tail is (-inf, 0x7fffffff).  splits: 0 = automatic; the result does not depend on it.
+    check_offsets: verify t_off, role and v_off on the host (one synchronisation): 1 to 32 terms per query, roles in [-1, 31], at
+    least one clause term per query; otherwise they are the caller's contract.  out / ws: caller-owned outputs (the same 2-tuple)
+    and scratch (uint8, >= compound_topk_ws_bytes) instead of fresh ones.  ValueError: a NaN veto."""
+    _compound_args("compound_topk", tq, vn, t_off, role, v_off, q_scale, v_scale, check_offsets)
+    veto = float(veto)
+    if veto != veto:
+        raise ValueError("compound_topk: veto is NaN")
+    Qt, N, nq, nv, dev = tq.shape[0], vn.shape[0], t_off.numel() - 1, v_off.numel() - 1, tq.device
+    top_s, top_v = _lists(nq, k, dev) if out is None else out
+    ws = _scratch(ws, _lib.lib().tan_compound_topk_ws_bytes(nq, N, k), dev)
+    _call("compound_topk", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(t_off), _ptr(role), nq, _ptr(v_off), nv, veto, k, splits,
+          _f32(top_s), _ptr(top_v), _ptr(ws))
+    return top_s, top_v
+
+
+def compound_peaks(tq, vn, t_off, v_off, hits, *, q_scale=None, v_scale=None, check_offsets=False, out=None):
+    """(peak_score f32 [P, 32], peak_row int32 [P, 32]): for every hit h of hits [P, 2] int32 = (query, video), each term's peak
+    over the video and the first index row (global) that attains it, term t in column t -- the peaks `compound_topk` ranked by, bit
+    for bit (tan_compound_peaks / _e4m3).  Columns beyond the query's terms hold (-inf, 0x7fffffff).  out: caller-owned outputs
+    (the same 2-tuple).  Everything else as `compound_topk`."""
+    _compound_args("compound_peaks", tq, vn, t_off, None, v_off, q_scale, v_scale, check_offsets)
+    Qt, N, nq, nv, dev = tq.shape[0], vn.shape[0], t_off.numel() - 1, v_off.numel() - 1, tq.device
+    P = hits.shape[0]
+    assert hits.dtype == torch.int32 and hits.shape == (P, 2) and hits.is_contiguous()
+    peak_s, peak_r = _lists(P, 32, dev) if out is None else out
+    assert peak_s.dtype == torch.float32 and peak_r.dtype == torch.int32 and peak_s.shape == peak_r.shape == (P, 32)
+    assert peak_s.is_contiguous() and peak_r.is_contiguous()
+    _call("compound_peaks", tq, q_scale, vn, v_scale, Qt, N, tq.shape[1], _ptr(t_off), nq, _ptr(v_off), nv, _ptr(hits), P, _f32(peak_s),
+          _ptr(peak_r))
+    return peak_s, peak_r
 
 
 COVER_MAX_ROWS = 4096                                                 # tan_cover_max_rows(): the longest set of `cover_topk`

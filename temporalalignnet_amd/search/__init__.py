@@ -4,7 +4,7 @@ The reference's `get_visual_feature` "can be used for retrieval setting" (model/
 the dual encoder only about a video's own ASR sentences.  Here the video side is computed ONCE into a per-second index and any
 sentence is ranked against all of it.  One module per concern -- `index`, `text` (with what every search shares), `video`,
 `annotation`, `cluster`, `summary`, `cli` -- each with its own account of what it does; every public name is re-exported here, and only here.
-A search starts from a sentence (`search`, `search_moments`, `search_sequences`, `search_rerank`), from a vocabulary (`annotate`),
+A search starts from a sentence (`search`, `search_moments`, `search_sequences`, `search_compound`, `search_rerank`), from a vocabulary (`annotate`),
 from a piece of video (`search_clips`, `search_copies`, `align_paths`, `search_cover`) -- or from nothing: `discover_steps` clusters the index's
 seconds into the steps that recur in it, and its `StepClusters` serve as the vocabulary nobody had to write.  `storyboard` says what
 a video looks like: the k seconds that together cover it best; `chapters` says where its parts begin and end.
@@ -13,6 +13,7 @@ a video looks like: the k seconds that together cover it best; `chapters` says w
     python -m temporalalignnet_amd.search query --checkpoint C --vocab s3d_dict.npy --index I.npz -k 10 "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --moments [--width 0.07] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --sequence "crack two eggs" "whisk them" "pour into the pan"
+    python -m temporalalignnet_amd.search query ... --all "whisk eggs" "fry bacon|cook bacon" [--none "microwave" --veto 0.3] [-k K]
     python -m temporalalignnet_amd.search index ... --keep-stem;  ... query ... --rerank [--pool 32] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --index I0.npz --shard I1.npz --shard I2.npz [--host-resident] "crack two eggs" ...
     python -m temporalalignnet_amd.search query ... --only VID --only-file vids.txt --exclude VID --within VID:30-90 "crack two eggs" ...
@@ -40,8 +41,9 @@ from .cluster import MAX_CLUSTERS, StepClusters, centroid_image, discover_steps 
 from .index import E4M3, RowFilter, ShardedIndex, VideoIndex, _index_chunks, build_index, plan_index_windows, restrict_spans  # noqa: F401
 from .summary import (MAX_CHAPTER_K, MAX_CHAPTER_SECONDS, MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, Chapters,  # noqa: F401
                       Storyboard, chapters, plan_passes, storyboard, write_chapters_csv, write_storyboard_csv)
-from .text import (RERANK_TEXT_SLOTS, TEMPERATURE, Moment, Reranked, SequenceHit, _rerank_table,    # noqa: F401
-                   _Sweep, _TopLists, query_features, rerank_window, search, search_moments, search_rerank, search_sequences)
+from .text import (RERANK_TEXT_SLOTS, TEMPERATURE, Compound, CompoundHit, Moment, Reranked, SequenceHit, _rerank_table,  # noqa: F401
+                   _Sweep, _TopLists, compound_tables, compound_weakest, query_features, rerank_window, search, search_compound,
+                   search_moments, search_rerank, search_sequences)
 from .video import (EMPTY_ROW, MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, PIECE_ROWS, ClipHit, CopyHit,  # noqa: F401
                     CopyPath, CoverHit, align_paths, align_spans, align_tables, clip_features, clip_spans, copy_interval,
                     copy_inverse, copy_pieces, drop_source, path_tables, piece_offsets, search_clips, search_copies, search_cover,

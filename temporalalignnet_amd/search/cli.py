@@ -14,7 +14,7 @@ from .coarse import CoarseImage
 from .index import E4M3, ShardedIndex, VideoIndex, build_index
 from .summary import (MAX_CHAPTER_K, MAX_CHAPTER_SECONDS, MAX_STORYBOARD_K, MAX_STORYBOARD_SECONDS, chapters, storyboard,
                       write_chapters_csv, write_storyboard_csv)
-from .text import TEMPERATURE, search, search_moments, search_rerank, search_sequences
+from .text import TEMPERATURE, Compound, search, search_compound, search_moments, search_rerank, search_sequences
 from .video import MAX_ALIGN_SECONDS, MAX_CLIP_SECONDS, MAX_COVER_SECONDS, search_clips, search_copies, search_cover
 
 
@@ -60,6 +60,13 @@ def _parser():
     p.add_argument("--sequence", action="store_true",
                    help="the sentences are ONE ordered list of steps: the k videos that show them in order, each as "
                         "`vid score t_0 ... t_{m-1}` (seconds of the video, non-decreasing)")
+    p.add_argument("--all", action="store_true", dest="all_",
+                   help="the sentences are the clauses of ONE compound query, `|` between a clause's alternatives: the k videos that "
+                        "show every clause in whatever order, each as `vid score second:peak ...` (one pair per sentence, "
+                        "alternatives in place, then the --none ones)")
+    p.add_argument("--none", action="extend", nargs="+", default=None, metavar="S",
+                   help="with --all: a video where one of these sentences peaks at --veto or above is left out")
+    p.add_argument("--veto", type=float, default=None, help="with --none: the peak that bans a video (no default: its scale is the model's)")
     p.add_argument("--rerank", action="store_true",
                    help="two stages: the --pool best distinct videos of the dual sweep rescored by the joint encoder, the k best as "
                         "`sentence vid second score confidence alignability dual_second dual_score` (needs index --keep-stem)")
@@ -186,7 +193,17 @@ def _check_index(ap, a):
 
 def _check_query(ap, a):
     filtered = any(x is not None for x in (a.only, a.only_file, a.exclude, a.exclude_file, a.within))
+    clauses = [c.split("|") for c in a.sentences] if a.all_ else []
     _refuse(ap,
+            (a.all_ and (a.moments or a.sequence or a.rerank or a.coarse is not None or a.width is not None or a.pool is not None),
+             "--all does not go with --moments / --sequence / --rerank / --coarse"),
+            (a.all_ and filtered, "--all does not go with --only / --exclude / --within"),
+            (not a.all_ and (a.none is not None or a.veto is not None), "--none / --veto need --all"),
+            (a.none is not None and a.veto is None, "--none needs --veto"),
+            (a.veto is not None and a.none is None, "--veto needs --none"),
+            (a.veto is not None and a.veto != a.veto, "--veto must not be NaN"),
+            (any(not s.strip() for c in clauses for s in c), "--all: an empty alternative"),
+            (sum(len(c) for c in clauses) + len(a.none or ()) > 32, "--all takes at most 32 sentences, alternatives and --none included"),
             (a.sequence and (a.moments or a.width is not None), "--sequence does not go with --moments / --width"),
             (a.sequence and len(a.sentences) > 32, "--sequence takes at most 32 sentences"),
             (a.rerank and (a.sequence or a.moments), "--rerank does not go with --sequence / --moments"),
@@ -204,6 +221,7 @@ def _check_query(ap, a):
         a.within = None if a.within is None else [parse_within(w) for w in a.within]
     except ValueError as e:
         ap.error(str(e))
+    a.clauses = [[s.strip() for s in c] for c in clauses]
 
 
 def _check_annotate(ap, a):
@@ -448,7 +466,10 @@ def _run_annotate(a):
 def _run_query(a):
     model, embed, idx = _load_searcher(a)
     only = restrict_from_args(idx, a)                  # None with --sequence, which takes no filter options
-    if a.sequence:
+    if a.all_:
+        for h in search_compound(idx, model, embed, [Compound(a.clauses, a.none or ())], a.k, veto=a.veto)[0]:
+            print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(f"{t}:{p:.6f}" for t, p in zip(h.seconds, h.scores)))
+    elif a.sequence:
         for h in search_sequences(idx, model, embed, [a.sentences], a.k)[0]:
             print(f"{h.vid}\t{h.score:.6f}\t" + "\t".join(str(t) for t in h.seconds))
     elif a.rerank:

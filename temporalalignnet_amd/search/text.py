@@ -9,7 +9,10 @@
     index by the best non-decreasing assignment of seconds to an ordered list of sentences -- `tan_monotonic_decode`'s path, fused
     into the same matrix-free sweep -- and keeps the k best videos; `tan_sequence_scores` and the decode itself then give the
     winners' seconds (`query --sequence`).
-  * `search_rerank`: two stages.  The dual sweep (`tan_rank_topk_video`) proposes `pool` videos per sentence; one 64-second window
+  * `search_compound`: "which videos show this AND that, in whatever order, but NOT that?"  `tan_compound_topk` scores every video
+    of the index by the weakest of its clauses' peaks in the same matrix-free sweep, drops the videos a banned sentence matches,
+    and keeps the k best; `tan_compound_peaks` then gives the winners' per-sentence seconds and peaks (`query --all`).
+  * `search_rerank`: two stages. The dual sweep (`tan_rank_topk_video`) proposes `pool` videos per sentence; one 64-second window
     around each candidate's best second is cut out of the index's STEM store (`build_index(keep_stem=True)`: video_pre_proj of
     every second, the part of the video input that depends on neither window nor text), run through the joint stack
     (`TemporalAligner.joint_from_stem`) and reduced by `tan_rerank_tail` to the joint cosine, the second the joint encoder picks,
@@ -33,6 +36,10 @@ Moment = namedtuple("Moment", ("vid", "start", "end", "second", "score"))
 
 # one hit of `search_sequences`: the video, the second of every step (non-decreasing), and the path score
 SequenceHit = namedtuple("SequenceHit", ("vid", "seconds", "score"))
+
+# one hit of `search_compound`: the video, its score (the weakest clause), every term's best second of the video and its peak (in term
+# order, banned terms included), and the clause that set the score
+CompoundHit = namedtuple("CompoundHit", ("vid", "score", "seconds", "scores", "weakest"))
 
 # one hit of `search_rerank`: the video, the second / cosine / softmax confidence / alignability logit (None without the head) of the
 # joint encoder on the window around the dual encoder's best second, and that second and its dual score
@@ -295,6 +302,113 @@ def _sequence_seconds(sweep, feat, scale, s_off, v_off_dev, v_off, m, seq, video
                          _on_device(vtab, np.int32, dev), None, torch.empty(x.numel(), dtype=torch.int32, device=dev),
                          torch.empty(int(hv.sum()), device=dev), ts, path)
     return ts, first
+
+
+class Compound(namedtuple("Compound", ("all", "none"), defaults=((),))):
+    """One query of `search_compound`: `all` lists what the video must show -- each element a sentence, or a list of alternative
+    sentences (paraphrases: the best one counts) -- and `none` the sentences it must not show."""
+    __slots__ = ()
+
+
+def compound_tables(queries):
+    """The host tables of `search_compound`: (sentences: every query's terms one after the other -- its clauses' sentences in
+    clause order, then its banned ones --, t_off int64 [n + 1]: each query's first term, then their number, role int32 [terms]: the
+    term's clause (its position in `all`), or -1 = banned).  ValueError: a query without a clause, an empty clause, more than 32 terms."""
+    sentences, t_off, role = [], [0], []
+    for q in queries:
+        clauses = [[c] if isinstance(c, str) else list(c) for c in ([q.all] if isinstance(q.all, str) else q.all)]
+        if not clauses:
+            raise ValueError("search_compound: a query needs at least one clause in `all`")
+        if any(not c for c in clauses):
+            raise ValueError("search_compound: an empty clause in `all`")
+        banned = [q.none] if isinstance(q.none, str) else list(q.none)
+        if sum(len(c) for c in clauses) + len(banned) > 32:
+            raise ValueError("search_compound: a query holds at most 32 sentences, alternatives and banned ones included")
+        for j, c in enumerate(clauses):
+            sentences += c
+            role += [j] * len(c)
+        sentences += banned
+        role += [-1] * len(banned)
+        t_off.append(len(sentences))
+    return sentences, np.array(t_off, dtype=np.int64), np.array(role, dtype=np.int32)
+
+
+def compound_weakest(peaks, role):
+    """(score, clause): a video's compound score from its terms' peaks (f32 [m]) and their roles, by the definition of
+    include/tan_hip.h -- a clause is worth the first of its terms that none beats under >, the video the first clause, ascending,
+    that none undercuts under < -- and the clause that set it."""
+    score = weakest = None
+    for j in sorted({int(r) for r in role if r >= 0}):
+        g = None
+        for p, r in zip(peaks, role):
+            if r == j and (g is None or p > g):
+                g = p
+        if score is None or g < score:
+            score, weakest = g, j
+    return score, weakest
+
+
+@torch.no_grad()
+def search_compound(index, model, embed_text, queries, k=10, splits=0, veto=None):
+    """Per COMPOUND query -- `Compound(all=[...], none=[...])`: every element of `all` is a sentence or a list of alternative
+    sentences (one clause), `none` the banned sentences; 1 to 32 sentences in all -- the k videos that show EVERY clause, in whatever
+    order, and no banned sentence: [[CompoundHit(vid, score, seconds, scores, weakest)] ...] * len(queries), by descending score
+    (equal scores by video number).  A sentence's peak is its best second of the video (`search`'s score), a clause is worth its
+    best sentence, and `score` is the video's WEAKEST clause; a video where a banned sentence peaks at `veto` or above is left out,
+    so a list may be shorter than k.  `seconds` / `scores` hold every sentence's best second of the video and its peak, in the order
+    of `all` (alternatives in place) and then `none` -- the banned ones too: how close the video came to the veto.  `weakest` is
+    the position in `all` of the clause that set the score.  k is clamped to the number of videos and must lie in [1, 32].
+    veto has no default, like a threshold anywhere here: it is required with a `none` and refused without one.
+    `index`: a `VideoIndex`, or a `ShardedIndex` (device- or host-resident) -- then exactly what `VideoIndex.concat` of its shards
+    gives: one `tan_compound_topk` and one `tan_topk_fold` per shard, then `tan_compound_peaks` over the shards that hold winners.
+    Two read-backs: the winning videos, then scores and peaks.
+    There is no `restrict=` and no `coarse=` here: every video is scored whole by the exact sweep (whole-video filters for this
+    sweep are not built, and a coarse image proposes rows for one sentence, not videos for a conjunction)."""
+    queries = list(queries)
+    if not queries:
+        return []
+    sentences, t_off_h, role_h = compound_tables(queries)
+    banned = bool((role_h < 0).any())
+    if banned and veto is None:
+        raise ValueError("search_compound: `none` needs veto= (no default: its scale is the model's)")
+    if not banned and veto is not None:
+        raise ValueError("search_compound: veto= without any `none`")
+    if veto is not None and veto != veto:
+        raise ValueError("search_compound: veto is NaN")
+    k = _top_k("search_compound", k, len(index.vids))
+    n_query, dev = len(queries), index.device
+    t_off, role = _on_device(t_off_h, np.int32, dev), _on_device(role_h, np.int32, dev)
+    sweep = _Sweep(index, query_features(index, model, embed_text, sentences), splits=splits)
+    # phase 1: every shard's best videos, with row = the shard-local video number
+    top = _TopLists(index, n_query, k, 0)
+    for s, feat, scale, v_off in index.shard_views():
+        top.add(s, ops.compound_topk(sweep.tq, feat, t_off, role, v_off, min(k, v_off.numel() - 1),
+                                     veto=float("inf") if veto is None else float(veto), splits=splits, **sweep.scales(scale)))
+    shard, video = top.winners()                                           # read-back 1
+    # phase 2: the peaks, shard by shard over the shards that hold winners, each over its own hits; an empty slot is no hit
+    real = np.flatnonzero(video != 0x7fffffff)
+    query_of_hit = np.repeat(np.arange(n_query), k)[real]
+    parts = []
+    for at, s, feat, scale, v_off in hits_by_shard(index, shard[real]):
+        hits = _on_device(np.stack((query_of_hit[at], video[real][at]), 1), np.int32, dev)
+        parts.append((at, s, *ops.compound_peaks(sweep.tq, feat, t_off, v_off, hits, **sweep.scales(scale))))
+    score, *peaks = read_back([top.lists[0].view(torch.int32)] + [t.view(torch.int32) for part in parts for t in part[2:]])   # read-back 2
+    score = score.view(np.float32)
+    found = [[] for _ in range(n_query)]
+    rows = {}
+    for (at, s, *_), ps, pr in zip(parts, peaks[0::2], peaks[1::2]):
+        first = index.shards[s].v_off[video[real][at]]
+        for j, h in enumerate(at):
+            rows[real[h]] = (ps.view(np.float32).reshape(-1, 32)[j], pr.reshape(-1, 32)[j] - first[j])
+    gv, _ = _locate_videos(index, shard[real], video[real])
+    for h, slot in enumerate(real):                                        # ascending: every query's hits in rank order
+        q = query_of_hit[h]
+        m = int(t_off_h[q + 1] - t_off_h[q])
+        ps, sec = rows[slot]
+        _, weakest = compound_weakest(ps[:m], role_h[t_off_h[q]:t_off_h[q + 1]])
+        found[q].append(CompoundHit(index.vids[gv[h]], float(score[slot]), tuple(int(t) for t in sec[:m]),
+                                    tuple(float(p) for p in ps[:m]), weakest))
+    return found
 
 
 def rerank_window(sec, vlen, seq_len=64):
